@@ -16,6 +16,7 @@ decoder's P halo and its gradient (on a side stream, under the decoder passes), 
 one flat 216 KB gradient all-reduce (pangnn_amd/dist.py; `exchange="allgather"` is the dense-halo alternative).
 
 One JSON line on rank 0: value = supervised similarity edges per second over the whole job.
+`--dump-outputs DIR` (one process): the loss, logits and parameters of the last timed step as DIR/<name>.npy (dump_outputs).
 """
 import argparse
 import contextlib
@@ -55,6 +56,32 @@ S_BINDS = ("vector-instruction issue PLUS matrix-pipe time (557 vector incl. 84 
            "neither hides the other — profiles/r04y_pmc_sq_decoder16.txt, r04q_s_kernel_schedule_and_p3_experiments.txt, "
            "r04_decoder_instruction_budget.txt), not the matrix pipe alone (43 % busy) nor HBM (fabric traffic = 0.48 x the "
            "algorithmic bytes)")
+
+
+DUMP_BYTES = 48 << 20        # --dump-outputs: array bytes in all (under the 64 MB cap with room for the .npy headers)
+DUMP_SEED = 20240229         # positions of the fixed sample taken of an array too large for its share
+
+
+def dump_outputs(path, loss, logits, model, budget=DUMP_BYTES):
+    """--dump-outputs: what the last timed step handed its caller — the loss, the logits and the parameters the optimizer
+    step left — as float32 `path/<name>.npy` (parameters as `param.<name>.npy`), so that two builds run with the same
+    arguments can be compared output for output.  Arrays are taken whole, smallest first, while they fit an equal share of
+    what is left of `budget`; a larger one is flattened and replaced by its elements at `share` sorted positions drawn
+    with replacement from a CPU generator seeded with DUMP_SEED (the same positions in every run of the same shapes)."""
+    import numpy as np
+    arrays = {"loss": loss, "logits": logits}
+    arrays.update(("param." + k, p) for k, p in model.named_parameters())
+    os.makedirs(path, exist_ok=True)
+    left = budget // 4
+    items = sorted(arrays.items(), key=lambda kv: kv[1].numel())
+    for i, (name, t) in enumerate(items):
+        t = t.detach()
+        share = left // (len(items) - i)
+        if t.numel() > share:
+            pos = torch.randint(t.numel(), (share,), generator=torch.Generator().manual_seed(DUMP_SEED)).sort().values
+            t = t.reshape(-1)[pos.to(t.device)]
+        left -= t.numel()
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
 
 
 def spmm_alg_bytes(e, n, f, s=4):
@@ -151,10 +178,11 @@ def cpu_baseline(args, d, h):
                       f"train steps of oracle/gcn_oracle.py, {dt / steps * 1e3:.0f} ms/step"}
 
 
-def minibatch_line(workload, dev, steps, warmup_min, seed=0, genes=None):
+def minibatch_line(workload, dev, steps, warmup_min, seed=0, genes=None, dump=None):
     """the reference's own regime (pangnn.py:152-216): DataLoader(batch_size=32) over per-group sub-graphs, one train step
     per mini-batch.  cfg2mb: one captured HIP graph per batch, replayed; cfg2mb_fresh: a fresh Batch every step (collation,
-    both CSR orders, degree norms, run-sum plans, the first layer's r / s inside the timed step)."""
+    both CSR orders, degree norms, run-sum plans, the first layer's r / s inside the timed step).  `dump`: directory for
+    dump_outputs of the last timed step."""
     import pangnn_amd
     from pangnn_amd import simulate
     from pangnn_amd.train import make_optimizer, train_step
@@ -210,11 +238,13 @@ def minibatch_line(workload, dev, steps, warmup_min, seed=0, genes=None):
     t0 = time.perf_counter()
     edges = 0
     for k in range(steps):
-        loss, _ = steps_fn[k % len(batches)]()
+        loss, out = steps_fn[k % len(batches)]()
         edges += edge_counts[k % len(batches)]
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     gc.unfreeze()
+    if dump:
+        dump_outputs(dump, loss, out, model)
     return {"metric": "edges/sec in GNN forward+backward (link-pred train step)", "value": edges / dt,
             "unit": "edges/s", "n_gpus": 1, "steps": steps, "warmup": warmup,
             "ms_per_step": dt / steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -231,7 +261,8 @@ def minibatch_line(workload, dev, steps, warmup_min, seed=0, genes=None):
 
 
 def minibatch_bench(args, dev, json_fd):
-    line = minibatch_line(args.workload, dev, args.steps, args.warmup, seed=args.seed, genes=args.genes)
+    line = minibatch_line(args.workload, dev, args.steps, args.warmup, seed=args.seed, genes=args.genes,
+                          dump=args.dump_outputs)
     os.write(json_fd, (json.dumps(line) + "\n").encode())
 
 
@@ -412,7 +443,15 @@ def main():
                          "the halo exchange is a self-exchange of the true row counts over RCCL: dist.HaloPlan._emulate)")
     ap.add_argument("--of", type=int, default=8, help="world size the emulated rank belongs to")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (loss, logits) and the parameters it left "
+                         "as DIR/<name>.npy, float32, at most 64 MB in all (a fixed seeded sample of a larger array); "
+                         "single-process runs only")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.gpus != 1 or args.emulate_rank is not None):
+        ap.error("--dump-outputs needs --gpus 1 and no --emulate-rank")
 
     # stdout carries exactly ONE JSON line: everything native libraries print there (RCCL's version
     # banner at communicator creation) is sent to stderr instead
@@ -557,12 +596,14 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss, _ = step_fn()
+        loss, out = step_fn()
     torch.cuda.synchronize()
     if world > 1:
         torch.distributed.barrier()
     dt = time.perf_counter() - t0
     timer, PF.KERNEL_TIMER = PF.KERNEL_TIMER, None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, loss, out, model)
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         all_reduce_(t, torch.distributed.ReduceOp.MAX)
