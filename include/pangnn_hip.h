@@ -551,6 +551,54 @@ int    pangnn_softmax_qscore_f64(const int64_t* rowptr, const double* score, int
 int    pangnn_scale_unless_one_f32(float* const* ptrs, const int64_t* counts, int32_t n_tensors, const float* scale,
                                    pangnn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The weightless link decoders, src/gnn.py:171-180,202-207 (`--decoder cosine` / `dotproduct`; pangnn_amd/gnn.py
+ * AlternateGCN.cosine_sim / decode), as per-edge reductions over two gathered rows — no [E, 2D] edge tensor:
+ *   mode PANGNN_SCORE_DOT:    logit_e = z[src_e] . z[dst_e]
+ *   mode PANGNN_SCORE_COSINE: logit_e = torch.nn.functional.cosine_similarity(z[src_e], z[dst_e], dim=1, eps=1e-8)
+ *                             = sum_k (a_k / max(|a|, eps)) (b_k / max(|b|, eps))
+ * z [num_nodes, d] (row stride ldz elements, a multiple of 4) is read as stored: z_dtype = PANGNN_DTYPE_F32 (rows on 16
+ * bytes), _BF16 or _F16 (rows on 8 bytes); every product and sum is fp32, so 2-byte rows give the bits of the f32 call on the
+ * up-converted rows.  d in {16, 32, 64, 128, 256} (pangnn_edge_score_supported); any other d: PANGNN_E_BADARG.
+ * edge_index[2][ld] int64, edges in the caller's order; node ids must lie in [0, num_nodes).
+ * norms [num_nodes][2] (cosine; unused and nullable for dot) is WRITTEN by the forward entries — (1 / max(|z_n|, eps),
+ * 1 / (max(|z_n|, eps) |z_n|), the latter 0 for a zero row) — and READ by the backward.
+ * All results are reproducible bit for bit (fixed reduction orders, no atomics).
+ * ---------------------------------------------------------------------------------------- */
+#define PANGNN_SCORE_DOT    0
+#define PANGNN_SCORE_COSINE 1
+#define PANGNN_EDGE_SCORE_LOSS_PARTS 4096   /* floats of the loss_parts scratch of pangnn_edge_score_loss_mixed */
+int    pangnn_edge_score_supported(int32_t d);
+int    pangnn_edge_score_mixed(const void* z, int32_t z_dtype, int64_t ldz, int64_t num_nodes, const int64_t* edge_index,
+                               int64_t ld, int64_t num_edges, int32_t d, int32_t mode, float* norms, float* logits,
+                               pangnn_stream_t stream);
+/* Forward with BCEWithLogitsLoss(pos_weight), mean over `denom`, in the same pass (parameterisation of pangnn_bce_logits_f32):
+ * logits[E], loss[1], g_logits[E] = dL/dlogit (NOT multiplied by any upstream gradient).  pos_weight: device scalar, nullable
+ * (= 1).  loss_parts: scratch of PANGNN_EDGE_SCORE_LOSS_PARTS floats (per-block partial sums, added in index order). */
+int    pangnn_edge_score_loss_mixed(const void* z, int32_t z_dtype, int64_t ldz, int64_t num_nodes, const int64_t* edge_index,
+                                    int64_t ld, int64_t num_edges, int32_t d, int32_t mode, const float* y,
+                                    const float* pos_weight, int64_t denom, float* norms, float* logits, float* loss,
+                                    float* g_logits, float* loss_parts, pangnn_stream_t stream);
+/* Backward: gz[n] (fp32, row stride ldg, 16-byte aligned) = g_scale[0] * dL/dz[n], written once per node, with g[E] = dL/dlogit
+ * in edge order and g_scale a DEVICE scalar (nullable = 1: `loss.backward()` needs no host read of the upstream gradient):
+ *   dot:    sum_{out-edges e=(n,m)} g_e z_m + sum_{in-edges e=(m,n)} g_e z_m
+ *   cosine: inv_n sum_{e at n} g_e inv_m z_m - z_n k_n sum_{e at n} g_e cos_e    (inv, k: the two norms entries, cos = logits)
+ * The out-edges come from the by-source CSR (rowptr_src / other_src / perm_src of pangnn_csr_build(group_by = 0)), the in-edges
+ * from the by-target CSR; per-edge scalars are read through perm.  A CSR order with hub rows may be passed as segments
+ * (seg_ptr [num_seg + 1], parts_rowptr [num_nodes + 1], as pangnn_amd/graph.py CSR.long_rows builds them; both NULL: none):
+ * one wave per segment writes a partial row into parts [num_seg * (d + 1)] floats (16-byte aligned), and the node's wave adds
+ * its segments' partials in a fixed order.  logits / norms: what the forward wrote (cosine; nullable for dot). */
+int    pangnn_edge_score_bwd_mixed(const void* z, int32_t z_dtype, int64_t ldz, int64_t num_nodes, int64_t num_edges, int32_t d,
+                                   int32_t mode,
+                                   const int64_t* rowptr_src, const int32_t* other_src, const int32_t* perm_src,
+                                   const int64_t* seg_ptr_src, const int64_t* parts_rowptr_src, int64_t num_seg_src,
+                                   float* parts_src,
+                                   const int64_t* rowptr_dst, const int32_t* other_dst, const int32_t* perm_dst,
+                                   const int64_t* seg_ptr_dst, const int64_t* parts_rowptr_dst, int64_t num_seg_dst,
+                                   float* parts_dst,
+                                   const float* g, const float* logits, const float* norms, const float* g_scale, float* gz,
+                                   int64_t ldg, pangnn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

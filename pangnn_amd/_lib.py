@@ -108,6 +108,16 @@ SIGNATURES = {
     "pangnn_decoder_dgrad_f32": (C.c_int, [_p, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _p, _sz, _p]),
     # (host array of device pointers, host array of element counts, n_tensors, device scalar, stream)
     "pangnn_scale_unless_one_f32": (C.c_int, [_p, _p, _i32, _p, _p]),
+    # weightless link decoders (csrc/edge_score.hip): (z, z_dtype, ldz, num_nodes, edge_index, ld, num_edges, d, mode, ...)
+    "pangnn_edge_score_supported": (C.c_int, [_i32]),
+    "pangnn_edge_score_mixed": (C.c_int, [_p, _i32, _i64, _i64, _p, _i64, _i64, _i32, _i32, _p, _p, _p]),
+    "pangnn_edge_score_loss_mixed": (C.c_int, [_p, _i32, _i64, _i64, _p, _i64, _i64, _i32, _i32,
+                                               _p, _p, _i64,                            # y, pos_weight, denom
+                                               _p, _p, _p, _p, _p, _p]),                # norms, logits, loss, g_logits, parts, stream
+    "pangnn_edge_score_bwd_mixed": (C.c_int, [_p, _i32, _i64, _i64, _i64, _i32, _i32,
+                                              _p, _p, _p, _p, _p, _i64, _p,            # by source (+ segments, parts)
+                                              _p, _p, _p, _p, _p, _i64, _p,            # by target
+                                              _p, _p, _p, _p, _p, _i64, _p]),          # g, logits, norms, g_scale, gz, ldg, stream
 }
 
 ABI_VERSION = 3          # PANGNN_ABI_VERSION of include/pangnn_hip.h this binding was written against

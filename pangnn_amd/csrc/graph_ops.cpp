@@ -1,5 +1,6 @@
 // The per-step operators that READ A GRAPH, in C++ end to end (round 5):
-//   gcn_propagate, embed_conv_in, embed_conv_in_linear, embed_propagate, decoder_loss, decoder_mlp and their backward ops
+//   gcn_propagate, embed_conv_in, embed_conv_in_linear, embed_propagate, decoder_loss, decoder_mlp, edge_score, edge_score_loss
+//   and their backward ops
 // — schema, HIP ("CUDA" key) implementation and autograd formula (torch::autograd::Function under the Autograd key), like
 // pangnn::linear.  Rounds 3-4 registered them from Python over ctypes because the structure cache lived in Python.
 //
@@ -757,6 +758,100 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tenso
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// weightless link decoders (--decoder cosine / dotproduct): csrc/edge_score.hip.  `norms` [N, 2] (cosine; [0, 2] for dot) is
+// what the forward computed per node and the backward reads again.
+// ---------------------------------------------------------------------------------------------------------------
+at::Tensor score_rows(const char* op, const at::Tensor& z, int64_t mode) {
+  on_gpu(z, "z");
+  TORCH_CHECK(z.dim() == 2 && z.is_floating_point(), "pangnn::", op, ": z must be a floating-point [N, D] tensor");
+  TORCH_CHECK(mode == PANGNN_SCORE_DOT || mode == PANGNN_SCORE_COSINE, "pangnn::", op, ": mode is 0 (dot) or 1 (cosine)");
+  TORCH_CHECK(pangnn_edge_score_supported((int32_t)z.size(1)), "pangnn::", op, ": D must be 16, 32, 64, 128 or 256, got ", z.size(1));
+  return rows_any(z);
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> score_forward(const char* op, const at::Tensor& z,
+                                                                         const at::Tensor& edge_index, int64_t mode,
+                                                                         const c10::optional<at::Tensor>& y,
+                                                                         const c10::optional<at::Tensor>& pos_weight, int64_t denom) {
+  const at::Tensor zr = score_rows(op, z, mode);
+  const DeviceGuard guard(z.device());
+  const int64_t n = zr.size(0);
+  const View v = lookup(op, edge_index, n, c10::nullopt, c10::nullopt, kEntry);
+  const int64_t e = v.num_edges;
+  auto fo = zr.options().dtype(at::kFloat);
+  at::Tensor logits = at::empty({e}, fo), norms = at::empty({mode == PANGNN_SCORE_COSINE ? n : 0, 2}, fo);
+  float* nrm = mode == PANGNN_SCORE_COSINE ? norms.data_ptr<float>() : nullptr;
+  if (!defined(y)) {
+    check_rc(pangnn_edge_score_mixed(zr.data_ptr(), dtype_code(zr), zr.stride(0), n, v.ei.data_ptr<int64_t>(), e, e,
+                                     (int32_t)zr.size(1), (int32_t)mode, nrm, logits.data_ptr<float>(), stream_of(z)),
+             "pangnn_edge_score_mixed");
+    return {logits, norms, at::Tensor(), at::Tensor()};
+  }
+  const at::Tensor yy = f32c(*y);
+  c10::optional<at::Tensor> pw;
+  if (defined(pos_weight)) pw = f32c(*pos_weight).reshape({-1});
+  at::Tensor loss = at::empty({1}, fo), g_logits = at::empty({e}, fo), parts = at::empty({PANGNN_EDGE_SCORE_LOSS_PARTS}, fo);
+  check_rc(pangnn_edge_score_loss_mixed(zr.data_ptr(), dtype_code(zr), zr.stride(0), n, v.ei.data_ptr<int64_t>(), e, e,
+                                        (int32_t)zr.size(1), (int32_t)mode, yy.data_ptr<float>(), opt_ptr<float>(pw), denom, nrm,
+                                        logits.data_ptr<float>(), loss.data_ptr<float>(), g_logits.data_ptr<float>(),
+                                        parts.data_ptr<float>(), stream_of(z)),
+           "pangnn_edge_score_loss_mixed");
+  return {logits, norms, loss.view(at::IntArrayRef{}), g_logits};
+}
+
+std::tuple<at::Tensor, at::Tensor> edge_score(const at::Tensor& z, const at::Tensor& edge_index, int64_t mode) {
+  auto r = score_forward("edge_score", z, edge_index, mode, c10::nullopt, c10::nullopt, 1);
+  return {std::get<0>(r), std::get<1>(r)};
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> edge_score_loss(const at::Tensor& z, const at::Tensor& edge_index,
+                                                                           int64_t mode, const at::Tensor& y,
+                                                                           const c10::optional<at::Tensor>& pos_weight,
+                                                                           int64_t denom) {
+  operand_any_float("edge_score_loss", "y", y, z);
+  operand_any_float("edge_score_loss", "pos_weight", pos_weight, z);
+  TORCH_CHECK(y.dim() == 1 && y.size(0) == edge_index.size(1) && denom > 0, "pangnn::edge_score_loss: y must be [E], denom > 0");
+  auto [logits, norms, loss, g_logits] = score_forward("edge_score_loss", z, edge_index, mode, y, pos_weight, denom);
+  return {loss, logits, g_logits, norms};
+}
+
+// dL/dz in z's dtype: one wave per node over its out- and in-edges (hub rows as segments), times the device scalar g_scale
+at::Tensor edge_score_backward(const at::Tensor& g, const at::Tensor& z, const at::Tensor& edge_index, const at::Tensor& logits,
+                               const at::Tensor& norms, const c10::optional<at::Tensor>& g_scale, int64_t mode) {
+  const char* op = "edge_score_backward";
+  const at::Tensor zr = score_rows(op, z, mode);
+  TORCH_CHECK(g.is_cuda() && g.device() == z.device() && g.dim() == 1 && g.size(0) == edge_index.size(1),
+              "pangnn::edge_score_backward: g must be [E] on ", z.device());
+  const DeviceGuard guard(z.device());
+  const int64_t n = zr.size(0), d = zr.size(1);
+  const View v = lookup(op, edge_index, n, c10::nullopt, c10::nullopt, kByDst | kBySrc);
+  const int64_t e = v.num_edges;
+  const bool cos = mode == PANGNN_SCORE_COSINE;
+  TORCH_CHECK(!cos || (logits.numel() == e && norms.numel() == 2 * n), "pangnn::edge_score_backward: cosine needs the forward's "
+              "logits [E] and norms [N, 2]");
+  const at::Tensor gg = f32c(g);
+  const at::Tensor lg = cos ? f32c(logits) : at::Tensor(), nm = cos ? f32c(norms) : at::Tensor();
+  c10::optional<at::Tensor> sc;
+  if (defined(g_scale)) sc = f32c(*g_scale).reshape({-1});
+  auto fo = zr.options().dtype(at::kFloat);
+  auto parts_of = [&](const Csr& c) { return c.seg_ptr.defined() ? at::empty({(c.seg_ptr.size(0) - 1) * (d + 1)}, fo) : at::Tensor(); };
+  const at::Tensor ps = parts_of(v.by_src), pd = parts_of(v.by_dst);
+  auto p64 = [](const at::Tensor& t) { return t.defined() ? t.data_ptr<int64_t>() : nullptr; };
+  auto pf = [](const at::Tensor& t) { return t.defined() ? t.data_ptr<float>() : nullptr; };
+  auto nseg = [](const Csr& c) { return c.seg_ptr.defined() ? c.seg_ptr.size(0) - 1 : (int64_t)0; };
+  at::Tensor gz = at::empty({n, d}, fo);
+  check_rc(pangnn_edge_score_bwd_mixed(
+               zr.data_ptr(), dtype_code(zr), zr.stride(0), n, e, (int32_t)d, (int32_t)mode,
+               v.by_src.rowptr.data_ptr<int64_t>(), v.by_src.other.data_ptr<int32_t>(), v.by_src.perm.data_ptr<int32_t>(),
+               p64(v.by_src.seg_ptr), p64(v.by_src.parts_rowptr), nseg(v.by_src), pf(ps),
+               v.by_dst.rowptr.data_ptr<int64_t>(), v.by_dst.other.data_ptr<int32_t>(), v.by_dst.perm.data_ptr<int32_t>(),
+               p64(v.by_dst.seg_ptr), p64(v.by_dst.parts_rowptr), nseg(v.by_dst), pf(pd),
+               gg.data_ptr<float>(), pf(lg), pf(nm), opt_ptr<float>(sc), gz.data_ptr<float>(), d, stream_of(z)),
+           "pangnn_edge_score_bwd_mixed");
+  return z.scalar_type() == at::kFloat ? gz : gz.to(z.scalar_type());
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // autograd formulas (Autograd key): forward redispatches below autograd, backward calls the registered backward op — a
 // tracer sees both
 // ---------------------------------------------------------------------------------------------------------------
@@ -988,6 +1083,61 @@ at::Tensor decoder_mlp_autograd(const at::Tensor& pq, const at::Tensor& edge_ind
   return DecoderMlpFunction::apply(pq, edge_index, extra, cvec, w2, b2, w3, b3);
 }
 
+using EdgeScoreBwd = at::Tensor(const at::Tensor&, const at::Tensor&, const at::Tensor&, const at::Tensor&, const at::Tensor&,
+                                const OptT&, int64_t);
+
+class EdgeScoreFunction : public torch::autograd::Function<EdgeScoreFunction> {
+ public:
+  static variable_list forward(AutogradContext* ctx, const at::Tensor& z, const at::Tensor& edge_index, int64_t mode) {
+    at::AutoDispatchBelowADInplaceOrView below;
+    static auto op = typed_op<std::tuple<at::Tensor, at::Tensor>(const at::Tensor&, const at::Tensor&, int64_t)>("pangnn::edge_score");
+    auto [logits, norms] = op.call(z, edge_index, mode);
+    ctx->save_for_backward({z, edge_index, logits, norms});
+    ctx->saved_data["mode"] = mode;
+    ctx->mark_non_differentiable({norms});
+    return {logits, norms};
+  }
+  static variable_list backward(AutogradContext* ctx, variable_list grads) {
+    const auto s = ctx->get_saved_variables();
+    static auto op = typed_op<EdgeScoreBwd>("pangnn::edge_score_backward");
+    return {op.call(grads[0], s[0], s[1], s[2], s[3], c10::nullopt, ctx->saved_data["mode"].toInt()), at::Tensor(), at::Tensor()};
+  }
+};
+std::tuple<at::Tensor, at::Tensor> edge_score_autograd(const at::Tensor& z, const at::Tensor& edge_index, int64_t mode) {
+  auto o = EdgeScoreFunction::apply(z, edge_index, mode);
+  return {o[0], o[1]};
+}
+
+// the fused loss keeps dL/dlogit from its forward; backward is ONE node pass scaled by the upstream gradient read on the device
+class EdgeScoreLossFunction : public torch::autograd::Function<EdgeScoreLossFunction> {
+ public:
+  static variable_list forward(AutogradContext* ctx, const at::Tensor& z, const at::Tensor& edge_index, int64_t mode,
+                               const at::Tensor& y, const OptT& pos_weight, int64_t denom) {
+    at::AutoDispatchBelowADInplaceOrView below;
+    static auto op = typed_op<std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor>(
+        const at::Tensor&, const at::Tensor&, int64_t, const at::Tensor&, const OptT&, int64_t)>("pangnn::edge_score_loss");
+    auto [loss, logits, g_logits, norms] = op.call(z, edge_index, mode, y, pos_weight, denom);
+    ctx->save_for_backward({z, edge_index, logits, g_logits, norms});
+    ctx->saved_data["mode"] = mode;
+    ctx->mark_non_differentiable({logits, g_logits, norms});
+    return {loss, logits, g_logits, norms};
+  }
+  static variable_list backward(AutogradContext* ctx, variable_list grads) {
+    variable_list out(6);
+    if (!grads[0].defined()) return out;
+    const auto s = ctx->get_saved_variables();
+    static auto op = typed_op<EdgeScoreBwd>("pangnn::edge_score_backward");
+    out[0] = op.call(s[3], s[0], s[1], s[2], s[4], OptT(grads[0]), ctx->saved_data["mode"].toInt());
+    return out;
+  }
+};
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> edge_score_loss_autograd(const at::Tensor& z, const at::Tensor& edge_index,
+                                                                                    int64_t mode, const at::Tensor& y,
+                                                                                    const OptT& pos_weight, int64_t denom) {
+  auto o = EdgeScoreLossFunction::apply(z, edge_index, mode, y, pos_weight, denom);
+  return {o[0], o[1], o[2], o[3]};
+}
+
 }  // namespace
 
 TORCH_LIBRARY_FRAGMENT(pangnn, m) {
@@ -1022,6 +1172,11 @@ TORCH_LIBRARY_FRAGMENT(pangnn, m) {
   m.def("decoder_mlp(Tensor pq, Tensor edge_index, Tensor? extra, Tensor? cvec, Tensor w2, Tensor b2, Tensor w3, Tensor b3) -> Tensor");
   m.def("decoder_mlp_backward(Tensor g, Tensor pq, Tensor edge_index, Tensor? extra, Tensor? cvec, Tensor w2, Tensor b2, Tensor w3, "
         "Tensor b3) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
+  // weightless link decoders: mode 0 = dot, 1 = cosine; norms [N, 2] (cosine) / [0, 2] (dot) feed the backward
+  m.def("edge_score(Tensor z, Tensor edge_index, int mode) -> (Tensor, Tensor)");
+  m.def("edge_score_backward(Tensor g, Tensor z, Tensor edge_index, Tensor logits, Tensor norms, Tensor? g_scale, int mode) -> Tensor");
+  m.def("edge_score_loss(Tensor z, Tensor edge_index, int mode, Tensor y, Tensor? pos_weight, int denom) -> "
+        "(Tensor, Tensor, Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(pangnn, CompositeExplicitAutograd, m) {
@@ -1047,6 +1202,9 @@ TORCH_LIBRARY_IMPL(pangnn, CUDA, m) {
   m.impl("decoder_loss", &decoder_loss);
   m.impl("decoder_mlp", &decoder_mlp);
   m.impl("decoder_mlp_backward", &decoder_mlp_backward);
+  m.impl("edge_score", &edge_score);
+  m.impl("edge_score_backward", &edge_score_backward);
+  m.impl("edge_score_loss", &edge_score_loss);
 }
 
 TORCH_LIBRARY_IMPL(pangnn, Autograd, m) {
@@ -1056,4 +1214,6 @@ TORCH_LIBRARY_IMPL(pangnn, Autograd, m) {
   m.impl("embed_propagate", &embed_propagate_autograd);
   m.impl("decoder_loss", &decoder_loss_autograd);
   m.impl("decoder_mlp", &decoder_mlp_autograd);
+  m.impl("edge_score", &edge_score_autograd);
+  m.impl("edge_score_loss", &edge_score_loss_autograd);
 }

@@ -873,6 +873,130 @@ def decoder_loss_pq(pq, st, extra, cvec, w2, b2, w3, b3, y, pos_weight, denom, l
     return _DecoderLoss.apply(pq, None, st, extra, cvec, w2, b2, w3, b3, y, pos_weight, denom, True, live)
 
 
+# ---- weightless link decoders (--decoder cosine / dotproduct, gnn.py:171-180,202-207): csrc/edge_score.hip
+SCORE_MODES = {"dot": 0, "cosine": 1}      # PANGNN_SCORE_DOT / PANGNN_SCORE_COSINE
+
+
+@torch.compiler.assume_constant_result
+def edge_score_supported(d: int) -> bool:
+    """pangnn_edge_score_supported(d): D in {16, 32, 64, 128, 256}"""
+    return bool(_lib.load().pangnn_edge_score_supported(int(d)))
+
+
+def _score_fwd(z, st: EdgeStructure, mode: int, y=None, pw=None, denom=0):
+    """(logits, norms, loss, g_logits) of pangnn_edge_score[_loss]_mixed on rows as stored"""
+    lib = _lib.load()
+    e, n, d = st.num_edges, z.shape[0], z.shape[1]
+    dev = z.device
+    logits = torch.empty(e, dtype=torch.float32, device=dev)
+    norms = torch.empty(n if mode == 1 else 0, 2, dtype=torch.float32, device=dev)
+    nrm = norms.data_ptr() if mode == 1 else None
+    with _lib.device_guard(dev):
+        if y is None:
+            _lib.check(lib.pangnn_edge_score_mixed(z.data_ptr(), _dt(z), z.stride(0), n, st.edge_index.data_ptr(), e, e, d, mode,
+                                                   nrm, logits.data_ptr(), _lib.stream_ptr()), "pangnn_edge_score_mixed")
+            return logits, norms, None, None
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        g_logits = torch.empty(e, dtype=torch.float32, device=dev)
+        parts = torch.empty(_SCORE_LOSS_PARTS, dtype=torch.float32, device=dev)
+        _lib.check(lib.pangnn_edge_score_loss_mixed(z.data_ptr(), _dt(z), z.stride(0), n, st.edge_index.data_ptr(), e, e, d, mode,
+                                                    y.data_ptr(), _lib.ptr(pw), int(denom), nrm, logits.data_ptr(),
+                                                    loss.data_ptr(), g_logits.data_ptr(), parts.data_ptr(), _lib.stream_ptr()),
+                   "pangnn_edge_score_loss_mixed")
+    return logits, norms, loss.view(()), g_logits
+
+
+_SCORE_LOSS_PARTS = 4096    # PANGNN_EDGE_SCORE_LOSS_PARTS
+
+
+def _score_bwd(z, st: EdgeStructure, mode: int, g, logits, norms, g_scale=None):
+    """dL/dz (fp32) of pangnn_edge_score_bwd_mixed: one wave per node over both CSR orders, hub rows as segments"""
+    lib = _lib.load()
+    n, d, e = z.shape[0], z.shape[1], st.num_edges
+    dev = z.device
+    gz = torch.empty(n, d, dtype=torch.float32, device=dev)
+    args, keep = [], []
+    for csr in (st.by_src, st.by_dst):
+        args += [csr.rowptr.data_ptr(), csr.other.data_ptr(), csr.perm.data_ptr()]
+        long = csr.long_rows()
+        if long is None:
+            args += [None, None, 0, None]
+        else:
+            seg_ptr, parts_rowptr = long
+            nseg = seg_ptr.shape[0] - 1
+            keep.append(torch.empty(nseg * (d + 1), dtype=torch.float32, device=dev))   # partial rows of the segments
+            args += [seg_ptr.data_ptr(), parts_rowptr.data_ptr(), nseg, keep[-1].data_ptr()]
+    with _lib.device_guard(dev):
+        _lib.check(lib.pangnn_edge_score_bwd_mixed(z.data_ptr(), _dt(z), z.stride(0), n, e, d, mode, *args, g.data_ptr(),
+                                                   _lib.ptr(logits if mode == 1 else None), _lib.ptr(norms if mode == 1 else None),
+                                                   _lib.ptr(g_scale), gz.data_ptr(), d, _lib.stream_ptr()),
+                   "pangnn_edge_score_bwd_mixed")
+    return gz
+
+
+class _EdgeScore(torch.autograd.Function):
+    """logits[e] = z[src_e] . z[dst_e] (mode 0) or cosine_similarity(z[src_e], z[dst_e]) (mode 1), rows gathered as stored;
+    backward: one node pass over both CSR orders (weightless decoders)"""
+
+    @staticmethod
+    def forward(ctx, z, st: EdgeStructure, mode):
+        _lib.require_device(z)
+        zr = _rows_any(z)
+        logits, norms, _, _ = _score_fwd(zr, st, mode)
+        ctx.st, ctx.mode, ctx.dtype = st, mode, z.dtype
+        ctx.save_for_backward(zr, logits, norms)
+        return logits
+
+    @staticmethod
+    def backward(ctx, g):
+        zr, logits, norms = ctx.saved_tensors
+        gz = _score_bwd(zr, ctx.st, ctx.mode, _f32c(g), logits, norms)
+        return gz.to(ctx.dtype), None, None
+
+
+class _EdgeScoreLoss(torch.autograd.Function):
+    """(mean BCEWithLogits(pos_weight) over `denom`, detached logits) of the weightless decoders in one edge pass; backward is
+    one node pass scaled by the upstream gradient, read on the device (no sync, no unit-gradient special case)"""
+
+    @staticmethod
+    def forward(ctx, z, st: EdgeStructure, mode, y, pos_weight, denom):
+        _lib.require_device(z, y, pos_weight)
+        zr = _rows_any(z)
+        pw = None if pos_weight is None else _f32c(pos_weight).reshape(-1)
+        logits, norms, loss, g_logits = _score_fwd(zr, st, mode, _f32c(y), pw, denom)
+        ctx.st, ctx.mode, ctx.dtype = st, mode, z.dtype
+        ctx.save_for_backward(zr, logits, norms, g_logits)
+        ctx.mark_non_differentiable(logits)
+        return loss, logits
+
+    @staticmethod
+    def backward(ctx, go, _go_logits):
+        zr, logits, norms, g_logits = ctx.saved_tensors
+        gz = _score_bwd(zr, ctx.st, ctx.mode, g_logits, logits, norms, _f32c(go).reshape(-1))
+        return gz.to(ctx.dtype), None, None, None, None, None
+
+
+def edge_score(z, st: EdgeStructure, mode: str):
+    """per-edge logits of the `dot` / `cosine` decoder (fp32 [E]); dL/dz comes back in z's dtype"""
+    m = SCORE_MODES[mode]
+    _lib.require_device(z)
+    if _via_ops(st):
+        from . import torch_ops
+        return torch_ops.edge_score(z, st, m)
+    return _EdgeScore.apply(z, st, m)
+
+
+def edge_score_loss(z, st: EdgeStructure, mode: str, y, pos_weight=None, denom=None):
+    """(loss, detached logits) = (BCEWithLogitsLoss(pos_weight)(decoder(z), y) averaged over `denom` edges, logits)"""
+    m = SCORE_MODES[mode]
+    _lib.require_device(z, y, pos_weight)
+    denom = st.num_edges if denom is None else denom
+    if _via_ops(st):
+        from . import torch_ops
+        return torch_ops.edge_score_loss(z, st, m, y, pos_weight, denom)
+    return _EdgeScoreLoss.apply(z, st, m, y, pos_weight, denom)
+
+
 @torch.compiler.assume_constant_result
 def _linear_supported(k: int, m: int) -> bool:
     """pangnn_linear_supported(k, m, wgrad=1); a constant of the shapes, baked in when torch.compile traces"""

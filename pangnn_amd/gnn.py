@@ -237,8 +237,23 @@ class AlternateGCN(nn.Module):
                                       labels.shape[0], live=getattr(graph, "live_edges", None))
         if getattr(graph, "live_edges", None) is not None:
             raise NotImplementedError("a padded fixed-shape batch needs the fused training decoder (mlp decoder, node_dim 64)")
+        mode = self._score_mode()
+        if mode is not None and self._scores_fused(z):
+            # cosine / dot: logits, loss and dL/dlogit in one edge pass, dL/dz in one node pass (csrc/edge_score.hip)
+            st = structure_of(graph.edge_index, z.shape[0], holder=graph, name="sim")
+            return PF.edge_score_loss(z, st, mode, labels, pos_weight, labels.shape[0])
         out = self._decode(z, graph)
         return criterion(out, labels, pos_weight), out.detach()
+
+    def _score_mode(self):
+        """"dot" / "cosine" when `_decode` picks a weightless decoder ("dot" wins over "cosine", which wins over "mlp"), else None"""
+        dec = self.flags.decoder
+        return "dot" if "dot" in dec else "cosine" if "cosine" in dec else None
+
+    def _scores_fused(self, z) -> bool:
+        """the weightless decoders run on csrc/edge_score.hip (D in {16, 32, 64, 128, 256}); `fused_decoder=False` keeps the
+        literal gather-concat route"""
+        return bool(self.fused_decoder) and z.dim() == 2 and PF.edge_score_supported(z.shape[1])
 
     def _defers(self) -> bool:
         """training-mode `forward` hands out a DeferredLogits handle instead of launching the inference decoder: only where the
@@ -323,9 +338,13 @@ class AlternateGCN(nn.Module):
     def decode(self, z, edge_index, graph=None):
         # gnn.py:202-204 is `z[src] @ z[dst]`, a shape error unless E == D (broken in the
         # reference); build-defined semantics: per-edge dot product.
+        if self._scores_fused(z):
+            return PF.edge_score(z, structure_of(edge_index, z.shape[0], holder=graph, name="sim"), "dot")
         a, b = self._pairs(z, edge_index, graph)
         return (a * b).sum(dim=1)
 
     def cosine_sim(self, z, edge_index, graph=None):
+        if self._scores_fused(z):
+            return PF.edge_score(z, structure_of(edge_index, z.shape[0], holder=graph, name="sim"), "cosine")
         a, b = self._pairs(z, edge_index, graph)
         return F.cosine_similarity(a, b, dim=1)

@@ -11,7 +11,7 @@ registers, on the same ops,
     stored (half the bytes) with fp32 weights / accumulation / result; float16 rows are promoted to fp32 (the kernels
     have no fp16 row format); everything else runs in fp32.
 The per-step operators of the train step that read a graph (gcn_propagate, embed_conv_in[_linear], embed_propagate,
-decoder_loss, decoder_mlp and their backward ops) are C++ too since round 5 (csrc/graph_ops.cpp: schema, HIP implementation,
+decoder_loss, decoder_mlp, edge_score, edge_score_loss and their backward ops) are C++ too since round 5 (csrc/graph_ops.cpp: schema, HIP implementation,
 autograd formula, and the structure registry they look a graph up in by the identity of its `edge_index` tensor); the second
 half of this module holds their fake kernels, the registry's build-on-miss hook and the wrappers `functional` calls with this
 package's structure objects (`functional.USE_DISPATCHER_OPS`; PANGNN_DISPATCHER_OPS=auto: only when a tracer / dispatch mode
@@ -241,6 +241,24 @@ def _(g, pq, edge_index, extra, cvec, w2, b2, w3, b3):
             f(*b3.shape))
 
 
+@torch.library.register_fake("pangnn::edge_score")
+def _(z, edge_index, mode):
+    f = lambda *s: z.new_empty(s, dtype=torch.float32)           # noqa: E731
+    return f(edge_index.shape[1]), f(z.shape[0] if mode == 1 else 0, 2)
+
+
+@torch.library.register_fake("pangnn::edge_score_backward")
+def _(g, z, edge_index, logits, norms, g_scale, mode):
+    return z.new_empty(z.shape)
+
+
+@torch.library.register_fake("pangnn::edge_score_loss")
+def _(z, edge_index, mode, y, pos_weight, denom):
+    f = lambda *s: z.new_empty(s, dtype=torch.float32)           # noqa: E731
+    e = edge_index.shape[1]
+    return f(), f(e), f(e), f(z.shape[0] if mode == 1 else 0, 2)
+
+
 # ---------------------------------------------------------------------------------------------- wrappers taking structures
 _N = _G
 
@@ -286,3 +304,14 @@ def decoder_loss_pq(pq, st, extra, cvec, w2, b2, w3, b3, y, pos_weight, denom, l
 def decoder_mlp_pq(pq, st, extra, cvec, w2, b2, w3, b3):
     _ready(st, _N.NEED_ENTRY)
     return ops.decoder_mlp(pq, st._key_tensor, extra, cvec, w2, b2, w3, b3)
+
+
+def edge_score(z, st, mode):
+    _ready(st, _N.NEED_BY_DST | _N.NEED_BY_SRC)          # the backward walks both CSR orders
+    return ops.edge_score(z, st._key_tensor, int(mode))[0]
+
+
+def edge_score_loss(z, st, mode, y, pos_weight, denom):
+    _ready(st, _N.NEED_BY_DST | _N.NEED_BY_SRC)
+    out = ops.edge_score_loss(z, st._key_tensor, int(mode), y, pos_weight, int(denom))
+    return out[0], out[1]
