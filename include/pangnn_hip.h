@@ -599,6 +599,26 @@ int    pangnn_edge_score_bwd_mixed(const void* z, int32_t z_dtype, int64_t ldz, 
                                    const float* g, const float* logits, const float* norms, const float* g_scale, float* gz,
                                    int64_t ldg, pangnn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Max-candidate labelling, the "best hit per genome" baselines of predict_homolog_genes (src/predict.py:83-90):
+ * calculate_baseline_labels (src/helper.py:437-485) over Q-scores and raw scores, calculate_logit_baseline_labels
+ * (src/helper.py:494-576) over logits.  Segment k = the edges of one (source gene, candidate genome) group:
+ * positions [seg_rowptr[k], seg_rowptr[k+1]) of the segment order, edge id seg_edge[pos] (int32), or pos itself when
+ * seg_edge is NULL (a relation already in segment order).  seg_rowptr[num_segments + 1] starts at 0, ends at num_edges
+ * and has no empty segment; every edge lies in exactly one segment.  Writes
+ *   label[e] = isnan(v[e]) | (v[e] >= max of the non-NaN values of e's segment)      (uint8 0 / 1)
+ * — the reference's strict `score < candidate_score` test: ties are all 1, a NaN value is 1, a NaN candidate beats nobody.
+ * Optionally y[E] (float 0 / 1, > 0.5 = positive) with counts[4] (int64 [tn, fp, fn, tp], the layout of
+ * pangnn_confusion_update_f32) += the confusion counts of label against y, in the same pass; both NULL or neither.
+ * One wave per segment; integer atomics for the counts only; the result is bitwise reproducible.
+ * ---------------------------------------------------------------------------------------- */
+int    pangnn_best_candidate_f32(const int64_t* seg_rowptr, const int32_t* seg_edge, int64_t num_segments,
+                                 int64_t num_edges, const float* value, const float* y, int64_t* counts, uint8_t* label,
+                                 pangnn_stream_t stream);
+int    pangnn_best_candidate_f64(const int64_t* seg_rowptr, const int32_t* seg_edge, int64_t num_segments,
+                                 int64_t num_edges, const double* value, const float* y, int64_t* counts, uint8_t* label,
+                                 pangnn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

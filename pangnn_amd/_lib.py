@@ -118,6 +118,9 @@ SIGNATURES = {
                                               _p, _p, _p, _p, _p, _i64, _p,            # by source (+ segments, parts)
                                               _p, _p, _p, _p, _p, _i64, _p,            # by target
                                               _p, _p, _p, _p, _p, _i64, _p]),          # g, logits, norms, g_scale, gz, ldg, stream
+    # max-candidate labelling (csrc/candidates.hip): (seg_rowptr, seg_edge, num_segments, num_edges, value, y, counts, label, stream)
+    "pangnn_best_candidate_f32": (C.c_int, [_p, _p, _i64, _i64, _p, _p, _p, _p, _p]),
+    "pangnn_best_candidate_f64": (C.c_int, [_p, _p, _i64, _i64, _p, _p, _p, _p, _p]),
 }
 
 ABI_VERSION = 3          # PANGNN_ABI_VERSION of include/pangnn_hip.h this binding was written against

@@ -1293,3 +1293,6 @@ def pq_operands(w, b, d: int, skip: bool):
                 w[:, 2 * d].contiguous() if skip else None)
     return _PQOperands.apply(w, b, d, skip)
 
+
+
+from .candidates import best_candidate, candidate_baselines   # noqa: E402,F401  (max-candidate labelling, csrc/candidates.hip)

@@ -99,7 +99,7 @@ class _RankingMetric:
             a[0] is b[0] and a[1] is b[1] and a[2] == b[2] and a[3] == b[3] for a, b in zip(self._src, other._src))
 
     def _curve(self):
-        """(tps, fps) at every distinct threshold, scores descending; int64"""
+        """(tps, fps, thresholds) at every distinct threshold, scores descending; tps / fps int64, thresholds the scores"""
         if self._curve_kept is None:
             p = None if self._partner is None else self._partner()
             if p is not None and p._curve_kept is not None and self._same_data(p):
@@ -118,7 +118,7 @@ class _RankingMetric:
         idx = torch.nonzero(last).view(-1)
         tps = torch.cumsum(y, 0)[idx]
         fps = idx + 1 - tps
-        return tps, fps
+        return tps, fps, s[idx]
 
 
 class BinaryAUROC(_RankingMetric):
@@ -128,7 +128,7 @@ class BinaryAUROC(_RankingMetric):
     def compute(self) -> torch.Tensor:
         if not self.scores or sum(t.numel() for t in self.scores) == 0:
             return torch.zeros((), dtype=torch.float32)
-        tps, fps = self._curve()
+        tps, fps, _ = self._curve()
         p, n = tps[-1], fps[-1]
         if int(p) == 0 or int(n) == 0:
             return torch.zeros((), dtype=torch.float32, device=tps.device)
@@ -137,6 +137,12 @@ class BinaryAUROC(_RankingMetric):
         fpr = torch.cat([z, fps.double() / n.double()])
         return torch.trapezoid(tpr, fpr).to(torch.float32)
 
+    def optimal_threshold(self) -> torch.Tensor:
+        """Youden threshold of the kept curve (no second sort): see `youden_threshold`"""
+        if not self.scores or sum(t.numel() for t in self.scores) == 0:
+            return torch.full((), float("inf"), dtype=torch.float32)
+        return _youden(*self._curve())
+
 
 class BinaryAveragePrecision(_RankingMetric):
     """AP = sum_k (R_k - R_{k-1}) P_k over distinct thresholds (no interpolation)"""
@@ -144,7 +150,7 @@ class BinaryAveragePrecision(_RankingMetric):
     def compute(self) -> torch.Tensor:
         if not self.scores or sum(t.numel() for t in self.scores) == 0:
             return torch.zeros((), dtype=torch.float32)
-        tps, fps = self._curve()
+        tps, fps, _ = self._curve()
         p = tps[-1]
         if int(p) == 0:
             return torch.zeros((), dtype=torch.float32, device=tps.device)
@@ -152,3 +158,34 @@ class BinaryAveragePrecision(_RankingMetric):
         recall = tps.double() / p.double()
         prev = torch.cat([torch.zeros(1, dtype=torch.float64, device=tps.device), recall[:-1]])
         return ((recall - prev) * precision).sum().to(torch.float32)
+
+
+def _youden(tps, fps, thr) -> torch.Tensor:
+    dev = tps.device
+    m = tps.numel()
+    # sklearn's drop_intermediate: of the curve's points keep the first, the last and every point where the second difference
+    # of fps or tps is non-zero.  The dropped points are not argmax candidates: in exact arithmetic they never hold the first
+    # maximum, but in float64 a point inside a flat collinear run can round one ulp above the run's first point.
+    keep = torch.ones(m, dtype=torch.bool, device=dev)
+    if m > 2:
+        keep[1:-1] = ((tps[2:] - 2 * tps[1:-1] + tps[:-2]) != 0) | ((fps[2:] - 2 * fps[1:-1] + fps[:-2]) != 0)
+    p, n = tps[-1].double(), fps[-1].double()
+    z = torch.zeros(1, dtype=torch.float64, device=dev)
+    j = torch.cat([z, tps.double() / p - fps.double() / n])               # leading point (0, 0) at threshold inf
+    j = torch.where(torch.cat([keep.new_ones(1), keep]), j, torch.full_like(j, -float("inf")))
+    # one class absent: sklearn's tpr or fpr is 0/0 = NaN and numpy's argmax takes the first NaN, the leading point
+    k = torch.where(torch.isnan(j).any(), torch.zeros((), dtype=torch.int64, device=dev), torch.argmax(j))
+    t = torch.cat([torch.full((1,), float("inf"), dtype=thr.dtype, device=dev), thr])
+    return t[k]
+
+
+def youden_threshold(scores, target) -> torch.Tensor:
+    """thresholds[argmax(tpr - fpr)] of sklearn.metrics.roc_curve(target, scores) (src/plot.py:103-105, what plot_roc
+    returns as stats['optimatl_threshold'] and --dynamic_binary_threshold sets): the FIRST maximum, on a curve whose leading
+    point is (0, 0) at threshold inf — so inf when no score gives tpr - fpr > 0 or one class is absent.  The argmax runs over
+    the points sklearn keeps (its default drop_intermediate rule), so float64 rounding inside a collinear run picks what
+    sklearn picks.
+    A 0-d float32 tensor on the device of `scores` (float32 scores, as the ranking metrics keep them)."""
+    m = BinaryAUROC()
+    m.update(scores, target)
+    return m.optimal_threshold()
