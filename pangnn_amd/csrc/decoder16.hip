@@ -48,11 +48,7 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int D16 = 64;
 constexpr int SLAB16 = 64 * 64 + 64 + 64 + 64 + 16;   // gW2 | gb2 | gw3 | gcvec | gb3, loss (+pad): layout of decoder.hip
-#ifdef PANGNN_D16_PROBE_ONE_WAVE        // tools/slp_probe.sh: diagnostic builds only (one wave per SIMD)
-constexpr int S_WAVES = 4;
-#else
 constexpr int S_WAVES = 8;                            // 512 threads, one workgroup per CU, two waves per SIMD
-#endif
 // Run sums are taken per CHUNK of 2^chunk_log consecutive 32-edge tiles: a wave walks the tiles of a chunk in order and
 // carries an open run from tile to tile, so a run only ends where its key changes or the chunk ends — one part row per
 // (chunk, key) run (N + E / 512 rows instead of one per (tile, key) run, N + E / 32), and most half tiles have no
@@ -94,14 +90,9 @@ constexpr int WV_HG = 0, WV_M2 = 3 * T_IMG, WV_REC = 4 * T_IMG, WV_GL = WV_REC +
 constexpr int WV_BYTES = WV_WL + 64;                  // 8576
 constexpr int S_LDS = LDS_WAVE0 + S_WAVES * WV_BYTES;
 
-// s_setprio around every run of matrix instructions: with two to four waves per SIMD the arbiter otherwise lets a
-// wave in its vector phase starve the one feeding the matrix pipe; raised priority for the MFMA issuer keeps the
+// s_setprio(1) / (0) around every run of matrix instructions: with two to four waves per SIMD the arbiter otherwise lets
+// a wave in its vector phase starve the one feeding the matrix pipe; raised priority for the MFMA issuer keeps the
 // pipe busy while the other waves fill the issue slots in between (measured: -4 % on the S kernel).
-#ifdef PANGNN_D16_PROBE_NOPRIO          // tools/slp_probe.sh: diagnostic builds only
-#define D16_SETPRIO(x) ((void)0)
-#else
-#define D16_SETPRIO(x) __builtin_amdgcn_s_setprio(x)
-#endif
 
 struct Split3 { bf16x8 hi, mid, lo; };
 // x = hi + mid + lo EXACTLY: three bf16 terms by truncation (8 + 8 + 8 significand bits, all of the sign of x).
@@ -192,40 +183,6 @@ __device__ __forceinline__ bf16x8 ld_b128(const char* lds_base, int off) {
   return *reinterpret_cast<const bf16x8*>(lds_base + off);
 }
 
-#ifdef PANGNN_D16_DEBUG
-__device__ float* d16_dbg_v = nullptr;     // [E][64] dL/dh1pre as the S kernel sees it (diagnostic builds only)
-#endif
-#ifdef PANGNN_D16_STAMP                   // diagnostic builds only (tools/probe_decoder_stamps.py): where a small launch spends its time
-__device__ unsigned long long* d16_stamps = nullptr;     // wave 0 of workgroup 0: wall_clock64() (100 MHz) at the marked points
-#define D16_STAMP(i)                                                                          \
-  do {                                                                                        \
-    if (d16_stamps != nullptr && blockIdx.x == 0 && threadIdx.x == 0) {                       \
-      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                             \
-      d16_stamps[i] = wall_clock64();                                                         \
-    }                                                                                         \
-  } while (0)
-#else
-#define D16_STAMP(i) ((void)0)
-#endif
-#ifdef PANGNN_D16_CYC                     // diagnostic builds only (tools/probe_decoder_cycles.py): where the S kernel's waves spend their
-// cycles AT FULL SIZE: every wave adds the shader-clock cycles (s_memtime) between consecutive marks of its loop body into
-// per-phase sums over all of its half tiles — scalar registers, no waits of its own beyond the counter read's lgkmcnt — and
-// the eight waves of workgroup 0 write theirs out at the end: d16_cyc[wave][0 .. 5] = cycles in phase 0 .. 5, [6] = half tiles,
-// [7] = cycles from kernel entry to loop exit.
-__device__ unsigned long long* d16_cyc = nullptr;
-#define D16_CYC_DECL unsigned long long cyc_acc[6] = {0, 0, 0, 0, 0, 0}, cyc_halves = 0; \
-  const unsigned long long cyc_t0 = __builtin_readcyclecounter(); unsigned long long cyc_last = cyc_t0
-#define D16_CYC(i)                                                  \
-  do {                                                              \
-    const unsigned long long t__ = __builtin_readcyclecounter();    \
-    cyc_acc[i] += t__ - cyc_last;                                   \
-    cyc_last = t__;                                                 \
-  } while (0)
-#else
-#define D16_CYC_DECL ((void)0)
-#define D16_CYC(i) ((void)0)
-#endif
-
 struct D16Params {
   const void* p; const void* q; uint32_t ldp_b; uint32_t ldq_b;     // row strides in bytes; rows are f32 or bf16 (PQ16)
   const int64_t* ei; int64_t ld; int64_t E;
@@ -294,35 +251,6 @@ __device__ __forceinline__ void stage_weights16(const float* w2, const float* b2
 __device__ __forceinline__ void dgrad_masks(const char* recl, const char* gl, int c, int g, f32x4 (&gm)[4]) {
   const int bitpos = 16 * (c & 1) + 15 - ((c & 7) >> 1);      // m1 bits: the high byte of each half of a record dword
   const char* rrow = recl + 64 * g + 4 * (c >> 3);      // edge 4 g + i at + 16 i; dwords (c >> 3) and 2 + (c >> 3)
-#if defined(PANGNN_D16_PROBE_GE_SCALAR) || defined(PANGNN_D16_PROBE_WAIT0)
-  // diagnostic builds (tools/slp_probe.sh): the same arithmetic with (a) g_e read as four dwords instead of one
-  // ds_read_b128, (b) every LDS operand of the epilogue landed (lgkmcnt(0) + idle cycles) before the first use
-  f32x4 ge4;
-#ifdef PANGNN_D16_PROBE_GE_SCALAR
-#pragma unroll
-  for (int i = 0; i < 4; ++i) ge4[i] = *reinterpret_cast<const volatile float*>(gl + 16 * g + 4 * i);
-#else
-  ge4 = *reinterpret_cast<const f32x4*>(gl + 16 * g);
-#endif
-  uint32_t dd[4][2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    dd[i][0] = *reinterpret_cast<const uint32_t*>(rrow + 16 * i);
-    dd[i][1] = *reinterpret_cast<const uint32_t*>(rrow + 16 * i + 8);
-  }
-#ifdef PANGNN_D16_PROBE_WAIT0
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_nop 7\n\ts_nop 7" : "+v"(ge4), "+v"(dd[0][0]), "+v"(dd[1][0]), "+v"(dd[2][0]), "+v"(dd[3][0]),
-               "+v"(dd[0][1]), "+v"(dd[1][1]), "+v"(dd[2][1]), "+v"(dd[3][1]) :: "memory");
-#endif
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb) {
-      const int keep = __builtin_amdgcn_sbfe((int)dd[i][kb & 1], bitpos - 4 * (kb >> 1), 1);
-      const float gei = ge4[i];          // a float OBJECT: __builtin_bit_cast of the vector element itself takes element 0
-      gm[kb][i] = __builtin_bit_cast(float, __builtin_bit_cast(int, gei) & keep);
-    }
-#else
   const f32x4 ge4 = *reinterpret_cast<const f32x4*>(gl + 16 * g);
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -339,20 +267,13 @@ __device__ __forceinline__ void dgrad_masks(const char* recl, const char* gl, in
       gm[kb][i] = __builtin_bit_cast(float, gbits & keep);
     }
   }
-#endif
 }
-// the masked products themselves (rare paths of the run sums, the skip-feature gradient, diagnostic dumps)
+// the masked products themselves (rare paths of the run sums, the skip-feature gradient)
 __device__ __forceinline__ void dgrad_apply(f32x4 (&v)[4], const f32x4 (&gm)[4]) {
 #pragma unroll
   for (int kb = 0; kb < 4; ++kb)
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      float val = v[kb][i] * gm[kb][i];
-#ifdef PANGNN_D16_PROBE_OPAQUE_EPI
-      asm volatile("" : "+v"(val));
-#endif
-      v[kb][i] = val;
-    }
+    for (int i = 0; i < 4; ++i) v[kb][i] *= gm[kb][i];
 }
 
 // ---- P2 + its epilogue + run sums, shared by S and T.  Lane (c = lane & 15, g = lane >> 4).
@@ -373,7 +294,7 @@ __device__ __forceinline__ void dgrad_tile(const char* lds, const char* recl, co
 #pragma unroll
     for (int x = 0; x < 3; ++x) bq[0][x] = ld_b128(lds, w2p_off0 + x * W_IMG);
   }
-  D16_SETPRIO(1);
+  __builtin_amdgcn_s_setprio(1);
 #pragma unroll
   for (int st = 0; st < 8; ++st) {
     const int t = st >> 2, kb = st & 3;
@@ -392,7 +313,7 @@ __device__ __forceinline__ void dgrad_tile(const char* lds, const char* recl, co
     v[kb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2[t], bq[st & 1][1], v[kb], 0, 0, 0);
     v[kb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2[t], bq[st & 1][0], v[kb], 0, 0, 0);
   }
-  D16_SETPRIO(0);
+  __builtin_amdgcn_s_setprio(0);
   dgrad_masks(recl, gl, c, g, gm);
 }
 
@@ -408,7 +329,7 @@ __device__ __forceinline__ void dgrad_tile2(const char* lds, const bf16x8 (&a2)[
   bf16x8 bq[2][3];
 #pragma unroll
   for (int x = 0; x < 3; ++x) bq[0][x] = ld_b128(lds, w2p_off0 + x * W_IMG);
-  D16_SETPRIO(1);
+  __builtin_amdgcn_s_setprio(1);
 #pragma unroll
   for (int st = 0; st < 8; ++st) {
     const int t = st >> 2, kb = st & 3;
@@ -423,7 +344,7 @@ __device__ __forceinline__ void dgrad_tile2(const char* lds, const bf16x8 (&a2)[
       for (int h = 0; h < 2; ++h)
         v[h][kb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2[h][t], bq[st & 1][x], v[h][kb], 0, 0, 0);
   }
-  D16_SETPRIO(0);
+  __builtin_amdgcn_s_setprio(0);
 }
 
 // Sums of the dL/dh1 rows of every run of equal keys (sources in S, targets in T) inside a 32-edge tile, written as
@@ -448,9 +369,6 @@ __device__ __forceinline__ void run_sums(const f32x4 (&v)[4], const f32x4 (&gm)[
       t = fmaf(v[kb][1], gm[kb][1], t);
       t = fmaf(v[kb][2], gm[kb][2], t);
       x[kb] = fmaf(v[kb][3], gm[kb][3], t);
-#ifdef PANGNN_D16_PROBE_OPAQUE_RUNSUM
-      asm volatile("" : "+v"(x[kb]));
-#endif
     }
     const float s = carry + red4(x[0], x[1], x[2], x[3]);
     if (m16 & 0x8000u) {
@@ -473,9 +391,6 @@ __device__ __forceinline__ void run_sums(const f32x4 (&v)[4], const f32x4 (&gm)[
         const bool first = 4 * g + i <= bnd;
         a[kb] = fmaf(v[kb][i], first ? gm[kb][i] : 0.f, a[kb]);
         b[kb] = fmaf(v[kb][i], first ? 0.f : gm[kb][i], b[kb]);
-#ifdef PANGNN_D16_PROBE_OPAQUE_RUNSUM
-        asm volatile("" : "+v"(a[kb]), "+v"(b[kb]));
-#endif
       }
     }
     const float lo = carry + red4(a[0], a[1], a[2], a[3]);
@@ -595,7 +510,7 @@ __device__ __forceinline__ float p1_logit(const char* lds, const float (&h)[2][8
     for (int x = 0; x < 3; ++x) aq[0][x] = ld_b128(lds, LDS_W2 + wfrag0 + x * W_IMG);
   }
   Split3 hbk;                                       // the terms of one K-step at a time (12 registers)
-  D16_SETPRIO(1);
+  __builtin_amdgcn_s_setprio(1);
 #pragma unroll
   for (int st = 0; st < 8; ++st) {
     const int ks = st >> 2, jb = st & 3;
@@ -626,7 +541,7 @@ __device__ __forceinline__ float p1_logit(const char* lds, const float (&h)[2][8
     acc[jb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w_hi, hbk.mid, acc[jb], 0, 0, 0);
     acc[jb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w_hi, hbk.hi, acc[jb], 0, 0, 0);
   }
-  D16_SETPRIO(0);
+  __builtin_amdgcn_s_setprio(0);
   float part = 0.f;
 #pragma unroll
   for (int jb = 0; jb < 4; ++jb) {
@@ -695,11 +610,8 @@ __global__ __launch_bounds__(S_WAVES * 64) void decoder_train16_kernel(
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   const int c = lane & 15, g = lane >> 4;
   char* wv = lds + LDS_WAVE0 + wave * WV_BYTES;
-  D16_STAMP(0);
   stage_weights16(a.w2, a.b2, a.w3, a.cvec, lds, S_WAVES * 64, 3, LDS_W2P, LDS_VEC);
-  D16_STAMP(1);
   __syncthreads();
-  D16_STAMP(2);
   const float* w3l = reinterpret_cast<const float*>(lds + LDS_VEC) + 64;
   const float* cvl = w3l + 64;
 
@@ -752,8 +664,6 @@ __global__ __launch_bounds__(S_WAVES * 64) void decoder_train16_kernel(
   int poff_cur = (RUNSUM && tile < n_tiles) ? rs.part_off[tile >> clog] : 0;
   float carry = 0.f;
   int64_t pidx = 0;
-  D16_STAMP(3);
-  D16_CYC_DECL;
 
   while (tile < n_tiles) {
     // chunk bookkeeping as selects (no branch in the loop body): a chunk's first tile starts from its part offset with
@@ -772,7 +682,6 @@ __global__ __launch_bounds__(S_WAVES * 64) void decoder_train16_kernel(
 #pragma unroll 1
     for (int hx = 0; hx < 2; ++hx) {
       // ids of the next half tile (this tile's second half, or the first half of the wave's next tile)
-      D16_CYC(5);                          // phase 5: loop / chunk bookkeeping between half tiles
       const HalfIn in_nxt = load_half<EXTRA>(a, auxp, hx == 0 ? tile : tile_nxt, n_tiles, hx ^ 1, c);    // one load site
       const int pos = 16 * hx + c;
       const bool live = pos <= live_lim;
@@ -784,11 +693,7 @@ __global__ __launch_bounds__(S_WAVES * 64) void decoder_train16_kernel(
       // ---- P1: C[j][e] = b2[j] + sum_k W2[j][k] h1[e][k]
       f32x4 acc[4];
       uint32_t m1 = 0;                     // relu mask bits of h1 (packed inside the first product, off its split terms)
-      D16_STAMP(4 + 4 * hx);
-      D16_CYC(0);                          // phase 0: next ids requested, the gathered rows of THIS half awaited, h1 = relu(p + q)
       const float xv = p1_logit<false, true>(lds, h, wfrag0, wfrag1, g, b3v, acc, one2, &m1);
-      D16_STAMP(5 + 4 * hx);
-      D16_CYC(1);                          // phase 1: P1 (splits, 48 matrix instructions, relu, w3 dot, lane sums)
       // the rows of the next half tile fly during the epilogue and the other two products
       issue_half_rows(a, in_nxt, g, rows);
 
@@ -882,7 +787,7 @@ __global__ __launch_bounds__(S_WAVES * 64) void decoder_train16_kernel(
       wave_sync();
 #pragma unroll
       for (int mb = 0; mb < 2; ++mb) am[mb] = ld_tr8(wv + WV_M2, tr3h[0] ^ (mb << 6), tr3h[1] ^ (mb << 6));
-      D16_SETPRIO(1);
+      __builtin_amdgcn_s_setprio(1);
       p3_block(0);
       write_hg(1);
       // record dword g of the edge: m2 bits in the low byte of each half (bit 7 - n / 23 - n for the pair n), m1 bits in the
@@ -900,24 +805,12 @@ __global__ __launch_bounds__(S_WAVES * 64) void decoder_train16_kernel(
       }
       wave_sync();
       p3_block(1);
-      D16_SETPRIO(0);
+      __builtin_amdgcn_s_setprio(0);
 
-      D16_STAMP(6 + 4 * hx);
-      D16_CYC(2);                          // phase 2: row requests of the next half, loss, m2 operands, g_e h1 splits, P3, records
       // ---- P2 + run sums by source
       if (RUNSUM || has_extra) {
         f32x4 v[4], gm[4];
         dgrad_tile<false>(lds, wv + WV_REC, wv + WV_GL, a2, c, g, LDS_W2P + wfrag0, LDS_W2P + wfrag1, v, gm);
-#ifdef PANGNN_D16_DEBUG
-        if (d16_dbg_v != nullptr) {
-#pragma unroll
-          for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-              if (tile * 32 + 16 * hx + 4 * g + i < a.E)
-                d16_dbg_v[(tile * 32 + 16 * hx + 4 * g + i) * 64 + 16 * kb + c] = v[kb][i] * gm[kb][i];
-        }
-#endif
         if (has_extra) {
           // the skip feature's gradient needs the rows themselves: multiplied out on the side (config 5's instances only);
           // the run sums below still take the factors, so that they are the same arithmetic in every instance
@@ -929,12 +822,7 @@ __global__ __launch_bounds__(S_WAVES * 64) void decoder_train16_kernel(
 #pragma unroll
           for (int kb = 0; kb < 4; ++kb)
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-              gcv[kb] = fmaf(w4[i], pv[kb][i], gcv[kb]);
-#ifdef PANGNN_D16_PROBE_OPAQUE_GCV
-              asm volatile("" : "+v"(gcv[kb]));
-#endif
-            }
+            for (int i = 0; i < 4; ++i) gcv[kb] = fmaf(w4[i], pv[kb][i], gcv[kb]);
         }
         if (RUNSUM) {
           const bool closes = in_cur.key != in_cur.key_nxt || (pos == 31 && last_tile);     // key change, or end of the chunk
@@ -943,27 +831,13 @@ __global__ __launch_bounds__(S_WAVES * 64) void decoder_train16_kernel(
           run_sums(v, gm, m16, carry, rs.part, pidx, wv, lane, c, g, colp);
         }
       }
-      D16_CYC(3);                          // phase 3: P2 (24 matrix instructions), mask factors, run sums
       wave_sync();          // the next half tile overwrites the images / recl / gl
-      D16_STAMP(7 + 4 * hx);
-      D16_CYC(4);                          // phase 4: the wave barrier that frees the tile images
-#ifdef PANGNN_D16_CYC
-      ++cyc_halves;
-#endif
       in_cur = in_nxt;
     }
     poff_cur = last_tile ? poff_nxt : poff_cur;
     tile = tile_nxt;
   }
 
-#ifdef PANGNN_D16_CYC
-  if (d16_cyc != nullptr && blockIdx.x == 0 && lane == 0) {
-#pragma unroll
-    for (int i = 0; i < 6; ++i) d16_cyc[wave * 8 + i] = cyc_acc[i];
-    d16_cyc[wave * 8 + 6] = cyc_halves;
-    d16_cyc[wave * 8 + 7] = cyc_last - cyc_t0;
-  }
-#endif
   // ---- finish: per-lane partials -> workgroup slab.  The eight waves are added as a fixed binary tree,
   // ((w0 + w1) + (w2 + w3)) + ((w4 + w5) + (w6 + w7)), through LDS: in round d the waves with bit d set (lower bits clear)
   // write their values, their partners d below add them — every value at its own address (value v of lane l at
@@ -986,7 +860,6 @@ __global__ __launch_bounds__(S_WAVES * 64) void decoder_train16_kernel(
     gb3p += __shfl_xor(gb3p, off);
     lossp += __shfl_xor(lossp, off);
   }
-  D16_STAMP(12);
   constexpr int NV = 64 + 16 + 4 + 2;                        // values per lane: dL/dW2 tile | gw3 | gcvec | gb3, loss
   float val[NV];
 #pragma unroll
@@ -1029,7 +902,6 @@ __global__ __launch_bounds__(S_WAVES * 64) void decoder_train16_kernel(
     }
     __syncthreads();
   }
-  D16_STAMP(13);
   // wave 0 lays the sums out as the slab in LDS (the tree buffers are free again), every thread copies its share out:
   // coalesced stores from 512 threads — written by wave 0 alone (68 stores per lane behind 32 dependent loads of w3) the
   // slab took 7 us of a 25 us mini-batch launch
@@ -1066,7 +938,6 @@ __global__ __launch_bounds__(S_WAVES * 64) void decoder_train16_kernel(
   __syncthreads();
   float* slab = slabs + (int64_t)blockIdx.x * SLAB16;
   for (int i = threadIdx.x; i < 4096 + 194; i += S_WAVES * 64) slab[i] = img[i];
-  D16_STAMP(14);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -1411,22 +1282,6 @@ int launch_decoder_infer16(const float* p, int64_t ldp, const float* q, int64_t 
 }  // namespace pangnn
 
 using namespace pangnn;
-
-#ifdef PANGNN_D16_STAMP
-extern "C" int pangnn_debug_set_stamps(unsigned long long* ptr) {
-  return (int)hipMemcpyToSymbol(HIP_SYMBOL(d16_stamps), &ptr, sizeof(ptr));
-}
-#endif
-#ifdef PANGNN_D16_CYC
-extern "C" int pangnn_debug_set_cyc(unsigned long long* ptr) {
-  return (int)hipMemcpyToSymbol(HIP_SYMBOL(d16_cyc), &ptr, sizeof(ptr));
-}
-#endif
-#ifdef PANGNN_D16_DEBUG
-extern "C" int pangnn_debug_set_v(float* ptr) {
-  return (int)hipMemcpyToSymbol(HIP_SYMBOL(d16_dbg_v), &ptr, sizeof(ptr));
-}
-#endif
 
 extern "C" int pangnn_decoder_chunk_tiles(void) { return 1 << D16_CHUNK_LOG_MAX; }
 extern "C" int pangnn_decoder_chunk_tiles_for(int64_t num_edges) {

@@ -13,12 +13,6 @@ namespace pangnn {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-#ifdef PANGNN_LIN_NOMFMA   // diagnostic builds only (tools/ablate_linear.sh): one VALU op per MFMA
-#define LIN_MFMA(a, b, c) ([&] { f32x16 t_ = (c); t_[0] += (a) * (b); return t_; }())
-#else
-#define LIN_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
-#endif
-
 __device__ __forceinline__ constexpr int jrow(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }
 
 __device__ __forceinline__ void wave_sync_lds() {
@@ -32,14 +26,11 @@ __device__ __forceinline__ void wave_sync_lds() {
 // the base is known to sit in SGPRs and the offset's zero-extension is in the same basic block, hence `pin()`
 // at the top of every block of accesses: an empty asm that ties `base` to an SGPR pair and `off` to a VGPR.
 __device__ __forceinline__ void pin(int64_t& base, uint32_t& off) { asm volatile("" : "+s"(base), "+v"(off)); }
+// rows are read once per kernel: streaming loads (3-8 % in isolation)
 __device__ __forceinline__ float4 ld_f4(const float* ubase, uint32_t byte_off) {
-#ifndef PANGNN_LIN_NO_NT      // rows are read once per kernel: streaming loads (3-8 % in isolation, tools/ablate_linear.sh)
   typedef float f32x4 __attribute__((ext_vector_type(4)));
   const f32x4 t = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(ubase) + byte_off));
   return make_float4(t[0], t[1], t[2], t[3]);
-#else
-  return *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(ubase) + byte_off);
-#endif
 }
 __device__ __forceinline__ void st_f32(float* ubase, uint32_t byte_off, float v) {
   *reinterpret_cast<float*>(reinterpret_cast<char*>(ubase) + byte_off) = v;
@@ -171,23 +162,17 @@ __device__ __forceinline__ void store_rows(const RowRegs<C, T>& rg, int lane, fl
   }
 }
 
-// Waves per workgroup of the forward kernel.  Measured at N = 1e6 (tools/ablate_linear.sh): 4 waves per CU
+// Waves per workgroup of the forward kernel.  Measured at N = 1e6: 4 waves per CU
 // (one per SIMD) is the fastest arrangement — an f32 MFMA occupies its SIMD's vector lanes, so a second wave
 // on the SIMD cannot hide the first one's epilogue, it only adds LDS / issue contention (8 waves +5..10 %,
 // 12 waves +30 %).
 template <int K, int M>
 struct FwdGeo {
   static constexpr int KS = K + 4;
-#ifdef PANGNN_LIN_WAVES      // diagnostic builds only
-  static constexpr int WAVES = PANGNN_LIN_WAVES;
-#elif defined(PANGNN_LIN_F32_MFMA) || defined(PANGNN_LIN_128_W4)
-  static constexpr int WAVES = 4;
-#else
   // (8 waves for K = 64 measured: no gain — these kernels are at their HBM time.)  128 x 128: the three split images of the
   // weight take 102 KB, which leaves room for THREE 16.5 KB row tiles — three waves on the split-bf16 product beat four on
-  // v_mfma_f32_32x32x2_f32 (round 5, N = 1e6: forward 0.23-0.25 ms vs 0.30, dL/dx + dL/dW 0.65 vs 0.71; -DPANGNN_LIN_128_W4)
+  // v_mfma_f32_32x32x2_f32 (round 5, N = 1e6: forward 0.23-0.25 ms vs 0.30, dL/dx + dL/dW 0.65 vs 0.71)
   static constexpr int WAVES = (K == 128 && M == 128) ? 3 : 4;
-#endif
 };
 
 // one 32-row tile out of LDS: acc[b] = x_tile . w[32b .. 32b+32)^T.  Operand fragments of k-step i+1 are read
@@ -218,10 +203,10 @@ __device__ __forceinline__ void tile_product(const float* Xt, const float* Wl, i
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int b = 0; b < M / 32; ++b) {
-      acc[b] = LIN_MFMA(a.x, bw[b].x, acc[b]);
-      acc[b] = LIN_MFMA(a.y, bw[b].y, acc[b]);
-      acc[b] = LIN_MFMA(a.z, bw[b].z, acc[b]);
-      acc[b] = LIN_MFMA(a.w, bw[b].w, acc[b]);
+      acc[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, bw[b].x, acc[b], 0, 0, 0);
+      acc[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, bw[b].y, acc[b], 0, 0, 0);
+      acc[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, bw[b].z, acc[b], 0, 0, 0);
+      acc[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, bw[b].w, acc[b], 0, 0, 0);
     }
     __builtin_amdgcn_sched_barrier(0);
     a = an;
@@ -230,15 +215,15 @@ __device__ __forceinline__ void tile_product(const float* Xt, const float* Wl, i
   }
 }
 
-// ---- the same product on the bf16 matrix pipe with fp32-exact operand handling (default; -DPANGNN_LIN_F32_MFMA: the
-// f32-MFMA product above).  v_mfma_f32_32x32x2_f32 runs at 1/16 of the bf16 rate and holds its SIMD for 16 passes: at
-// N = 1e6 a 128 x 64 layer is 1.6e10 flop = 0.10 ms of matrix time at peak, 0.20 ms measured — above the layers' HBM
-// time once their row streams are short (the generated first layer reads 8 bytes per row).  Here both operands are split
-// into three bf16 terms by truncation (x = hi + mid + lo EXACTLY: 8 + 8 + 8 significand bits) and the six partial
-// products of order <= 2^-16 are accumulated in fp32 by v_mfma_f32_32x32x16_bf16, smallest first; the three dropped
-// terms (mid.lo, lo.mid, lo.lo) are <= 2^-23 |x||w| — below fp32's own rounding of the product.  Weights are split
-// once per workgroup into three LDS images [M][K+8] bf16; a tile's x values are split as they are read (5.5 VALU per
-// value, under the matrix instructions).
+// ---- the same product on the bf16 matrix pipe with fp32-exact operand handling (wherever its weight images fit in
+// LDS, WImg::X3; the f32-MFMA product above otherwise).  v_mfma_f32_32x32x2_f32 runs at 1/16 of the bf16 rate and holds
+// its SIMD for 16 passes: at N = 1e6 a 128 x 64 layer is 1.6e10 flop = 0.10 ms of matrix time at peak, 0.20 ms measured
+// — above the layers' HBM time once their row streams are short (the generated first layer reads 8 bytes per row).
+// Here both operands are split into three bf16 terms by truncation (x = hi + mid + lo EXACTLY: 8 + 8 + 8 significand
+// bits) and the six partial products of order <= 2^-16 are accumulated in fp32 by v_mfma_f32_32x32x16_bf16, smallest
+// first; the three dropped terms (mid.lo, lo.mid, lo.lo) are <= 2^-23 |x||w| — below fp32's own rounding of the
+// product.  Weights are split once per workgroup into three LDS images [M][K+8] bf16; a tile's x values are split as
+// they are read (5.5 VALU per value, under the matrix instructions).
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned int u32x4v __attribute__((ext_vector_type(4)));
 struct Split3 { bf16x8 hi, mid, lo; };
@@ -264,19 +249,13 @@ __device__ __forceinline__ Split3 split8(const float4& f0, const float4& f1) {
   return r;
 }
 
-#ifdef PANGNN_LIN_F32_MFMA
-constexpr bool kLinX3 = false;
-#else
-constexpr bool kLinX3 = true;
-#endif
-
 // floats of LDS the weight image of a [M][K] layer takes
 template <int K, int M>
 struct WImg {
   static constexpr int WS = K + 8;                                     // bf16 row stride of a split image
   // 128 x 128: three 34 KB images + three 16.5 KB row tiles (FwdGeo: three waves) = 152 KB of the 160 KB; with four tiles it
   // does not fit and the f32 product is used
-  static constexpr bool X3 = kLinX3 && (3 * M * WS * 2 + FwdGeo<K, M>::WAVES * 32 * (K + 4) * 4 <= 156 * 1024);
+  static constexpr bool X3 = (3 * M * WS * 2 + FwdGeo<K, M>::WAVES * 32 * (K + 4) * 4 <= 156 * 1024);
   static constexpr int FLOATS = X3 ? (3 * M * WS + 1) / 2 : M * (K + 4);
 };
 
@@ -467,54 +446,37 @@ __global__ __launch_bounds__((FwdGeo<K, M>::WAVES * 64)) void linear_fwd_kernel(
 }
 
 // One 32-row tile of the weight gradient: acc[a][b] (32 x 32 block of gw[M][K]) += G_tile^T X_tile, gbp[a] += column sums
-// of G.  f32 product: 16 steps of 2 rows on v_mfma_f32_32x32x2_f32.  Split-bf16 product (default): 2 steps of 16 rows on
-// v_mfma_f32_32x32x16_bf16 — both operands are data here, so both are split (three exact bf16 terms each, six partial
-// products, smallest first): per tile 96 column reads, 12 splits, 96 matrix instructions of 8 passes instead of 128 of 16.
+// of G.  Split-bf16 product: 2 steps of 16 rows on v_mfma_f32_32x32x16_bf16 — both operands are data here, so both are
+// split (three exact bf16 terms each, six partial products, smallest first): per tile 96 column reads, 12 splits, 96 matrix
+// instructions of 8 passes instead of the f32 product's 128 of 16.
 template <int K, int M>
 __device__ __forceinline__ void wgrad_tile(const float* Xt, const float* Gt, int r, int hh, f32x16 (&acc)[M / 32][K / 32],
                                            float (&gbp)[M / 32]) {
   constexpr int KS = K + 4, MS = M + 4;
-  if constexpr (kLinX3) {
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int row0 = 16 * j + 8 * hh;
-      Split3 ga[M / 32], xb[K / 32];
+  for (int j = 0; j < 2; ++j) {
+    const int row0 = 16 * j + 8 * hh;
+    Split3 ga[M / 32], xb[K / 32];
 #pragma unroll
-      for (int a = 0; a < M / 32; ++a) {
-        float f[8];
+    for (int a = 0; a < M / 32; ++a) {
+      float f[8];
 #pragma unroll
-        for (int q = 0; q < 8; ++q) { f[q] = Gt[(row0 + q) * MS + r + 32 * a]; gbp[a] += f[q]; }
-        ga[a] = split8(make_float4(f[0], f[1], f[2], f[3]), make_float4(f[4], f[5], f[6], f[7]));
-      }
+      for (int q = 0; q < 8; ++q) { f[q] = Gt[(row0 + q) * MS + r + 32 * a]; gbp[a] += f[q]; }
+      ga[a] = split8(make_float4(f[0], f[1], f[2], f[3]), make_float4(f[4], f[5], f[6], f[7]));
+    }
 #pragma unroll
-      for (int b = 0; b < K / 32; ++b) {
-        float f[8];
+    for (int b = 0; b < K / 32; ++b) {
+      float f[8];
 #pragma unroll
-        for (int q = 0; q < 8; ++q) f[q] = Xt[(row0 + q) * KS + r + 32 * b];
-        xb[b] = split8(make_float4(f[0], f[1], f[2], f[3]), make_float4(f[4], f[5], f[6], f[7]));
-      }
+      for (int q = 0; q < 8; ++q) f[q] = Xt[(row0 + q) * KS + r + 32 * b];
+      xb[b] = split8(make_float4(f[0], f[1], f[2], f[3]), make_float4(f[4], f[5], f[6], f[7]));
+    }
 #define PG_W3(GT, XT)                                                                                     \
-      _Pragma("unroll") for (int a = 0; a < M / 32; ++a)                                                  \
-      _Pragma("unroll") for (int b = 0; b < K / 32; ++b)                                                  \
-        acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ga[a].GT, xb[b].XT, acc[a][b], 0, 0, 0);
-      PG_W3(lo, hi) PG_W3(hi, lo) PG_W3(mid, mid) PG_W3(mid, hi) PG_W3(hi, mid) PG_W3(hi, hi)
+    _Pragma("unroll") for (int a = 0; a < M / 32; ++a)                                                    \
+    _Pragma("unroll") for (int b = 0; b < K / 32; ++b)                                                    \
+      acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ga[a].GT, xb[b].XT, acc[a][b], 0, 0, 0);
+    PG_W3(lo, hi) PG_W3(hi, lo) PG_W3(mid, mid) PG_W3(mid, hi) PG_W3(hi, mid) PG_W3(hi, hi)
 #undef PG_W3
-    }
-  } else {
-#pragma unroll
-    for (int s = 0; s < 16; ++s) {
-      const int row = 2 * s + hh;
-      float av[M / 32], bv[K / 32];
-#pragma unroll
-      for (int a = 0; a < M / 32; ++a) { av[a] = Gt[row * MS + r + 32 * a]; gbp[a] += av[a]; }
-#pragma unroll
-      for (int b = 0; b < K / 32; ++b) bv[b] = Xt[row * KS + r + 32 * b];
-#pragma unroll
-      for (int a = 0; a < M / 32; ++a)
-#pragma unroll
-        for (int b = 0; b < K / 32; ++b)
-          acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[a], bv[b], acc[a][b], 0, 0, 0);
-    }
   }
 }
 
@@ -980,11 +942,8 @@ __global__ __launch_bounds__(256) void gen_linear_wgrad_kernel(const float* __re
   float* Gt = Xt + 32 * KS;
   gen_params<K>(w_emb, b_emb, w_in, b_in, D, acb, 256);
   __syncthreads();
-  const int q = lane % (K / 4);
-  const float4 a4 = *reinterpret_cast<const float4*>(acb + 4 * q), c4 = *reinterpret_cast<const float4*>(acb + K + 4 * q);
-  const float4 b4 = *reinterpret_cast<const float4*>(acb + 2 * K + 4 * q);
   const int r = lane & 31, hh = lane >> 5;
-  float ca[K / 32], cc[K / 32], cb[K / 32];      // (a, c, b_in) of this lane's columns r + 32 b (split-bf16 form)
+  float ca[K / 32], cc[K / 32], cb[K / 32];      // (a, c, b_in) of this lane's columns r + 32 b
 #pragma unroll
   for (int b = 0; b < K / 32; ++b) { ca[b] = acb[r + 32 * b]; cc[b] = acb[K + r + 32 * b]; cb[b] = acb[2 * K + r + 32 * b]; }
   f32x16 acc[M / 32][K / 32];
@@ -1003,14 +962,12 @@ __global__ __launch_bounds__(256) void gen_linear_wgrad_kernel(const float* __re
   float rsv = gen_load(rvec, svec, n, tile * 32, lane);
   load_rows<M, float>(g, ldg, n, tile * 32, lane, rgm);
   for (; tile < n_tiles; tile += stride) {
-    if constexpr (kLinX3) Xt[lane] = rsv;                   // the tile's (r, s): the X operand is formed in registers
-    else gen_store_rows<K>(rsv, lane, Xt, a4, c4, b4);
+    Xt[lane] = rsv;                                         // the tile's (r, s): the X operand is formed in registers
     store_rows<M, 0, float>(rgm, lane, Gt);                 // rows >= n are zero: their generated x contributes nothing
     rsv = gen_load(rvec, svec, n, (tile + stride) * 32, lane);
     load_rows<M, float>(g, ldg, n, (tile + stride) * 32, lane, rgm);
     wave_sync_lds();
-    if constexpr (kLinX3) gen_wgrad_tile_x3<K, M>(Gt, Xt, ca, cc, cb, r, hh, acc, gbp);
-    else wgrad_tile<K, M>(Xt, Gt, r, hh, acc, gbp);
+    gen_wgrad_tile_x3<K, M>(Gt, Xt, ca, cc, cb, r, hh, acc, gbp);
     wave_sync_lds();
   }
 #pragma unroll

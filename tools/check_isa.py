@@ -9,7 +9,7 @@ Rule 1 — packed-f32 instruction whose LOW result takes the HIGH dword of src1 
   neighbour, with op_sel on src0 / src2, with op_sel_hi, or with plain v_mul_f32) — profiles/r03_pk_opsel_probe.txt.
   hipcc -O3 emits the form from SLP-vectorised f32 math (a broadcast of the odd element of a register pair); it is
   what made the SLP build of csrc/decoder16.hip return dL/dh1 = v * (+0) for edge 13 / 29 of a tile in round 2
-  (tools/slp_probe.py, tools/slp_probe_rows.py).  The library is built so that the form does not occur
+  (profiles/r03_slp_probe.txt).  The library is built so that the form does not occur
   (-fno-slp-vectorize where SLP produced it) and this gate keeps a compiler or source change from bringing it back.
 
 usage: check_isa.py file.o [file.o ...]        (exit status 1 and a listing on a hit)"""

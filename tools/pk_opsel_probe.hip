@@ -1,4 +1,4 @@
-// Reduced reproducer for the S kernel's SLP-build miscompute (DESIGN.md §4 "what went wrong" 2, tools/slp_probe*.py).
+// Reduced reproducer for the S kernel's SLP-build miscompute (DESIGN.md §4 "what went wrong" 2, profiles/r03_slp_probe.txt).
 //
 // In the SLP build of csrc/decoder16.hip the epilogue of the second product multiplies pairs of accumulator values
 // by g_e with v_pk_mul_f32; element (lane group 3, i = 1) of two of the four column blocks then came out as v * (+0)

@@ -1,6 +1,6 @@
 // Does a VALU write that FOLLOWS a packed-f32 instruction overtake that instruction's operand reads on gfx950?
 // (write-after-read on a v_pk_*_f32 source, with one or two waves per SIMD and with / without matrix instructions
-// issued around it.)  Background: DESIGN.md §4 "what went wrong" 2 and tools/slp_probe.py — the SLP build of the S
+// issued around it.)  Background: DESIGN.md §4 "what went wrong" 2 and profiles/r03_slp_probe.txt — the SLP build of the S
 // kernel (-O3 packs adjacent f32 math into v_pk_*_f32 and reuses the pair registers right behind them) miscomputes only
 // with two waves per SIMD.  Every lane computes r = a + b with v_pk_add_f32 from registers that the NEXT instruction(s)
 // overwrite, and compares with the same sums taken by plain v_add_f32 from untouched copies.
