@@ -17,6 +17,10 @@ one flat 216 KB gradient all-reduce (pangnn_amd/dist.py; `exchange="allgather"` 
 
 One JSON line on rank 0: value = supervised similarity edges per second over the whole job.
 `--dump-outputs DIR` (one process): the loss, logits and parameters of the last timed step as DIR/<name>.npy (dump_outputs).
+A plain run sets up, warms up, times the steps and prints the line (with the roofline figures its own timed steps give).
+`--full` (one GPU) then also times, in the same process, what takes runs of its own: the general-feature and strict-fp32
+steps (and roofline_propagate from the first), the reference_loop / eval siblings, the cfg5slice and mini-batch siblings and
+the CPU baseline.
 """
 import argparse
 import contextlib
@@ -421,23 +425,28 @@ def eval_sibling(dev, model, graph, labels, pos_weight, e_sim, passes=3):
             "roc_auc": res["roc_auc"], "pr_auc": res["pr_auc"], "loss": res["loss"]}
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="cfg4", choices=sorted(WORKLOADS))
     ap.add_argument("--genes", type=int, default=None, help="override genes per genome (debug)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline's timed steps, also time the sibling workloads and the CPU baseline (one GPU; "
+                         "the --no-* switches below trim what this adds); a plain run times the headline alone")
     ap.add_argument("--cpu-genes", type=int, default=2500, help="genes per genome of the CPU-baseline sample (1/20 of cfg 4)")
     ap.add_argument("--cpu-steps", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-siblings", action="store_true",
-                    help="keep the general-feature and strict-fp32 timings but skip the siblings that build their own data "
-                         "(cfg5slice, mini-batch regimes) and the reference_loop / eval ones: what the counter passes of "
-                         "tools/pmc_traffic.sh want")
+                    help="with --full: keep the general-feature and strict-fp32 timings but skip the siblings that build their "
+                         "own data (cfg5slice, mini-batch regimes) and the reference_loop / eval ones: what the counter passes "
+                         "of tools/pmc_traffic.sh want")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the sibling timings (general-feature step, strict fp32, cfg5slice, mini-batch regimes)")
-    ap.add_argument("--reference-loop", action="store_true", help="time the reference_loop / eval siblings with --genes too")
+                    help="with --full: skip the sibling timings (general-feature step, strict fp32, cfg5slice, mini-batch "
+                         "regimes)")
+    ap.add_argument("--reference-loop", action="store_true",
+                    help="with --full: time the reference_loop / eval siblings with --genes too")
     ap.add_argument("--emulate-rank", type=int, default=None,
                     help="ONE process stands in for rank r of an --of W rank job (compute side of the partitioned step on one GPU; "
                          "the halo exchange is a self-exchange of the true row counts over RCCL: dist.HaloPlan._emulate)")
@@ -447,11 +456,16 @@ def main():
                     help="after the timed steps, write what the last one returned (loss, logits) and the parameters it left "
                          "as DIR/<name>.npy, float32, at most 64 MB in all (a fixed seeded sample of a larger array); "
                          "single-process runs only")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
     if args.dump_outputs and (args.gpus != 1 or args.emulate_rank is not None):
         ap.error("--dump-outputs needs --gpus 1 and no --emulate-rank")
+    return args
+
+
+def main():
+    args = parse_args()
 
     # stdout carries exactly ONE JSON line: everything native libraries print there (RCCL's version
     # banner at communicator creation) is sent to stderr instead
@@ -662,9 +676,10 @@ def main():
     # step evaluates conv_in(embedding(x)) by linearity and runs that propagate once per graph, not per step (config 5's
     # --categorical_node, the union / hidden layers and every mini-batch run it per step): timed here on a layer-by-layer
     # (fuse_embedding=False) model over the same graph;
-    # (ii) the strict-fp32 step (every decoder product on f32 MFMA: PANGNN_DECODER_PRECISION=0)
+    # (ii) the strict-fp32 step (every decoder product on f32 MFMA: PANGNN_DECODER_PRECISION=0).  --full only, as are the
+    # siblings and the CPU baseline below
     extra = {}
-    if world == 1 and not force_dist and not args.no_extras and not cfg5:
+    if args.full and world == 1 and not force_dist and not args.no_extras and not cfg5:
         old_mode = PF.DECODER_PRECISION
         try:
             # (i) general-feature step: the same graph, the same model layer by layer (fuse_embedding=False) — the * propagate
@@ -882,7 +897,7 @@ def main():
                    "cfg2mb_fresh", "extras_error"):
             if k_ in extra:
                 line[k_] = extra[k_]
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline(args, d, h)
         os.write(json_fd, (json.dumps(line) + "\n").encode())
     if torch.distributed.is_available() and torch.distributed.is_initialized():

@@ -13,6 +13,9 @@ from conftest import ROOT
 pytestmark = pytest.mark.gpu
 REQUIRED = ["metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
             "vs_baseline", "dtype", "data", "config", "roofline"]
+# what only `bench.py --full` times and reports
+FULL_ONLY = {"general_features", "strict_fp32", "roofline_propagate", "reference_loop", "reference_loop_literal", "eval",
+             "cfg5slice", "cfg2mb", "cfg2mb_fresh", "extras_error", "cpu_baseline"}
 
 
 def _run(cmd, env_extra):
@@ -42,12 +45,25 @@ def test_bench_multi_rank_line(world):
     assert many["roofline"]["avg_launch_ms"] > 0
 
 
+def test_bench_plain_line_times_the_headline_alone():
+    """a plain run (no --full): every required key, the roofline objects and step bytes its own timed steps give, and
+    nothing that takes a run of its own — no sibling workloads, no propagate roofline from the layer-by-layer step, no CPU
+    baseline"""
+    d = _run([sys.executable, "bench.py", "--workload", "cfg2", "--steps", "3", "--warmup", "1"], {})
+    assert all(k in d for k in REQUIRED), d.keys()
+    assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["dtype"] == "f32"
+    assert abs(d["value"] - d["config"]["sim_edges"] / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
+    assert d["roofline"]["avg_launch_ms"] > 0 and d["roofline_dgrad"]["avg_launch_ms"] > 0
+    assert abs(sum(d["step_alg_bytes_terms"].values()) - d["step_alg_bytes"]) < 1.0
+    assert not FULL_ONLY & set(d), FULL_ONLY & set(d)
+
+
 def test_bench_single_gpu_line_carries_roofline_step_bytes_and_cpu_baseline():
-    """the N = 1 line of the measurement contract on a small workload: every required key, the roofline object of the
-    dominant kernel with its live launch time, the step-level byte accounting whose terms add up, the strict-fp32 extra,
-    and the CPU baseline (the oracle's train step on a bounded sample)"""
-    d = _run([sys.executable, "bench.py", "--workload", "cfg2", "--steps", "3", "--warmup", "1", "--cpu-genes", "100",
-              "--cpu-steps", "1"], {})
+    """the N = 1 line of the measurement contract on a small workload with --full: every required key, the roofline object
+    of the dominant kernel with its live launch time, the step-level byte accounting whose terms add up, the strict-fp32
+    extra, and the CPU baseline (the oracle's train step on a bounded sample)"""
+    d = _run([sys.executable, "bench.py", "--workload", "cfg2", "--steps", "3", "--warmup", "1", "--full", "--cpu-genes",
+              "100", "--cpu-steps", "1"], {})
     assert all(k in d for k in REQUIRED), d.keys()
     assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["higher_is_better"] is True
     assert d["unit"] == "edges/s" and d["vs_baseline"] is None and d["data"] == "synthetic" and d["dtype"] == "f32"
