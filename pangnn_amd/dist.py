@@ -320,37 +320,41 @@ class _BandTinyHalo(torch.autograd.Function):
     kernel straight from the [n_local, F] block, no table — and the few edges that cross the partition boundary (at most k
     rows on either side) are added from the exchanged halo rows.  Against HaloGather + the generic propagate this saves the
     concatenation of the block into a table, the copy of its gradient back out, the accumulation pass over it and the separate
-    column sum of the bias gradient (one step of rank 0 of 2, profiles/r05z_*: 57 + 46 + 46 + 43 us of a 6.4 ms step)."""
+    column sum of the bias gradient (one step of rank 0 of 2, profiles/r05z_*: 57 + 46 + 46 + 43 us of a 6.4 ms step).
+    The boundary edges are summed in a fixed order, like the rest of the propagate path: by target into the result, by
+    source into the halo rows' gradient (the CSRs of `h_st`, built once in _tiny_halo_band), and the returned rows into the
+    owner's through the plan's `back_csr` — no atomics, bitwise reproducible."""
 
     @staticmethod
-    def forward(ctx, x, bias, plan, dis, k, h_src, h_dst, h_val):
-        ctx.plan, ctx.k, ctx.has_bias = plan, int(k), bias is not None
-        ctx.save_for_backward(dis, h_src, h_dst, h_val)
+    def forward(ctx, x, bias, plan, dis, k, h_st, h_val_dst, h_val_src, acc):
+        ctx.plan, ctx.k, ctx.has_bias, ctx.h_st, ctx.acc = plan, int(k), bias is not None, h_st, acc
+        ctx.save_for_backward(dis, h_val_src)
         out = PF._band_call(x, None if bias is None else PF._f32c(bias), dis, int(k), False)[0]
         if plan.any_exchange:
             send = x.index_select(0, plan.send_idx)
             recv = x.new_empty((plan.n_halo, x.shape[1]))
             _all_to_all_v(recv, send, plan.recv_splits, plan.send_splits, plan.group)
-            if h_src.numel():
-                out.index_add_(0, h_dst, recv.float().index_select(0, h_src) * h_val.unsqueeze(1))
+            if h_st is not None:
+                PF.spmm_csr(h_st.by_dst, h_val_dst, recv, plan.n_local, out=out, accumulate=True)
         return out
 
     @staticmethod
     def backward(ctx, g):
-        dis, h_src, h_dst, h_val = ctx.saved_tensors
-        plan = ctx.plan
+        dis, h_val_src = ctx.saved_tensors
+        plan, h_st = ctx.plan, ctx.h_st
         want_b = ctx.has_bias and ctx.needs_input_grad[1]
         g = PF._f32c(g)
         gx, gb = PF._band_call(g, None, dis, ctx.k, want_b)           # the band is symmetric: the same kernel, + column sums
         if plan.any_exchange:
-            gh = g.new_zeros((plan.n_halo, g.shape[1]))
-            if h_src.numel():
-                gh.index_add_(0, h_src, g.index_select(0, h_dst) * h_val.unsqueeze(1))
+            if h_st is not None:                                      # every halo row is read by at least one boundary edge
+                gh = PF.spmm_csr(h_st.by_src, h_val_src, g, plan.n_halo)
+            else:
+                gh = g.new_zeros((plan.n_halo, g.shape[1]))
             back = g.new_empty((plan.send_idx.numel(), g.shape[1]))
             _all_to_all_v(back, gh, plan.send_splits, plan.recv_splits, plan.group)
             if back.shape[0]:
-                gx.index_add_(0, plan.send_idx, back)
-        return gx, gb, None, None, None, None, None, None
+                ctx.acc(gx, back, plan)
+        return gx, gb, None, None, None, None, None, None, None
 
 
 _SIDE_STREAMS = {}
@@ -452,11 +456,16 @@ class _OverlappedDecoderLoss(torch.autograd.Function):
         fwd.done()
         box = {}
 
+        # The halo rows' dL/dP travel in the table's storage type when that is bfloat16 (fp32's range, half the bytes), in
+        # float32 when it is float16: they are finished with the UNSCALED loss here, a GradScaler's factor only arrives in
+        # backward(), and at a large edge count (config 4: E = 7.5e7) most of them lie below float16's subnormal spacing.
+        wire = torch.float32 if p_local.dtype == torch.float16 else p_local.dtype
+
         def send_back(gp_table):
             with _Side(dev, *(gp_table if joint else [gp_table])) as bwd:
-                g_halo = g_halo32.to(p_local.dtype) if joint else \
-                    torch.cat([gp_table[:n_low], gp_table[n_low + n_loc:]], dim=0).to(p_local.dtype)
-                back = p_local.new_empty((plan.send_idx.numel(), d))    # travels in the table's storage type
+                g_halo = g_halo32.to(wire) if joint else \
+                    torch.cat([gp_table[:n_low], gp_table[n_low + n_loc:]], dim=0).to(wire)
+                back = torch.empty((plan.send_idx.numel(), d), dtype=wire, device=dev)
                 _all_to_all_v(back, g_halo, plan.send_splits, plan.recv_splits, plan.group)
                 bwd.keep(back)
             box["bwd"], box["back"] = bwd, back
@@ -732,11 +741,12 @@ class DistAlternateGCN(AlternateGCN):
         return self.ops.linear(x, w, b, in_act, out_dtype)
 
     def _tiny_halo_band(self, shard, name, weight, wkey):
-        """(plan, deg^-1/2 of the own rows, k, halo-source edges as (compact halo row, own target row, norm)) when the shard's
-        `name` graph is the positional-neighbour band with unit weights, else None.  Decided once per shard (host read-backs),
-        the same way on every rank of a genome-major partition (each rank sees the band or none does: the decision uses only
-        the shard's own edge list, and a rank whose list is not the band keeps the generic path — both paths exchange the same
-        rows with the same split lists)."""
+        """(plan, deg^-1/2 of the own rows, k, structure of the halo-source edges (compact halo row -> own target row) or None,
+        their norms in its by-target and by-source CSR orders, accumulate_back) when the shard's `name` graph is the
+        positional-neighbour band with unit weights, else None.  Decided once per shard (host read-backs), the same way on
+        every rank of a genome-major partition (each rank sees the band or none does: the decision uses only the shard's own
+        edge list, and a rank whose list is not the band keeps the generic path — both paths exchange the same rows with the
+        same split lists)."""
         cache = shard.__dict__.setdefault("_dist_band", {})
         if name not in cache:
             cache[name] = None
@@ -754,8 +764,16 @@ class DistAlternateGCN(AlternateGCN):
                         and plan.n_halo <= 2 * k:
                     norm = self._norm(shard, name, weight, wkey)
                     hs = src[~own]
-                    h_src = torch.where(hs < n_low, hs, hs - n_loc).contiguous()       # row of the compact [low | high] halo block
-                    cache[name] = (plan, norm.deg_inv_sqrt, k, h_src, dst[~own].contiguous(), norm.orig[~own].contiguous())
+                    h_src = torch.where(hs < n_low, hs, hs - n_loc)                    # row of the compact [low | high] halo block
+                    h_val = norm.orig[~own]
+                    h_st, h_vd, h_vs = None, None, None
+                    if h_src.numel():
+                        # the <= 2 k (k + 1) boundary edges in both CSR orders, their norms permuted to match: the forward sum
+                        # runs by target, the halo rows' gradient by source, both in a fixed order
+                        h_st = self.ops.structure(torch.stack([h_src, dst[~own]]).contiguous(), n_loc, plan.n_halo)
+                        h_vd = h_val[h_st.by_dst.perm.long()].contiguous()
+                        h_vs = h_val[h_st.by_src.perm.long()].contiguous()
+                    cache[name] = (plan, norm.deg_inv_sqrt, k, h_st, h_vd, h_vs, self.ops.accumulate_back)
         return cache[name]
 
     def _propagate_rows(self, rows_local, bias, shard, name, weight, wkey, tag):
