@@ -616,12 +616,10 @@ class HipOps:
         """one-pass training decoder on (a range of) a shard: (loss, logits, dL/dtable, dL/dq, g_cvec, g_w2, g_b2, g_w3,
         g_b3), all finished; `after_p(dL/dtable)` runs before the by-target pass is enqueued; `out_q`: where dL/dq is written
         (a column window of a wider matrix is fine), or ADDED to it with `accumulate_q`"""
-        f = PF._f32c
-        pw = None if pos_weight is None else f(pos_weight).reshape(-1)
+        p, q, ex, cv, w2, b2, w3, b3, y, pw = PF._decoder_operands(table, q_local, extra, cvec, w2, b2, w3, b3, y, pos_weight)
         loss, logits, gp, gq, g_cv, g_w2, g_b2, g_w3, g_b3 = PF._decoder_train16(
-            PF._rows_dec(table), PF._rows_dec(q_local), st, None if extra is None else f(extra),
-            None if cvec is None else f(cvec), f(w2), f(b2), f(w3), f(b3), y=f(y), pw=pw, denom=denom, after_p=after_p,
-            out_q=out_q, accumulate_q=accumulate_q, out_p=out_p, p_windows=p_windows, out_logits=out_logits)
+            p, q, st, ex, cv, w2, b2, w3, b3, y=y, pw=pw, denom=denom, after_p=after_p, out_q=out_q,
+            accumulate_q=accumulate_q, out_p=out_p, p_windows=p_windows, out_logits=out_logits)
         return loss.view(()), logits, gp, gq, g_cv, g_w2, g_b2, g_w3, g_b3
 
     def linear(self, x, w, b, in_act: int = 0, out_dtype=None):

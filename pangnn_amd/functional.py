@@ -570,11 +570,6 @@ def autocast_rows_dtype(t: torch.Tensor):
     return None
 
 
-def _rows_dec(t: torch.Tensor) -> torch.Tensor:
-    """decoder tables as the decoder kernels read them: float32, or bfloat16 / float16 as stored"""
-    return _rows_any(t)
-
-
 def autocast_bf16(t: torch.Tensor) -> bool:
     """bf16 mixed precision is on for `t`'s device (config 5)"""
     return autocast_rows_dtype(t) == torch.bfloat16
@@ -590,6 +585,85 @@ def _dt(t: torch.Tensor) -> int:
     return dtype_code(t.dtype)
 
 
+def _decoder_operands(p, q, extra, cvec, w2, b2, w3, b3, y=None, pos_weight=None):
+    """(p, q, ex, cv, w2, b2, w3, b3, y, pw) as the decoder kernels read them under DECODER_PRECISION: the tables as float32
+    rows, or in mode 1 bfloat16 / float16 rows as stored (p and q stored differently: both as float32); `q=None`: `p` is
+    one joint [N, 2D] table and comes back as its two column windows.  Everything else float32 and contiguous, pos_weight
+    flattened."""
+    rows = _rows_any if DECODER_PRECISION == 1 else _rows_f32
+    if q is None:
+        pq = rows(p)
+        d = pq.shape[1] // 2
+        p, q = pq[:, :d], pq[:, d:]
+    else:
+        p, q = rows(p), rows(q)
+        if p.dtype != q.dtype:
+            p, q = p.float(), q.float()
+    w2, b2, w3, b3 = (_f32c(t) for t in (w2, b2, w3, b3))
+    ex, cv, y, pw = (None if t is None else _f32c(t) for t in (extra, cvec, y, pos_weight))
+    return p, q, ex, cv, w2, b2, w3, b3, y, (None if pw is None else pw.reshape(-1))
+
+
+def _decoder_f32(p, q, st: EdgeStructure, ex, cv, w2, b2, w3, b3, y=None, pw=None, denom=0, g_logits=None,
+                 out_p=None, out_q=None, need_p=True, need_q=True, live=None):
+    """_decoder_train16's strict-fp32 counterpart (DECODER_PRECISION 0), same arguments and result: one launch of
+    pangnn_decoder_mlp_loss_f32 (y given: logits, loss and every gradient) or pangnn_decoder_mlp_bwd_f32 (the given
+    dL/dlogits), which writes dL/dh1 [E, D] and, for a source-sorted list, per-run partial rows; then dL/dP by source and
+    dL/dQ by target, into `out_p` / `out_q` when given (e.g. the column windows of one [N, 2D] gradient).  A padded batch
+    (`live`) needs mode 1."""
+    assert live is None
+    lib = _lib.load()
+    dev = p.device
+    e, d = st.num_edges, p.shape[1]
+    fused = y is not None
+    logits = torch.empty(e, dtype=torch.float32, device=dev) if fused else None
+    loss = torch.empty(1, dtype=torch.float32, device=dev) if fused else None
+    g_h1 = torch.empty(e, d, dtype=torch.float32, device=dev)
+    g_w2 = torch.empty_like(w2)
+    g_b2, g_w3, g_b3 = torch.empty_like(b2), torch.empty_like(w3), torch.empty_like(b3)
+    g_cv = None if cv is None else torch.empty_like(cv)
+    plan = st.runsum_plan()
+    parts = None if plan is None else torch.empty(plan.n_parts, d, dtype=torch.float32, device=dev)
+    with _lib.device_guard(dev):
+        ws_bytes = lib.pangnn_decoder_mlp_bwd_workspace_bytes(e)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        head = (p.data_ptr(), p.stride(0), q.data_ptr(), q.stride(0), max(p.shape[0], q.shape[0]),
+                st.edge_index.data_ptr(), e, e, _lib.ptr(ex), _lib.ptr(cv), w2.data_ptr(), b2.data_ptr(), w3.data_ptr(),
+                b3.data_ptr(), d)
+        tail = (_lib.ptr(g_h1), g_w2.data_ptr(), g_b2.data_ptr(), g_w3.data_ptr(), g_b3.data_ptr(), _lib.ptr(g_cv),
+                _lib.ptr(parts), None if plan is None else plan.part_off.data_ptr(), DECODER_PRECISION, ws.data_ptr(),
+                ws_bytes, _lib.stream_ptr())
+        ev = _timer_start("dec.bwd")
+        if fused:
+            _lib.check(lib.pangnn_decoder_mlp_loss_f32(*head, _lib.ptr(y), _lib.ptr(pw), int(denom), _lib.ptr(logits),
+                                                       loss.data_ptr(), *tail), "pangnn_decoder_mlp_loss_f32")
+        else:
+            _lib.check(lib.pangnn_decoder_mlp_bwd_f32(*head, _lib.ptr(g_logits), *tail), "pangnn_decoder_mlp_bwd_f32")
+        _timer_stop("dec.bwd", ev)
+    gp = gq = None
+    if need_p:
+        if plan is not None:       # per-run partial rows came out of the kernel: short contiguous sum
+            gp = _sum_parts(plan, parts, p.shape[0], out_p if out_p is not None else torch.empty(p.shape[0], d, device=dev))
+        else:
+            gp = segment_sum_rows(st.by_src, g_h1, 0, d, p.shape[0], out=out_p)
+    if need_q:
+        gq = segment_sum_rows(st.by_dst, g_h1, 0, d, q.shape[0], out=out_q)
+    return loss, logits, gp, gq, g_cv, g_w2, g_b2, g_w3, g_b3
+
+
+def _decoder_grads(p, q, st: EdgeStructure, ex, cv, w2, b2, w3, b3, joint: bool, **kw):
+    """the training decoder of the current DECODER_PRECISION (_decoder_train16 / _decoder_f32) on normalised operands;
+    `joint`: p and q are the column windows of one [N, 2D] table and dL/dP | dL/dQ come back as ONE [N, 2D] matrix in
+    the gp slot (gq None).  Returns (loss, logits, gp, gq, g_cv, g_w2, g_b2, g_w3, g_b3)."""
+    train = _decoder_train16 if DECODER_PRECISION == 1 else _decoder_f32
+    if not joint:
+        return train(p, q, st, ex, cv, w2, b2, w3, b3, **kw)
+    d = p.shape[1]
+    g_pq = torch.empty(p.shape[0], 2 * d, dtype=torch.float32, device=p.device)
+    r = train(p, q, st, ex, cv, w2, b2, w3, b3, out_p=g_pq[:, :d], out_q=g_pq[:, d:], **kw)
+    return r[:2] + (g_pq, None) + r[4:]
+
+
 class _DecoderMLP(torch.autograd.Function):
     """Fused link decoder (node_dim 64): logits[e] = w3 . relu(W2 relu(p[src]+q[dst] (+w_e c)) + b2) + b3.
     Forward keeps every [E, 64] intermediate on chip; backward recomputes per tile, emits
@@ -601,18 +675,7 @@ class _DecoderMLP(torch.autograd.Function):
     def forward(ctx, p, q, st: EdgeStructure, extra, cvec, w2, b2, w3, b3, pq_joint=False):
         lib = _lib.load()
         _lib.require_device(p, q, extra, cvec, w2, b2, w3, b3)
-        rows = _rows_dec if DECODER_PRECISION == 1 else _rows_f32      # bf16-stored tables: gathered as stored
-        if pq_joint:
-            pq = rows(p)
-            d = pq.shape[1] // 2
-            p, q = pq[:, :d], pq[:, d:]
-        else:
-            p, q = rows(p), rows(q)
-            if p.dtype != q.dtype:
-                p, q = p.float(), q.float()
-        w2, b2, w3, b3 = (_f32c(t) for t in (w2, b2, w3, b3))
-        ex = None if extra is None else _f32c(extra)
-        cv = None if cvec is None else _f32c(cvec)
+        p, q, ex, cv, w2, b2, w3, b3, _, _ = _decoder_operands(p, None if pq_joint else q, extra, cvec, w2, b2, w3, b3)
         e, d = st.num_edges, p.shape[1]
         logits = torch.empty(e, dtype=torch.float32, device=p.device)
         with _lib.device_guard(p.device):
@@ -638,56 +701,10 @@ class _DecoderMLP(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        lib = _lib.load()
-        st = ctx.st
         p, q, ex, cv, w2, b2, w3, b3 = ctx.saved_tensors
-        g = _f32c(g)
-        e, d = st.num_edges, p.shape[1]
-        dev = p.device
-        if DECODER_PRECISION == 1:
-            if ctx.joint:
-                g_pq = torch.empty(p.shape[0], 2 * d, dtype=torch.float32, device=dev)
-                _, _, _, _, g_cv, g_w2, g_b2, g_w3, g_b3 = _decoder_train16(
-                    p, q, st, ex, cv, w2, b2, w3, b3, g_logits=g, out_p=g_pq[:, :d], out_q=g_pq[:, d:])
-                return g_pq, None, None, None, g_cv, g_w2, g_b2, g_w3, g_b3, None
-            _, _, gp, gq, g_cv, g_w2, g_b2, g_w3, g_b3 = _decoder_train16(
-                p, q, st, ex, cv, w2, b2, w3, b3, g_logits=g, need_p=ctx.needs_input_grad[0],
-                need_q=ctx.needs_input_grad[1])
-            return gp, gq, None, None, g_cv, g_w2, g_b2, g_w3, g_b3, None
-        g_h1 = torch.empty(e, d, dtype=torch.float32, device=dev)
-        g_w2 = torch.empty_like(w2)
-        g_b2, g_w3, g_b3 = torch.empty_like(b2), torch.empty_like(w3), torch.empty_like(b3)
-        g_cv = None if cv is None else torch.empty_like(cv)
-        plan = st.runsum_plan()
-        parts = None if plan is None else torch.empty(plan.n_parts, d, dtype=torch.float32, device=dev)
-        with _lib.device_guard(dev):
-            ws_bytes = lib.pangnn_decoder_mlp_bwd_workspace_bytes(e)
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            ev = _timer_start("dec.bwd")
-            _lib.check(lib.pangnn_decoder_mlp_bwd_f32(p.data_ptr(), p.stride(0), q.data_ptr(), q.stride(0),
-                                                      max(p.shape[0], q.shape[0]), st.edge_index.data_ptr(), e, e,
-                                                      _lib.ptr(ex), _lib.ptr(cv), w2.data_ptr(), b2.data_ptr(),
-                                                      w3.data_ptr(), b3.data_ptr(), d, _lib.ptr(g), _lib.ptr(g_h1),
-                                                      g_w2.data_ptr(), g_b2.data_ptr(), g_w3.data_ptr(),
-                                                      g_b3.data_ptr(), _lib.ptr(g_cv), _lib.ptr(parts),
-                                                      None if plan is None else plan.part_off.data_ptr(),
-                                                      DECODER_PRECISION, ws.data_ptr(), ws_bytes,
-                                                      _lib.stream_ptr()), "pangnn_decoder_mlp_bwd_f32")
-            _timer_stop("dec.bwd", ev)
-
-        def by_source(out=None):
-            if plan is not None:
-                return _sum_parts(plan, parts, p.shape[0],
-                                  out if out is not None else torch.empty(p.shape[0], d, device=dev))
-            return segment_sum_rows(st.by_src, g_h1, 0, d, p.shape[0], out=out)
-
-        if ctx.joint:
-            g_pq = torch.empty(p.shape[0], 2 * d, dtype=torch.float32, device=dev)
-            by_source(g_pq[:, :d])
-            segment_sum_rows(st.by_dst, g_h1, 0, d, p.shape[0], out=g_pq[:, d:])
-            return g_pq, None, None, None, g_cv, g_w2, g_b2, g_w3, g_b3, None
-        gp = by_source() if ctx.needs_input_grad[0] else None
-        gq = segment_sum_rows(st.by_dst, g_h1, 0, d, q.shape[0]) if ctx.needs_input_grad[1] else None
+        _, _, gp, gq, g_cv, g_w2, g_b2, g_w3, g_b3 = _decoder_grads(
+            p, q, ctx.st, ex, cv, w2, b2, w3, b3, ctx.joint, g_logits=_f32c(g),
+            need_p=ctx.joint or ctx.needs_input_grad[0], need_q=ctx.joint or ctx.needs_input_grad[1])
         return gp, gq, None, None, g_cv, g_w2, g_b2, g_w3, g_b3, None
 
 
@@ -767,81 +784,18 @@ def scale_by_loss_grad_(ctx, tensors, go):
 
 class _DecoderLoss(torch.autograd.Function):
     """Training form of the fused decoder: mean BCEWithLogits(pos_weight) loss, logits and ALL gradients in
-    one pass over the edges (pangnn_decoder_mlp_loss_f32).  Everything is computed in forward(); backward()
-    only scales the stored gradients by the upstream gradient of the loss."""
+    one pass over the edges (_decoder_train16, or _decoder_f32 in strict-fp32 mode).  Everything is computed in
+    forward(); backward() only scales the stored gradients by the upstream gradient of the loss."""
 
     @staticmethod
     def forward(ctx, p, q, st: EdgeStructure, extra, cvec, w2, b2, w3, b3, y, pos_weight, denom, pq_joint, live=None):
-        lib = _lib.load()
         _lib.require_device(p, q, extra, cvec, w2, b2, w3, b3, y, pos_weight)
         if live is not None and (DECODER_PRECISION != 1 or live.dtype != torch.int64 or not live.is_cuda):
             raise ValueError("live= (a padded fixed-shape batch) needs the default decoder mode and a device int64 tensor")
-        rows = _rows_dec if DECODER_PRECISION == 1 else _rows_f32      # bf16-stored tables: gathered as stored
-        if pq_joint:
-            pq = rows(p)
-            d = pq.shape[1] // 2
-            p, q = pq[:, :d], pq[:, d:]
-        else:
-            p, q = rows(p), rows(q)
-            if p.dtype != q.dtype:
-                p, q = p.float(), q.float()
-        w2, b2, w3, b3, y = (_f32c(t) for t in (w2, b2, w3, b3, y))
-        ex = None if extra is None else _f32c(extra)
-        cv = None if cvec is None else _f32c(cvec)
-        pw = None if pos_weight is None else _f32c(pos_weight).reshape(-1)
-        e, d = st.num_edges, p.shape[1]
-        dev = p.device
-        if DECODER_PRECISION == 1:
-            if pq_joint:
-                g_pq = torch.empty(p.shape[0], 2 * d, dtype=torch.float32, device=dev)
-                loss, logits, _, _, g_cv, g_w2, g_b2, g_w3, g_b3 = _decoder_train16(
-                    p, q, st, ex, cv, w2, b2, w3, b3, y=y, pw=pw, denom=denom, out_p=g_pq[:, :d], out_q=g_pq[:, d:],
-                    live=live)
-                gp, gq = g_pq, None
-            else:
-                loss, logits, gp, gq, g_cv, g_w2, g_b2, g_w3, g_b3 = _decoder_train16(
-                    p, q, st, ex, cv, w2, b2, w3, b3, y=y, pw=pw, denom=denom, live=live)
-            ctx.has_cv, ctx.has_q = g_cv is not None, gq is not None
-            ctx.save_for_backward(gp, gq if gq is not None else gp.new_empty(0),
-                                  g_cv if g_cv is not None else gp.new_empty(0), g_w2, g_b2, g_w3, g_b3)
-            ctx.mark_non_differentiable(logits)
-            return loss.view(()), logits
-        logits = torch.empty(e, dtype=torch.float32, device=dev)
-        loss = torch.empty(1, dtype=torch.float32, device=dev)
-        g_h1 = torch.empty(e, d, dtype=torch.float32, device=dev)
-        g_w2 = torch.empty_like(w2)
-        g_b2, g_w3, g_b3 = torch.empty_like(b2), torch.empty_like(w3), torch.empty_like(b3)
-        g_cv = None if cv is None else torch.empty_like(cv)
-        plan = st.runsum_plan()
-        parts = None if plan is None else torch.empty(plan.n_parts, d, dtype=torch.float32, device=dev)
-        with _lib.device_guard(dev):
-            ws_bytes = lib.pangnn_decoder_mlp_bwd_workspace_bytes(e)
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            ev = _timer_start("dec.bwd")
-            _lib.check(lib.pangnn_decoder_mlp_loss_f32(
-                p.data_ptr(), p.stride(0), q.data_ptr(), q.stride(0), max(p.shape[0], q.shape[0]),
-                st.edge_index.data_ptr(), e, e, _lib.ptr(ex), _lib.ptr(cv), w2.data_ptr(), b2.data_ptr(),
-                w3.data_ptr(), b3.data_ptr(), d, _lib.ptr(y), _lib.ptr(pw), int(denom), _lib.ptr(logits),
-                loss.data_ptr(), _lib.ptr(g_h1), g_w2.data_ptr(), g_b2.data_ptr(), g_w3.data_ptr(), g_b3.data_ptr(),
-                _lib.ptr(g_cv), _lib.ptr(parts), None if plan is None else plan.part_off.data_ptr(),
-                DECODER_PRECISION, ws.data_ptr(), ws_bytes, _lib.stream_ptr()), "pangnn_decoder_mlp_loss_f32")
-            _timer_stop("dec.bwd", ev)
-
-        def by_source(out=None):
-            if plan is not None:       # per-run partial rows came out of the kernel: short contiguous sum
-                return _sum_parts(plan, parts, p.shape[0],
-                                  out if out is not None else torch.empty(p.shape[0], d, device=dev))
-            return segment_sum_rows(st.by_src, g_h1, 0, d, p.shape[0], out=out)
-
-        if pq_joint:
-            g_pq = torch.empty(p.shape[0], 2 * d, dtype=torch.float32, device=dev)
-            by_source(g_pq[:, :d])
-            segment_sum_rows(st.by_dst, g_h1, 0, d, p.shape[0], out=g_pq[:, d:])
-            gp, gq = g_pq, None
-        else:
-            gp = by_source()
-            gq = segment_sum_rows(st.by_dst, g_h1, 0, d, q.shape[0])
-        del g_h1
+        p, q, ex, cv, w2, b2, w3, b3, y, pw = _decoder_operands(p, None if pq_joint else q, extra, cvec, w2, b2, w3, b3,
+                                                                y, pos_weight)
+        loss, logits, gp, gq, g_cv, g_w2, g_b2, g_w3, g_b3 = _decoder_grads(
+            p, q, st, ex, cv, w2, b2, w3, b3, pq_joint, y=y, pw=pw, denom=denom, live=live)
         ctx.has_cv, ctx.has_q = g_cv is not None, gq is not None
         ctx.save_for_backward(gp, gq if gq is not None else gp.new_empty(0),
                               g_cv if g_cv is not None else gp.new_empty(0), g_w2, g_b2, g_w3, g_b3)

@@ -134,6 +134,38 @@ def test_ops_refuse_cpu_tensors():
                                      torch.randn(64), torch.randn(64), torch.randn(1))
 
 
+def test_decoder_operands_of_the_direct_route():
+    """functional._decoder_operands (host only, no launch): 16-bit tables reach the kernels as stored in mode 1 and as float32
+    copies in mode 0; a pair stored differently becomes float32; a joint [N, 2D] table comes back as its two column windows;
+    the small operands are float32 and contiguous, pos_weight flat"""
+    from pangnn_amd import functional as PF
+    n, d, e = 5, 64, 7
+    pq = torch.randn(n, 2 * d).to(torch.bfloat16)
+    w2, b2, w3, b3 = torch.randn(d, d).t(), torch.randn(d).double(), torch.randn(d), torch.randn(1)
+    old = PF.DECODER_PRECISION
+    try:
+        for mode in (1, 0):
+            PF.DECODER_PRECISION = mode
+            rows = torch.bfloat16 if mode == 1 else torch.float32
+            p, q, ex, cv, w2c, b2c, w3c, b3c, y, pw = PF._decoder_operands(pq, None, None, None, w2, b2, w3, b3)
+            assert p.dtype == q.dtype == rows and p.shape == q.shape == (n, d)
+            assert q.data_ptr() == p.data_ptr() + d * p.element_size() and p.stride(0) == 2 * d
+            assert (p.data_ptr() == pq.data_ptr()) == (mode == 1)
+            assert torch.equal(torch.cat([p, q], 1).float(), pq.float())
+            assert ex is None and cv is None and y is None and pw is None
+            for a, b in ((w2c, w2), (b2c, b2), (w3c, w3), (b3c, b3)):
+                assert a.dtype == torch.float32 and a.is_contiguous() and torch.equal(a, b.float())
+            p, q, *_ = PF._decoder_operands(pq[:, :d], pq[:, d:], None, None, w2, b2, w3, b3)
+            assert p.dtype == q.dtype == rows
+            p, q, ex, cv, *_, y, pw = PF._decoder_operands(pq[:, :d], pq[:, d:].float(), torch.rand(e).half(),
+                                                           torch.randn(d), w2, b2, w3, b3, torch.rand(e).double(),
+                                                           torch.tensor([[2.5]]))
+            assert p.dtype == q.dtype == torch.float32 and torch.equal(p, pq[:, :d].float())
+            assert all(t.dtype == torch.float32 for t in (ex, cv, y, pw)) and pw.shape == (1,)
+    finally:
+        PF.DECODER_PRECISION = old
+
+
 @pytest.mark.gpu
 def test_dispatcher_propagate_equals_ctypes_path_and_oracle():
     from pangnn_amd import functional as PF, torch_ops
