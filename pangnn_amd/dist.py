@@ -665,16 +665,14 @@ class DistAlternateGCN(AlternateGCN):
         self.overlap = os.environ.get("PANGNN_DIST_OVERLAP", "1") != "0"
         if self.flags.decoder != "mlp":
             raise NotImplementedError("partitioned mode implements the mlp decoder")
-        if dims[0] != 64 and isinstance(self.ops, HipOps):
+        if isinstance(self.ops, HipOps) and not self._fused_width():
             raise NotImplementedError("partitioned HIP decoder is built for node_dim 64")
 
     # structures / norms are per shard tensor and cached on the shard object
     def _plan(self, shard, name):
         cache = shard.__dict__.setdefault("_dist_plans", {})
         if name not in cache:
-            ei = {"sim": shard.edge_index, "nb": getattr(shard, "neighbour_edge_index", None),
-                  "union": getattr(shard, "union_edge_index", None)}[name]
-            cache[name] = HaloPlan(ei, shard.lo, shard.n_local, self.group,
+            cache[name] = HaloPlan(self._edge_index(shard, name), shard.lo, shard.n_local, self.group,
                                    getattr(self.ops, "make_back_csr", None), getattr(shard, "bounds", None),
                                    getattr(shard, "emulated_world", None))
         return cache[name]
@@ -689,9 +687,7 @@ class DistAlternateGCN(AlternateGCN):
             else:
                 if shard.n_pad is None:
                     raise ValueError("exchange='allgather' needs equal node ranges (partition without bounds=)")
-                ei = {"sim": shard.edge_index, "nb": getattr(shard, "neighbour_edge_index", None),
-                      "union": getattr(shard, "union_edge_index", None)}[name]
-                cache[key] = self.ops.structure(ei, shard.n_local, shard.n_pad)
+                cache[key] = self.ops.structure(self._edge_index(shard, name), shard.n_local, shard.n_pad)
         return cache[key]
 
     def _st_split(self, shard):
@@ -710,7 +706,7 @@ class DistAlternateGCN(AlternateGCN):
         sorted shard and something to exchange (PANGNN_DIST_OVERLAP=0 switches it off)"""
         if self.exchange != "halo" or not self.overlap or not hasattr(self.ops, "decoder_train"):
             return False
-        if isinstance(self.ops, HipOps) and PF.DECODER_PRECISION != 1:
+        if isinstance(self.ops, HipOps) and not self._decoder16():      # (another back end's decoder_train has no modes)
             return False
         plan = self._plan(shard, "sim")
         return plan.sorted_by_src and plan.any_exchange           # both agreed over all ranks (HaloPlan.__init__)
@@ -734,9 +730,14 @@ class DistAlternateGCN(AlternateGCN):
         return hit[1]
 
     def _linear(self, x, w, b, in_act: int = 0, out_dtype=None):
-        if out_dtype is None:
-            return self.ops.linear(x, w, b, in_act)
-        return self.ops.linear(x, w, b, in_act, out_dtype)
+        # a back end's `linear` need not take out_dtype (the CPU restatement of the tests does not): passed only when set
+        return self.ops.linear(x, w, b, in_act, *(() if out_dtype is None else (out_dtype,)))
+
+    def _edge_weight(self, shard, name, conv=None):
+        """as AlternateGCN._edge_weight; a shard keeps the union graph's weights beside the sim edges' (partition_graph)"""
+        if name == "union" and conv is not self.conv_out:
+            return shard.union_edge_attr
+        return super()._edge_weight(shard, name, conv)
 
     def _tiny_halo_band(self, shard, name, weight, wkey):
         """(plan, deg^-1/2 of the own rows, k, structure of the halo-source edges (compact halo row -> own target row) or None,
@@ -783,19 +784,21 @@ class DistAlternateGCN(AlternateGCN):
         st, norm = self._st(shard, name), self._norm(shard, name, weight, wkey)
         return self.ops.propagate(self._table(rows_local, shard, name), bias, st, norm, tag)
 
-    def _conv(self, conv, h_local, shard, name, weight, wkey, tag, in_elu: bool = False, dense_done: bool = False):
+    def _conv(self, conv, h_local, shard, name, in_elu: bool = False, dense_done: bool = False):
         """`in_elu`: h_local is the pre-activation of the deferred ELU (see AlternateGCN._encode_pre);
         `dense_done`: h_local already is conv.lin(...) of the layer's input (GCNConv.forward, dense_done)"""
+        weight = self._edge_weight(shard, name, conv)
+        where = (shard, name, weight, "1" if weight is None else "w", name)
         if dense_done:
-            return self._propagate_rows(h_local, conv.bias, shard, name, weight, wkey, tag)
+            return self._propagate_rows(h_local, conv.bias, *where)
         if in_elu and conv.in_channels < conv.out_channels:
             h_local, in_elu = F.elu(h_local), False
         if conv.in_channels < conv.out_channels:
             # propagate (and exchange) on the narrower side: half the all-gather bytes for 64 -> 128
-            agg = self._propagate_rows(h_local, None, shard, name, weight, wkey, tag)
+            agg = self._propagate_rows(h_local, None, *where)
             return self._linear(agg, conv.lin.weight, conv.bias)
         xw = self._linear(h_local, conv.lin.weight, None, 1 if in_elu else 0)
-        return self._propagate_rows(xw, conv.bias, shard, name, weight, wkey, tag)
+        return self._propagate_rows(xw, conv.bias, *where)
 
     def _xtab(self, shard, name):
         """the scalar feature of every row the shard's `name` edges read (own + halo), exchanged once and cached"""
@@ -806,93 +809,58 @@ class DistAlternateGCN(AlternateGCN):
                 cache[key] = self._table(shard.x.float().view(-1, 1), shard, name).view(-1).contiguous()
         return cache[key]
 
-    def _embed_conv_in_then_dense(self, shard, name, weight, w_out, bias_out):
+    def _embed_conv_in_then_dense(self, shard, name, w_out, bias_out):
         """AlternateGCN._embed_conv_in_then_dense on a shard: the first layer's rows of the OWN nodes generated inside the
         dense layer that consumes them (node-level: no exchange involved); None where it does not apply"""
         conv = self.conv_in
+        if name == "union":
+            # today's behaviour: a shard never fuses conv_in into conv_hidden's dense layer (the whole-graph model does);
+            # enabling it changes a partitioned step's kernels — a feature with its own measurement, not a wiring matter
+            return None
         if self.sharded_embedding or not self.fuse_first_dense or not self._fold_elu() or not self.fuse_embedding \
                 or self.fuse_embedding == "propagate" or not hasattr(self.ops, "embed_conv_in_linear"):
             return None
         if w_out.shape[1] != conv.out_channels or not PF.embed_linear_supported(conv.out_channels, w_out.shape[0]) \
                 or PF.autocast_bf16(shard.x):
             return None
-        st, norm = self._st(shard, name), self._norm(shard, name, weight, "w")
+        st, norm = self._st(shard, name), self._norm(shard, name, self._edge_weight(shard, name), "w")
         return self.ops.embed_conv_in_linear(self._xtab(shard, name), self.embedding.weight, self.embedding.bias,
                                              conv.lin.weight, conv.bias, w_out, bias_out, st, norm)
 
-    def _embed_conv_in(self, shard, name, weight):
+    def _embed_conv_in(self, shard, name):
         """conv_in(embedding(x)): x is constant, so the scalar features of the halo rows are exchanged once
         (cached on the shard) and the first layer runs without any per-step exchange, forward or backward."""
         conv = self.conv_in
         if self.sharded_embedding:
             # rows of the owned nodes are the parameter itself; the exchange of the first layer carries the halo rows
-            return self._conv(conv, self.embedding.weight, shard, name, weight, "w", name)
+            return self._conv(conv, self.embedding.weight, shard, name)
         rank2 = self.fuse_embedding and self.fuse_embedding != "propagate" and hasattr(self.ops, "embed_conv_in")
         if rank2 or (conv.in_channels < conv.out_channels and self.fuse_embedding and hasattr(self.ops, "embed_propagate")):
             xtab = self._xtab(shard, name)
-            st, norm = self._st(shard, name), self._norm(shard, name, weight, "w")
+            st, norm = self._st(shard, name), self._norm(shard, name, self._edge_weight(shard, name), "w")
             if rank2:      # the whole layer by linearity (functional._EmbedConvIn): r = A_hat x, s = A_hat 1 of the OWN rows
                 return self.ops.embed_conv_in(xtab, self.embedding.weight, self.embedding.bias, conv.lin.weight,
                                               conv.bias, st, norm)
             agg = self.ops.embed_propagate(xtab, self.embedding.weight, self.embedding.bias, st, norm, name)
             return self._linear(agg, conv.lin.weight, conv.bias)
         h = shard.x.float().view(-1, 1) * self.embedding.weight.view(1, -1) + self.embedding.bias
-        return self._conv(conv, h, shard, name, weight, "w", name)
-
-    def _encode_pre(self, shard):
-        """as AlternateGCN._encode_pre, on a shard: (z or its pre-activation, pending)"""
-        fl, act, fold = self.flags, self.activation_fct, self._fold_elu()
-        pre = (lambda h: h) if fold else act
-        if fl.union_edge_weights:
-            w = shard.union_edge_attr
-            h = self._embed_conv_in(shard, "union", w)
-            for _ in range(max(fl.neighbours - 2, 1)):
-                h = self._conv(self.conv_hidden, pre(h), shard, "union", w, "w", "union", in_elu=fold)
-            h = self._conv(self.conv_out, pre(h), shard, "union", None, "1", "union", in_elu=fold)
-        elif fl.base_model:
-            h = self._embed_conv_in_then_dense(shard, "sim", shard.edge_attr, self.linear_out.weight, self.linear_out.bias)
-            if h is None:
-                h = self._embed_conv_in(shard, "sim", shard.edge_attr)
-                h = self._linear(pre(h), self.linear_out.weight, self.linear_out.bias, 1 if fold else 0)
-        else:
-            out = self.conv_out
-            y = self._embed_conv_in_then_dense(shard, "sim", shard.edge_attr, out.lin.weight, None) \
-                if out.in_channels >= out.out_channels else None
-            if y is not None:
-                h = self._conv(out, y, shard, "nb", None, "1", "nb", dense_done=True)
-            else:
-                h = self._embed_conv_in(shard, "sim", shard.edge_attr)
-                h = self._conv(out, pre(h), shard, "nb", None, "1", "nb", in_elu=fold)
-        return h, True
-
-    def encode(self, shard):
-        h, pending = self._encode_pre(shard)
-        return self.activation_fct(h) if pending else h
+        return self._conv(conv, h, shard, name)
 
     def _dec_in(self, z, shard, in_act: int = 0, gather: bool = True):
-        """gather=False: p stays this rank's block (the overlapped decoder exchanges the halo rows itself)"""
-        fl = self.flags
+        """(p, q, extra, cvec) with P and Q as two products: what the gather-first and all-gather exchanges and a back end
+        without the joint layout need.  gather=False: p stays this rank's block (the overlapped decoder exchanges the halo
+        rows itself)"""
         d = z.shape[1]
         lin0 = self.mlp[0]
         w = lin0.weight
-        # bf16 mixed precision (config 5): P and Q are stored as bfloat16 — the halo exchange of P moves half the bytes
-        pq_dtype = PF.autocast_rows_dtype(z) if (isinstance(self.ops, HipOps) and d == 64 and PF.DECODER_PRECISION == 1) else None
+        # bf16 mixed precision (config 5): P and Q are stored as bfloat16 — the halo exchange of P moves half the bytes;
+        # only the HIP decoder reads 16-bit rows
+        pq_dtype = PF.autocast_rows_dtype(z) if (isinstance(self.ops, HipOps) and self._decoder16()) else None
         p = self._linear(z, w[:, :d].contiguous(), None, in_act, pq_dtype)
         q = self._linear(z, w[:, d:2 * d].contiguous(), lin0.bias, in_act, pq_dtype)
         p_full = self._table(p, shard, "sim") if gather else p
-        extra = shard.edge_attr if fl.skip_connections else None
-        cvec = w[:, 2 * d].contiguous() if fl.skip_connections else None
-        return p_full, q, extra, cvec
-
-    def _dec_in_joint(self, z, shard, in_act: int = 0):
-        """(P | Q [n_local, 2 D] of this rank's rows, extra, cvec): the re-associated first decoder layer as one product"""
-        fl = self.flags
-        d = z.shape[1]
-        lin0 = self.mlp[0]
-        w_pq, b_pq, cvec = PF.pq_operands(lin0.weight, lin0.bias, d, bool(fl.skip_connections))
-        pq_dtype = PF.autocast_rows_dtype(z) if PF.DECODER_PRECISION == 1 else None
-        pq = self._linear(z, w_pq, b_pq, in_act, pq_dtype)
-        return pq, (shard.edge_attr if fl.skip_connections else None), cvec
+        cvec = w[:, 2 * d].contiguous() if self.flags.skip_connections else None
+        return p_full, q, self._skip_feature(shard), cvec
 
     def decode_mlp(self, z, shard):
         p_full, q, extra, cvec = self._dec_in(z, shard)
@@ -909,11 +877,10 @@ class DistAlternateGCN(AlternateGCN):
         if not fold:
             z = self.activation_fct(z) if pending else z
         if torch.is_grad_enabled() and self._overlap_ok(shard):
-            if isinstance(self.ops, HipOps) and z.shape[1] == 64:
-                # ONE node-level product z -> P | Q (AlternateGCN._decoder_inputs' layout): the decoder reads its two column
+            if isinstance(self.ops, HipOps) and self._fused_width():
+                # ONE node-level product z -> P | Q (AlternateGCN._decoder_pq): the decoder reads its two column
                 # halves in place and hands back one [n_local, 128] gradient
-                p, extra, cvec = self._dec_in_joint(z, shard, 1 if fold else 0)
-                q = None
+                (p, extra, cvec), q = self._decoder_pq(z, shard, 1 if fold else 0), None
             else:
                 p, q, extra, cvec = self._dec_in(z, shard, 1 if fold else 0, gather=False)
             st_loc, st_halo = self._st_split(shard)

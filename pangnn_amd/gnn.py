@@ -102,33 +102,59 @@ class AlternateGCN(nn.Module):
             self.to(device)
 
     # ---------------------------------------------------------------------------------
-    def _embed_conv_in(self, graph, ei, name):
+    # The wiring of the model (`_encode_pre`, the decoder's first layer) is written once, against the primitives below;
+    # dist.DistAlternateGCN evaluates the same wiring on a shard by overriding them.
+    @staticmethod
+    def _edge_index(graph, name):
+        """edge list of the graph `name`: "sim" (similarity), "nb" (positional neighbours), "union" (both)"""
+        return getattr(graph, {"sim": "edge_index", "nb": "neighbour_edge_index", "union": "union_edge_index"}[name])
+
+    def _edge_weight(self, graph, name, conv=None):
+        """edge weights a layer on the graph `name` uses: `edge_attr` on "sim" and on "union" (dataset.py:380 stores the
+        union weights there), none on "nb" (gnn.py:165) and for conv_out (gnn.py:138,165)"""
+        return None if (name == "nb" or conv is self.conv_out) else graph.edge_attr
+
+    def _linear(self, x, w, b, in_act: int = 0, out_dtype=None):
+        """one node-level dense layer"""
+        return PF.linear(x, w, b, in_act, out_dtype)
+
+    def _conv(self, conv, h, graph, name, in_elu: bool = False, dense_done: bool = False):
+        """one GCN layer on the graph `name` (GCNConv.forward: in_elu, dense_done)"""
+        return conv(h, self._edge_index(graph, name), self._edge_weight(graph, name, conv), graph=graph, name=name,
+                    in_elu=in_elu, dense_done=dense_done)
+
+    def _embed_conv_in(self, graph, name):
         """act-less `conv_in(embedding(x))` (gnn.py:125-131,143-146,156-158)"""
         x, conv = graph.x, self.conv_in
         _lib.require_device(x)
         if self.categorical_nodes:
-            return conv(self.embedding(x.long().view(-1)), ei, graph.edge_attr, graph=graph, name=name)
+            return self._conv(conv, self.embedding(x.long().view(-1)), graph, name)
         if self.fuse_embedding and (self.fuse_embedding != "propagate" or conv.in_channels < conv.out_channels):
-            st = structure_of(ei, x.shape[0], holder=graph, name=name)
-            w = graph.edge_attr
-            if w is not None and w.shape[0] != st.num_edges:
-                raise ValueError(f"edge_weight has {w.shape[0]} entries for {st.num_edges} edges")
+            st, norm = self._first_layer_graph(graph, name)
             out_dtype = PF.autocast_rows_dtype(x)          # the autocast Linear's output type (bf16 / fp16 mixed precision)
             if self.fuse_embedding != "propagate":
                 # the whole layer by linearity: r a^T + s c^T + b_in, r = A_hat x and s = A_hat 1 cached per graph
                 # (functional._EmbedConvIn) — one [N, H] write per step, one pass over its gradient in backward
                 return PF.embed_conv_in(x, self.embedding.weight, self.embedding.bias, conv.lin.weight, conv.bias, st,
-                                        st.gcn_norm(w), out_dtype)
+                                        norm, out_dtype)
             # round 2's form: embedding + propagate as one operator whose backward yields the embedding's two parameter
             # gradients without the transposed propagate (functional._EmbedPropagate), then the dense layer
-            agg = PF.embed_propagate(x, self.embedding.weight, self.embedding.bias, st, st.gcn_norm(w), tag=name)
+            agg = PF.embed_propagate(x, self.embedding.weight, self.embedding.bias, st, norm, tag=name)
             return PF.linear(agg, conv.lin.weight, conv.bias, 0, out_dtype)
         # Linear(1, D) on a [N,1] column is an outer product; as a GEMM its weight gradient is a
         # 64 x 1 x N problem that the BLAS library runs at < 0.1 TB/s
         h = x.float().view(-1, 1) * self.embedding.weight.view(1, -1) + self.embedding.bias
-        return conv(h, ei, graph.edge_attr, graph=graph, name=name)
+        return self._conv(conv, h, graph, name)
 
-    def _embed_conv_in_then_dense(self, graph, ei, name, w_out, bias_out):
+    def _first_layer_graph(self, graph, name):
+        """(structure, normalisation) of the graph `name` for the first layer's fused operators"""
+        st = structure_of(self._edge_index(graph, name), graph.x.shape[0], holder=graph, name=name)
+        w = self._edge_weight(graph, name)
+        if w is not None and w.shape[0] != st.num_edges:
+            raise ValueError(f"edge_weight has {w.shape[0]} entries for {st.num_edges} edges")
+        return st, st.gcn_norm(w)
+
+    def _embed_conv_in_then_dense(self, graph, name, w_out, bias_out):
         """linear(ELU(conv_in(embedding(x))), w_out, bias_out) with the [N, H] rows of the first layer generated inside the
         dense layer's kernels (functional._EmbedConvInLinear) — or None where that operator does not apply: categorical
         nodes, fuse_embedding / fuse_first_dense / fold_activation off, widths its kernels do not cover, bf16 / fp16 autocast
@@ -142,12 +168,9 @@ class AlternateGCN(nn.Module):
         _lib.require_device(x)
         if PF.autocast_rows_dtype(x) is not None:
             return None
-        st = structure_of(ei, x.shape[0], holder=graph, name=name)
-        w = graph.edge_attr
-        if w is not None and w.shape[0] != st.num_edges:
-            raise ValueError(f"edge_weight has {w.shape[0]} entries for {st.num_edges} edges")
+        st, norm = self._first_layer_graph(graph, name)
         return PF.embed_conv_in_linear(x, self.embedding.weight, self.embedding.bias, conv.lin.weight, conv.bias, w_out,
-                                       bias_out, st, st.gcn_norm(w))
+                                       bias_out, st, norm)
 
     def _fold_elu(self) -> bool:
         """the encoder's activation (gnn.py:108: ELU) can be folded into the dense layer that follows it"""
@@ -157,70 +180,75 @@ class AlternateGCN(nn.Module):
     def _encode_pre(self, graph):
         """(z or its pre-activation, pending): every `h = act(layer(...))` of gnn.py:125-166 is consumed by exactly
         one dense layer (GCNConv.lin of the next conv, linear_out, or the decoder's first layer), so with ELU the
-        activation runs inside that layer's kernels (functional.linear, in_act) and only the LAST one can be
-        left pending for the caller."""
-        fl = self.flags
-        act, fold = self.activation_fct, self._fold_elu()
+        activation runs inside that layer's kernels (`in_elu` / `in_act`) and only the LAST one can be left pending for
+        the caller.  `graph` is whatever the primitives above take: a Data / Batch here, a shard in dist.py."""
+        fl, fold = self.flags, self._fold_elu()
+        pre = (lambda h: h) if fold else self.activation_fct      # an ELU that is not folded runs as its own op
         if fl.union_edge_weights:                                              # gnn.py:128-139
-            ei = graph.union_edge_index
             hid = self.conv_hidden
-            y = self._embed_conv_in_then_dense(graph, ei, "union", hid.lin.weight, None) \
+            y = self._embed_conv_in_then_dense(graph, "union", hid.lin.weight, None) \
                 if hid.in_channels >= hid.out_channels else None
-            h = self._embed_conv_in(graph, ei, "union") if y is None else None
+            h = self._embed_conv_in(graph, "union") if y is None else None
             for k in range(max(fl.neighbours - 2, 1)):
                 if k == 0 and y is not None:           # the first hidden layer's dense part came fused with conv_in
-                    h = hid(y, ei, graph.edge_attr, graph=graph, name="union", dense_done=True)
-                    continue
-                h = hid(h, ei, graph.edge_attr, graph=graph, name="union", in_elu=True) if fold \
-                    else hid(act(h), ei, graph.edge_attr, graph=graph, name="union")
-            h = self.conv_out(h, ei, graph=graph, name="union", in_elu=True) if fold \
-                else self.conv_out(act(h), ei, graph=graph, name="union")
+                    h = self._conv(hid, y, graph, "union", dense_done=True)
+                else:
+                    h = self._conv(hid, pre(h), graph, "union", in_elu=fold)
+            h = self._conv(self.conv_out, pre(h), graph, "union", in_elu=fold)
         elif fl.base_model:                                                    # gnn.py:143-150
-            h = self._embed_conv_in_then_dense(graph, graph.edge_index, "sim", self.linear_out.weight, self.linear_out.bias)
+            h = self._embed_conv_in_then_dense(graph, "sim", self.linear_out.weight, self.linear_out.bias)
             if h is None:
-                h = self._embed_conv_in(graph, graph.edge_index, "sim")
-                h = PF.linear(h, self.linear_out.weight, self.linear_out.bias, 1) if fold \
-                    else PF.linear(act(h), self.linear_out.weight, self.linear_out.bias)
+                h = self._embed_conv_in(graph, "sim")
+                h = self._linear(pre(h), self.linear_out.weight, self.linear_out.bias, 1 if fold else 0)
         else:                                                                  # gnn.py:153-166
             out = self.conv_out
-            y = self._embed_conv_in_then_dense(graph, graph.edge_index, "sim", out.lin.weight, None) \
+            y = self._embed_conv_in_then_dense(graph, "sim", out.lin.weight, None) \
                 if out.in_channels >= out.out_channels else None
             if y is not None:                          # conv_out's dense part came fused with conv_in: propagate + bias left
-                h = out(y, graph.neighbour_edge_index, graph=graph, name="nb", dense_done=True)
+                h = self._conv(out, y, graph, "nb", dense_done=True)
             else:
-                h = self._embed_conv_in(graph, graph.edge_index, "sim")
-                h = out(h, graph.neighbour_edge_index, graph=graph, name="nb", in_elu=True) if fold \
-                    else out(act(h), graph.neighbour_edge_index, graph=graph, name="nb")
+                h = self._conv(out, pre(self._embed_conv_in(graph, "sim")), graph, "nb", in_elu=fold)
         return h, True
 
     def encode(self, graph) -> torch.Tensor:
         h, pending = self._encode_pre(graph)
         return self.activation_fct(h) if pending else h
 
-    def _decoder_inputs(self, z, graph, in_act: int = 0):
-        """(pq [N,2D], structure, extra, cvec) of the re-associated first decoder layer"""
-        fl = self.flags
-        ei = graph.edge_index
-        st = structure_of(ei, z.shape[0], holder=graph, name="sim")
-        d = z.shape[1]
-        extra = graph.edge_attr[: ei.shape[1]] if fl.skip_connections else None
-        w = self.mlp[0].weight
-        w_pq, b_pq, cvec = PF.pq_operands(w, self.mlp[0].bias, d, bool(fl.skip_connections))
-        # bf16 / fp16 mixed precision: mlp[0] is an autocast Linear, its node-level halves are stored (and gathered) in that type
-        pq_dtype = PF.autocast_rows_dtype(z) if (d == 64 and PF.DECODER_PRECISION == 1) else None
-        return PF.linear(z, w_pq, b_pq, in_act, pq_dtype), st, extra, cvec
+    def _fused_width(self) -> bool:
+        """node_dim is the one width the fused per-edge MLP kernels are built for (csrc/decoder_mlp.hip)"""
+        return self.mlp[2].in_features == 64
+
+    def _decoder16(self) -> bool:
+        """the fused kernels run in their default precision mode: the one-pass training decoder is functional._decoder_train16
+        and P | Q rows are read as stored, so under bf16 / fp16 autocast they may be stored in the autocast type"""
+        return self._fused_width() and PF.DECODER_PRECISION == 1
+
+    def _skip_feature(self, graph):
+        """the per-edge input of `--skip_connections` (gnn.py:173), else None"""
+        return graph.edge_attr[: graph.edge_index.shape[1]] if self.flags.skip_connections else None
+
+    def _decoder_pq(self, z, graph, in_act: int = 0, rows16: bool = True):
+        """(P | Q [N, 2D], extra, cvec) of the re-associated first decoder layer: ONE node-level product
+        z [W_a ; W_b]^T + [0 ; b1].  bf16 / fp16 mixed precision: mlp[0] is an autocast Linear, its node-level halves are
+        stored (and gathered) in that type where the decoder kernel reads them so (`rows16`: the caller's decoder does)"""
+        lin0 = self.mlp[0]
+        w_pq, b_pq, cvec = PF.pq_operands(lin0.weight, lin0.bias, z.shape[1], bool(self.flags.skip_connections))
+        pq_dtype = PF.autocast_rows_dtype(z) if (rows16 and self._decoder16()) else None
+        return self._linear(z, w_pq, b_pq, in_act, pq_dtype), self._skip_feature(graph), cvec
 
     def _fused_decoder_operands(self, graph):
         """(pq, structure, extra, cvec) of the one-pass training decoder, or None where that kernel does not apply (another
-        decoder, node_dim != 64, no gradient wanted): the encoder (gnn.py:125-166) with its last ELU folded into the
-        node-level half of `mlp[0]` (gnn.py:110,173-175)"""
+        decoder, a node_dim it is not built for, no gradient wanted): the encoder (gnn.py:125-166) with its last ELU folded
+        into the node-level half of `mlp[0]` (gnn.py:110,173-175)"""
         z, pending = self._encode_pre(graph)
-        fused = "mlp" in self.flags.decoder and self.fused_decoder is True and z.shape[1] == 64 and torch.is_grad_enabled()
+        fused = "mlp" in self.flags.decoder and self.fused_decoder is True and self._fused_width() and torch.is_grad_enabled()
         if not (fused and pending and self._fold_elu()):
             z, pending = (self.activation_fct(z) if pending else z), False
         if not fused:
             return None, z
-        return self._decoder_inputs(z, graph, 1 if pending else 0), z
+        st = structure_of(graph.edge_index, z.shape[0], holder=graph, name="sim")
+        pq, extra, cvec = self._decoder_pq(z, graph, 1 if pending else 0)
+        return (pq, st, extra, cvec), z
 
     def loss_and_logits(self, graph, labels, pos_weight=None):
         """`criterion(model(graph), labels)` (pangnn.py:200-203) as ONE decoder pass when the fused kernel
@@ -261,7 +289,7 @@ class AlternateGCN(nn.Module):
         wants plain tensors: `loss_and_logits` is the traceable training entry)"""
         fl = self.flags
         return (self.deferred_logits and self.training and torch.is_grad_enabled() and fl.decoder == "mlp"
-                and self.fused_decoder is True and self.mlp[2].in_features == 64 and PF.DECODER_PRECISION == 1
+                and self.fused_decoder is True and self._decoder16()
                 and not torch.compiler.is_compiling() and not PF.observed())
 
     def _decode(self, nodes, graph):
@@ -276,26 +304,19 @@ class AlternateGCN(nn.Module):
         return out
 
     def decode_mlp(self, z, graph) -> torch.Tensor:
-        fl = self.flags
-        ei = graph.edge_index
-        st = structure_of(ei, z.shape[0], holder=graph, name="sim")
+        st = structure_of(graph.edge_index, z.shape[0], holder=graph, name="sim")
         d = z.shape[1]
-        extra = graph.edge_attr[: ei.shape[1]] if fl.skip_connections else None   # gnn.py:173
-        lin0 = self.mlp[0]
         if self.fused_decoder and d % 4 == 0:
-            w = lin0.weight
-            # one node-level product gives P | Q = z [W_a ; W_b]^T + [0 ; b1]
-            w_pq, b_pq, cvec = PF.pq_operands(w, lin0.bias, d, bool(fl.skip_connections))
-            fused = d == 64 and self.fused_decoder != "pair_add"
-            pq_dtype = PF.autocast_rows_dtype(z) if (fused and PF.DECODER_PRECISION == 1) else None
-            pq = PF.linear(z, w_pq, b_pq, 0, pq_dtype)
+            # `fused_decoder="pair_add"` keeps the layer-by-layer form behind the P | Q rows, which reads them as fp32
+            fused = self._fused_width() and self.fused_decoder != "pair_add"
+            pq, extra, cvec = self._decoder_pq(z, graph, rows16=fused)
             if fused:
                 # whole per-edge MLP in one HIP kernel (f32 MFMA), no [E, D] tensor in HBM on the way
                 return PF.decoder_mlp_pq(pq, st, extra, cvec, self.mlp[2].weight, self.mlp[2].bias,
                                          self.mlp[4].weight.view(-1), self.mlp[4].bias)
             h = PF.edge_pair_add(pq[:, :d].contiguous(), pq[:, d:].contiguous(), st, extra, cvec)
         else:
-            h = lin0(PF.edge_gather_concat(z, st, extra))
+            h = self.mlp[0](PF.edge_gather_concat(z, st, self._skip_feature(graph)))
         for layer in list(self.mlp)[1:]:
             # [E, D] intermediates are the largest tensors of the step: rectify them in place
             h = torch.relu_(h) if isinstance(layer, nn.ReLU) else layer(h)
