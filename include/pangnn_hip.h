@@ -619,6 +619,25 @@ int    pangnn_best_candidate_f64(const int64_t* seg_rowptr, const int32_t* seg_e
                                  int64_t num_edges, const double* value, const float* y, int64_t* counts, uint8_t* label,
                                  pangnn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Connected components of the kept edges: the groups that write_groups_file (src/postprocessing.py:5-36, called commented
+ * out at pangnn.py:375) is meant to produce from the binary predictions.  The reference's loop cannot run (it never
+ * initialises its list of sets and never merges two sets), so the semantics are defined here (pangnn_amd/postprocessing.py):
+ * the graph of kept edges is undirected; edge e is kept when keep[e] != 0 (keep_itemsize 1: one byte per edge, e.g. a bool
+ * mask; 4: one 32-bit word per edge, e.g. the int32 predictions of predict_homolog_genes, read as stored; 0: every edge is
+ * kept and `keep` is not read).  Writes
+ *   labels[v]  = the smallest node id of v's connected component (v itself for a node no kept edge joins to another),
+ *   touched[v] = 1 when a kept edge (a self loop included) has v as an endpoint, else 0          (nullable),
+ *   status[0]  = non-zero iff a kept edge names a node outside [0, num_nodes); such an edge is skipped, never dereferenced.
+ * Three launches on `stream`: init, one lock-free union-find pass over the edges (integer atomicCAS / atomicMin on labels,
+ * the larger root hooked onto the smaller id, so labels[x] <= x throughout), compress.  The result does not depend on the
+ * order of edges, on duplicates or on scheduling.  src / dst are read for kept edges only.  num_nodes >= 2^31:
+ * PANGNN_E_TOOLARGE.  num_edges == 0 or num_nodes == 0 still initialises labels, touched and status.
+ * ---------------------------------------------------------------------------------------- */
+int    pangnn_components_i32(const int64_t* src, const int64_t* dst, const void* keep, int keep_itemsize,
+                             int64_t num_edges, int64_t num_nodes, int32_t* labels, uint8_t* touched, int32_t* status,
+                             pangnn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

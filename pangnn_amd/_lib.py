@@ -121,6 +121,9 @@ SIGNATURES = {
     # max-candidate labelling (csrc/candidates.hip): (seg_rowptr, seg_edge, num_segments, num_edges, value, y, counts, label, stream)
     "pangnn_best_candidate_f32": (C.c_int, [_p, _p, _i64, _i64, _p, _p, _p, _p, _p]),
     "pangnn_best_candidate_f64": (C.c_int, [_p, _p, _i64, _i64, _p, _p, _p, _p, _p]),
+    # components of the kept edges (csrc/components.hip): (src, dst, keep, keep_itemsize, num_edges, num_nodes, labels, touched,
+    # status, stream)
+    "pangnn_components_i32": (C.c_int, [_p, _p, _p, C.c_int, _i64, _i64, _p, _p, _p, _p]),
 }
 
 ABI_VERSION = 3          # PANGNN_ABI_VERSION of include/pangnn_hip.h this binding was written against

@@ -1250,3 +1250,4 @@ def pq_operands(w, b, d: int, skip: bool):
 
 
 from .candidates import best_candidate, candidate_baselines   # noqa: E402,F401  (max-candidate labelling, csrc/candidates.hip)
+from .postprocessing import connected_components, homolog_groups   # noqa: E402,F401  (components of the predicted edges, csrc/components.hip)
