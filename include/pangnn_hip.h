@@ -638,6 +638,40 @@ int    pangnn_components_i32(const int64_t* src, const int64_t* dst, const void*
                              int64_t num_edges, int64_t num_nodes, int32_t* labels, uint8_t* touched, int32_t* status,
                              pangnn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Fused EdgeConv (src/convolution.py:5-23): out[i] = b2 + max over the edges e = (j -> i) of W2 relu(u[i] + v[j]), 0 for a row
+ * without in-edges, where u = x (Wa - Wb)^T + b1 and v = x Wb^T are the first Linear of mlp(cat[x_i, x_j - x_i]) taken at
+ * node level by the caller ([num_nodes, out_dim] f32, row strides ldu / ldv in elements, 16-byte aligned).  out_dim in
+ * {64, 128}; any other width: PANGNN_E_BADARG.  The graph is its by-target CSR (rowptr int64 [num_nodes + 1], col = source
+ * and perm = original edge id per sorted entry, int32) plus the caller's edge_index [2, ld] (the target of entry k is
+ * edge_index[ld + perm[k]]).  Nothing of size num_edges x out_dim exists: the product runs per 32-entry tile on
+ * v_mfma_f32_32x32x2_f32 and the per-row maximum is taken on chip; rows that cross the chunks of entries a wave owns (hub
+ * rows) leave one partial per chunk in `scratch`, combined by a second launch.
+ *   arg[i][c] = original id of the edge whose message is out[i][c] - b2[c]; -1 on rows without in-edges.
+ * Semantics of pangnn_segment_max_rows_f32: the first maximum in ascending edge id wins, NaN propagates, the maximum is
+ * taken over the messages alone (an all-negative row returns that negative value).  Bitwise reproducible, no atomics.
+ * `scratch`: pangnn_edge_conv_scratch_bytes(num_edges, out_dim, backward = 0 / 1) bytes (bounded in num_edges but for one
+ * byte per edge in the backward); smaller: PANGNN_E_WORKSPACE.
+ *
+ * pangnn_edge_conv_bwd_f32: with s_e[c] = g[i][c] * [arg[i][c] == e], h_e = relu(u[i] + v[j]) recomputed,
+ *   gh_e = (W2^T s_e) * [h_e > 0],  gu[i] = sum over in-edges,  gv[j] = sum over out-edges,  gw2 = sum_e s_e h_e^T.
+ * One pass over the by-target CSR (gu, gw2) and one over the by-source CSR (src_*: rowptr, col = target, perm), each in CSR
+ * order; tiles none of whose edges is an arg-max skip the products.  arg [num_nodes, out_dim] contiguous, as the forward
+ * wrote it; g / gu / gv row strides ldg / ldgrad.  Fixed-order sums, no float atomics.
+ * ---------------------------------------------------------------------------------------- */
+int64_t pangnn_edge_conv_scratch_bytes(int64_t num_edges, int32_t out_dim, int backward);
+int    pangnn_edge_conv_fwd_f32(const float* u, int64_t ldu, const float* v, int64_t ldv, int64_t num_nodes,
+                                const float* w2, const float* b2, int32_t out_dim, const int64_t* rowptr,
+                                const int32_t* col, const int32_t* perm, const int64_t* edge_index, int64_t ld,
+                                int64_t num_edges, float* out, int32_t* arg, int64_t ldo, void* scratch,
+                                int64_t scratch_bytes, pangnn_stream_t stream);
+int    pangnn_edge_conv_bwd_f32(const float* g, int64_t ldg, const int32_t* arg, const float* u, int64_t ldu,
+                                const float* v, int64_t ldv, int64_t num_nodes, const float* w2, int32_t out_dim,
+                                const int64_t* dst_rowptr, const int32_t* dst_col, const int32_t* dst_perm,
+                                const int64_t* src_rowptr, const int32_t* src_col, const int32_t* src_perm,
+                                const int64_t* edge_index, int64_t ld, int64_t num_edges, float* gu, float* gv,
+                                int64_t ldgrad, float* gw2, void* scratch, int64_t scratch_bytes, pangnn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

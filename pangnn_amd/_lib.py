@@ -124,6 +124,15 @@ SIGNATURES = {
     # components of the kept edges (csrc/components.hip): (src, dst, keep, keep_itemsize, num_edges, num_nodes, labels, touched,
     # status, stream)
     "pangnn_components_i32": (C.c_int, [_p, _p, _p, C.c_int, _i64, _i64, _p, _p, _p, _p]),
+    # fused EdgeConv (csrc/edge_conv.hip): (u, ldu, v, ldv, num_nodes, w2, b2, out, rowptr, col, perm, edge_index, ld, num_edges,
+    # out, arg, ldo, scratch, scratch_bytes, stream)
+    "pangnn_edge_conv_scratch_bytes": (_i64, [_i64, _i32, C.c_int]),
+    "pangnn_edge_conv_fwd_f32": (C.c_int, [_p, _i64, _p, _i64, _i64, _p, _p, _i32, _p, _p, _p, _p, _i64, _i64, _p, _p, _i64,
+                                           _p, _i64, _p]),
+    # (g, ldg, arg, u, ldu, v, ldv, num_nodes, w2, out, by-target rowptr / col / perm, by-source rowptr / col / perm,
+    # edge_index, ld, num_edges, gu, gv, ldgrad, gw2, scratch, scratch_bytes, stream)
+    "pangnn_edge_conv_bwd_f32": (C.c_int, [_p, _i64, _p, _p, _i64, _p, _i64, _i64, _p, _i32, _p, _p, _p, _p, _p, _p,
+                                           _p, _i64, _i64, _p, _p, _i64, _p, _p, _i64, _p]),
 }
 
 ABI_VERSION = 3          # PANGNN_ABI_VERSION of include/pangnn_hip.h this binding was written against

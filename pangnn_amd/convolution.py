@@ -172,7 +172,25 @@ class EdgeConv(MessagePassing):
         super().__init__(aggr="max")
         self.mlp = Seq(Linear(2 * in_channels, out_channels), ReLU(), Linear(out_channels, out_channels))
 
+    def _fusable(self, x) -> bool:
+        """the fused route (functional.edge_conv, csrc/edge_conv.hip) computes exactly this class's `message` for
+        mlp = Seq(Linear, ReLU, Linear) of width 64 / 128 on fp32 device rows outside autocast; anything else — a subclass
+        with its own `message`, another mlp, 16-bit rows — keeps the literal propagate"""
+        m = self.mlp
+        return (PF.FUSE_EDGE_CONV and type(self).message is EdgeConv.message
+                and type(m) is Seq and len(m) == 3 and type(m[0]) is Linear and type(m[1]) is ReLU and type(m[2]) is Linear
+                and m[0].bias is not None and m[2].bias is not None
+                and m[2].out_features in PF.EDGE_CONV_WIDTHS and m[2].in_features == m[2].out_features == m[0].out_features
+                and x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and m[0].in_features == 2 * x.shape[1]
+                and m[0].weight.dtype == torch.float32 and not torch.is_autocast_enabled())
+
     def forward(self, x, edge_index):
+        if self._fusable(x):
+            _lib.require_device(x, edge_index)
+            st = structure_of(edge_index, x.shape[0])
+            if st.num_src == st.num_nodes:              # (a partitioned shard's rectangular structure: literal route)
+                m = self.mlp
+                return PF.edge_conv(x, m[0].weight, m[0].bias, m[2].weight, m[2].bias, st)
         return self.propagate(edge_index, x=x)
 
     def message(self, x_i, x_j):

@@ -1,5 +1,6 @@
 // The per-step operators that READ A GRAPH, in C++ end to end (round 5):
-//   gcn_propagate, embed_conv_in, embed_conv_in_linear, embed_propagate, decoder_loss, decoder_mlp, edge_score, edge_score_loss
+//   gcn_propagate, embed_conv_in, embed_conv_in_linear, embed_propagate, decoder_loss, decoder_mlp, edge_score, edge_score_loss,
+//   edge_conv
 //   and their backward ops
 // — schema, HIP ("CUDA" key) implementation and autograd formula (torch::autograd::Function under the Autograd key), like
 // pangnn::linear.  Rounds 3-4 registered them from Python over ctypes because the structure cache lived in Python.
@@ -852,6 +853,78 @@ at::Tensor edge_score_backward(const at::Tensor& g, const at::Tensor& z, const a
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// fused EdgeConv (csrc/edge_conv.hip) on the node-level operands u = x (Wa - Wb)^T + b1, v = x Wb^T of its first Linear:
+// out[i] = b2 + max over the in-edges (j -> i) of W2 relu(u[i] + v[j]) and the winning edge ids; no [E, .] tensor
+// ---------------------------------------------------------------------------------------------------------------
+at::Tensor conv_rows(const char* op, const char* name, const at::Tensor& t, int64_t n, int64_t f) {
+  on_gpu(t, name);
+  TORCH_CHECK(t.dim() == 2 && t.size(0) == n && t.size(1) == f && t.is_floating_point(), "pangnn::", op, ": ", name,
+              " must be a floating-point [", n, ", ", f, "] tensor, got ", t.sizes());
+  return rows_any(t.to(at::kFloat));
+}
+
+std::tuple<at::Tensor, at::Tensor> edge_conv(const at::Tensor& u, const at::Tensor& v, const at::Tensor& w2, const at::Tensor& b2,
+                                             const at::Tensor& edge_index) {
+  const char* op = "edge_conv";
+  on_gpu(u, "u");
+  TORCH_CHECK(u.dim() == 2 && w2.dim() == 2 && (w2.size(0) == 64 || w2.size(0) == 128) && w2.size(1) == w2.size(0) &&
+                  b2.numel() == w2.size(0), "pangnn::edge_conv: w2 must be [out, out] and b2 [out] with out 64 or 128, got ",
+              w2.sizes());
+  const int64_t n = u.size(0), f = w2.size(0);
+  const at::Tensor ur = conv_rows(op, "u", u, n, f), vr = conv_rows(op, "v", v, n, f);
+  operand_any_float(op, "w2", w2, u);
+  operand_any_float(op, "b2", b2, u);
+  const at::Tensor w = f32c(w2), b = f32c(b2);
+  const DeviceGuard guard(u.device());
+  const View vw = lookup(op, edge_index, n, c10::nullopt, c10::nullopt, kByDst);
+  TORCH_CHECK(vw.n_src == vw.n_dst, "pangnn::edge_conv: a whole (square) graph is needed");
+  const int64_t e = vw.num_edges;
+  auto fo = ur.options();
+  at::Tensor out = at::empty({n, f}, fo), arg = at::empty({n, f}, fo.dtype(at::kInt));
+  const at::Tensor ws = bytes((size_t)std::max<int64_t>(pangnn_edge_conv_scratch_bytes(e, (int32_t)f, 0), 16), ur);
+  check_rc(pangnn_edge_conv_fwd_f32(ur.data_ptr<float>(), ur.stride(0), vr.data_ptr<float>(), vr.stride(0), n,
+                                    w.data_ptr<float>(), b.data_ptr<float>(), (int32_t)f, vw.by_dst.rowptr.data_ptr<int64_t>(),
+                                    vw.by_dst.other.data_ptr<int32_t>(), vw.by_dst.perm.data_ptr<int32_t>(),
+                                    vw.ei.data_ptr<int64_t>(), e, e, out.data_ptr<float>(), arg.data_ptr<int32_t>(), f,
+                                    ws.data_ptr(), ws.numel(), stream_of(u)),
+           "pangnn_edge_conv_fwd_f32");
+  return {out, arg};
+}
+
+// (dL/du, dL/dv [N, out], dL/dW2 [out, out], dL/db2 [out])
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> edge_conv_backward(const at::Tensor& g, const at::Tensor& arg,
+                                                                              const at::Tensor& u, const at::Tensor& v,
+                                                                              const at::Tensor& w2, const at::Tensor& edge_index) {
+  const char* op = "edge_conv_backward";
+  on_gpu(g, "g");
+  TORCH_CHECK(w2.dim() == 2 && (w2.size(0) == 64 || w2.size(0) == 128) && w2.size(1) == w2.size(0),
+              "pangnn::edge_conv_backward: w2 must be [out, out] with out 64 or 128, got ", w2.sizes());
+  const int64_t n = u.size(0), f = w2.size(0);
+  const at::Tensor gr = conv_rows(op, "g", g, n, f), ur = conv_rows(op, "u", u, n, f), vr = conv_rows(op, "v", v, n, f);
+  operand(op, "arg", arg, g, at::kInt);
+  TORCH_CHECK(arg.dim() == 2 && arg.size(0) == n && arg.size(1) == f, "pangnn::edge_conv_backward: arg must be [N, out]");
+  operand_any_float(op, "w2", w2, g);
+  const at::Tensor w = f32c(w2), ac = arg.contiguous();
+  const DeviceGuard guard(g.device());
+  const View vw = lookup(op, edge_index, n, c10::nullopt, c10::nullopt, kByDst | kBySrc);
+  const int64_t e = vw.num_edges;
+  auto fo = gr.options();
+  at::Tensor gu = at::empty({n, f}, fo), gv = at::empty({n, f}, fo), gw2 = at::empty({f, f}, fo);
+  const at::Tensor ws = bytes((size_t)std::max<int64_t>(pangnn_edge_conv_scratch_bytes(e, (int32_t)f, 1), 16), gr);
+  check_rc(pangnn_edge_conv_bwd_f32(gr.data_ptr<float>(), gr.stride(0), ac.data_ptr<int32_t>(), ur.data_ptr<float>(),
+                                    ur.stride(0), vr.data_ptr<float>(), vr.stride(0), n, w.data_ptr<float>(), (int32_t)f,
+                                    vw.by_dst.rowptr.data_ptr<int64_t>(), vw.by_dst.other.data_ptr<int32_t>(),
+                                    vw.by_dst.perm.data_ptr<int32_t>(), vw.by_src.rowptr.data_ptr<int64_t>(),
+                                    vw.by_src.other.data_ptr<int32_t>(), vw.by_src.perm.data_ptr<int32_t>(),
+                                    vw.ei.data_ptr<int64_t>(), e, e, gu.data_ptr<float>(), gv.data_ptr<float>(), f,
+                                    gw2.data_ptr<float>(), ws.data_ptr(), ws.numel(), stream_of(g)),
+           "pangnn_edge_conv_bwd_f32");
+  // dL/db2: the column sums of g over the rows that have in-edges (b2 does not reach the zero rows)
+  const at::Tensor gb2 = colsum(gr.masked_fill(ac.slice(1, 0, 1) < 0, 0.0));
+  return {gu, gv, gw2, gb2};
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // autograd formulas (Autograd key): forward redispatches below autograd, backward calls the registered backward op — a
 // tracer sees both
 // ---------------------------------------------------------------------------------------------------------------
@@ -1138,6 +1211,33 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> edge_score_loss_autog
   return {o[0], o[1], o[2], o[3]};
 }
 
+class EdgeConvFunction : public torch::autograd::Function<EdgeConvFunction> {
+ public:
+  static variable_list forward(AutogradContext* ctx, const at::Tensor& u, const at::Tensor& v, const at::Tensor& w2,
+                               const at::Tensor& b2, const at::Tensor& edge_index) {
+    at::AutoDispatchBelowADInplaceOrView below;
+    static auto op = typed_op<std::tuple<at::Tensor, at::Tensor>(const at::Tensor&, const at::Tensor&, const at::Tensor&,
+                                                                 const at::Tensor&, const at::Tensor&)>("pangnn::edge_conv");
+    auto [out, arg] = op.call(u, v, w2, b2, edge_index);
+    ctx->save_for_backward({arg, u, v, w2, edge_index});
+    ctx->mark_non_differentiable({arg});
+    return {out, arg};
+  }
+  static variable_list backward(AutogradContext* ctx, variable_list grads) {
+    const auto s = ctx->get_saved_variables();
+    static auto op = typed_op<std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor>(
+        const at::Tensor&, const at::Tensor&, const at::Tensor&, const at::Tensor&, const at::Tensor&, const at::Tensor&)>(
+        "pangnn::edge_conv_backward");
+    auto [gu, gv, gw2, gb2] = op.call(grads[0], s[0], s[1], s[2], s[3], s[4]);
+    return {gu, gv, gw2, gb2, at::Tensor()};
+  }
+};
+std::tuple<at::Tensor, at::Tensor> edge_conv_autograd(const at::Tensor& u, const at::Tensor& v, const at::Tensor& w2,
+                                                      const at::Tensor& b2, const at::Tensor& edge_index) {
+  auto o = EdgeConvFunction::apply(u, v, w2, b2, edge_index);
+  return {o[0], o[1]};
+}
+
 }  // namespace
 
 TORCH_LIBRARY_FRAGMENT(pangnn, m) {
@@ -1175,6 +1275,8 @@ TORCH_LIBRARY_FRAGMENT(pangnn, m) {
   // weightless link decoders: mode 0 = dot, 1 = cosine; norms [N, 2] (cosine) / [0, 2] (dot) feed the backward
   m.def("edge_score(Tensor z, Tensor edge_index, int mode) -> (Tensor, Tensor)");
   m.def("edge_score_backward(Tensor g, Tensor z, Tensor edge_index, Tensor logits, Tensor norms, Tensor? g_scale, int mode) -> Tensor");
+  m.def("edge_conv(Tensor u, Tensor v, Tensor w2, Tensor b2, Tensor edge_index) -> (Tensor, Tensor)");
+  m.def("edge_conv_backward(Tensor g, Tensor arg, Tensor u, Tensor v, Tensor w2, Tensor edge_index) -> (Tensor, Tensor, Tensor, Tensor)");
   m.def("edge_score_loss(Tensor z, Tensor edge_index, int mode, Tensor y, Tensor? pos_weight, int denom) -> "
         "(Tensor, Tensor, Tensor, Tensor)");
 }
@@ -1205,6 +1307,8 @@ TORCH_LIBRARY_IMPL(pangnn, CUDA, m) {
   m.impl("edge_score", &edge_score);
   m.impl("edge_score_backward", &edge_score_backward);
   m.impl("edge_score_loss", &edge_score_loss);
+  m.impl("edge_conv", &edge_conv);
+  m.impl("edge_conv_backward", &edge_conv_backward);
 }
 
 TORCH_LIBRARY_IMPL(pangnn, Autograd, m) {
@@ -1216,4 +1320,5 @@ TORCH_LIBRARY_IMPL(pangnn, Autograd, m) {
   m.impl("decoder_mlp", &decoder_mlp_autograd);
   m.impl("edge_score", &edge_score_autograd);
   m.impl("edge_score_loss", &edge_score_loss_autograd);
+  m.impl("edge_conv", &edge_conv_autograd);
 }

@@ -413,6 +413,103 @@ def segment_sum(msg, st: EdgeStructure):
     return _SegmentSum.apply(msg, st)
 
 
+# ---- fused EdgeConv (convolution.py:5-23): csrc/edge_conv.hip
+# PANGNN_FUSE_EDGE_CONV=0: EdgeConv.forward keeps the literal gather / MLP / segment-max route (the A/B baseline)
+FUSE_EDGE_CONV = os.environ.get("PANGNN_FUSE_EDGE_CONV", "1") != "0"
+EDGE_CONV_WIDTHS = (64, 128)
+
+
+def _edge_conv_scratch(lib, e: int, out: int, backward: bool, dev) -> torch.Tensor:
+    return torch.empty(max(int(lib.pangnn_edge_conv_scratch_bytes(e, out, int(backward))), 16), dtype=torch.uint8, device=dev)
+
+
+def edge_conv_max_fwd(u, v, w2, b2, st: EdgeStructure):
+    """(out [N, out] f32, arg [N, out] i32) of pangnn_edge_conv_fwd_f32: out[i] = b2 + max over in-edges (j -> i) of
+    W2 relu(u[i] + v[j]), 0 / -1 on rows without in-edges"""
+    lib = _lib.load()
+    _lib.require_device(u, v, w2, b2)
+    u, v, w2, b2 = _rows_f32(u), _rows_f32(v), _f32c(w2), _f32c(b2)
+    n, f = st.num_nodes, w2.shape[0]
+    if f not in EDGE_CONV_WIDTHS or tuple(w2.shape) != (f, f) or tuple(u.shape) != (n, f) or tuple(v.shape) != (n, f) \
+            or st.num_src != n:
+        raise ValueError(f"edge_conv: out width {f} (64 / 128), u / v [N, out] of a whole graph; got u {tuple(u.shape)}, "
+                         f"v {tuple(v.shape)}, w2 {tuple(w2.shape)}, N = {n}")
+    d = st.by_dst
+    out = torch.empty(n, f, dtype=torch.float32, device=u.device)
+    arg = torch.empty(n, f, dtype=torch.int32, device=u.device)
+    with _lib.device_guard(u.device):
+        ws = _edge_conv_scratch(lib, st.num_edges, f, False, u.device)
+        _lib.check(lib.pangnn_edge_conv_fwd_f32(u.data_ptr(), u.stride(0), v.data_ptr(), v.stride(0), n, w2.data_ptr(),
+                                                b2.data_ptr(), f, d.rowptr.data_ptr(), _lib.ptr(d.other), _lib.ptr(d.perm),
+                                                st.edge_index.data_ptr(), st.num_edges, st.num_edges, out.data_ptr(),
+                                                arg.data_ptr(), f, ws.data_ptr(), ws.numel(), _lib.stream_ptr()),
+                   "pangnn_edge_conv_fwd_f32")
+    return out, arg
+
+
+def edge_conv_max_bwd(g, arg, u, v, w2, st: EdgeStructure):
+    """(gu, gv [N, out], gW2 [out, out], gb2 [out]) of pangnn_edge_conv_bwd_f32; gb2 = column sums of g over the rows that
+    have in-edges"""
+    lib = _lib.load()
+    g, u, v, w2 = _rows_f32(g), _rows_f32(u), _rows_f32(v), _f32c(w2)
+    n, f = st.num_nodes, w2.shape[0]
+    d, s = st.by_dst, st.by_src
+    gu = torch.empty(n, f, dtype=torch.float32, device=g.device)
+    gv = torch.empty(n, f, dtype=torch.float32, device=g.device)
+    gw2 = torch.empty(f, f, dtype=torch.float32, device=g.device)
+    with _lib.device_guard(g.device):
+        ws = _edge_conv_scratch(lib, st.num_edges, f, True, g.device)
+        _lib.check(lib.pangnn_edge_conv_bwd_f32(g.data_ptr(), g.stride(0), arg.data_ptr(), u.data_ptr(), u.stride(0),
+                                                v.data_ptr(), v.stride(0), n, w2.data_ptr(), f, d.rowptr.data_ptr(),
+                                                _lib.ptr(d.other), _lib.ptr(d.perm), s.rowptr.data_ptr(), _lib.ptr(s.other),
+                                                _lib.ptr(s.perm), st.edge_index.data_ptr(), st.num_edges, st.num_edges,
+                                                gu.data_ptr(), gv.data_ptr(), f, gw2.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                _lib.stream_ptr()), "pangnn_edge_conv_bwd_f32")
+    gb2 = colsum(g.masked_fill(arg[:, :1] < 0, 0.0))
+    return gu, gv, gw2, gb2
+
+
+class _EdgeConvMax(torch.autograd.Function):
+    """the edge part of the fused EdgeConv on node-level operands u, v (edge_conv_max_fwd / _bwd); `arg` is saved for the
+    backward and handed out non-differentiable"""
+
+    @staticmethod
+    def forward(ctx, u, v, w2, b2, st: EdgeStructure):
+        out, arg = edge_conv_max_fwd(u, v, w2, b2, st)
+        ctx.st = st
+        ctx.save_for_backward(arg, u, v, w2)
+        ctx.mark_non_differentiable(arg)
+        return out, arg
+
+    @staticmethod
+    def backward(ctx, g, _g_arg):
+        arg, u, v, w2 = ctx.saved_tensors
+        gu, gv, gw2, gb2 = edge_conv_max_bwd(g, arg, u, v, w2, ctx.st)
+        return gu, gv, gw2, gb2, None
+
+
+def edge_conv(x, w1, b1, w2, b2, st: EdgeStructure, return_arg: bool = False):
+    """EdgeConv's max over in-edges of mlp(cat[x_i, x_j - x_i]) with mlp = Linear(2C, out), ReLU, Linear(out, out), out in
+    {64, 128}, without any [E, .] tensor.  The first Linear is taken at node level by linearity: with w1 = [Wa | Wb],
+    W1 cat[x_i, x_j - x_i] + b1 = u_i + v_j for u = x (Wa - Wb)^T + b1, v = x Wb^T (two `linear` calls, through which autograd
+    maps dL/du, dL/dv back to x, w1 and b1); the rest is one pass over the by-target CSR (csrc/edge_conv.hip).
+    `return_arg=True`: also the int32 [N, out] original id of the winning edge per (row, channel), -1 on rows without in-edges."""
+    _lib.require_device(x, w1, b1, w2, b2)
+    c = x.shape[1]
+    if w1.shape[1] != 2 * c or w2.shape[0] not in EDGE_CONV_WIDTHS:
+        raise ValueError(f"edge_conv: w1 must be [out, 2 * {c}] and out 64 or 128, got w1 {tuple(w1.shape)}, "
+                         f"w2 {tuple(w2.shape)}")
+    wa, wb = w1[:, :c], w1[:, c:]
+    u = linear(x, (wa - wb).contiguous(), b1)
+    v = linear(x, wb.contiguous(), None)
+    if _via_ops(st):
+        from . import torch_ops
+        out, arg = torch_ops.edge_conv(u, v, w2, b2, st)
+    else:
+        out, arg = _EdgeConvMax.apply(u, v, w2, b2, st)
+    return (out, arg) if return_arg else out
+
+
 def d16_chunk(num_edges: Optional[int] = None) -> int:
     """tiles per run-sum chunk of the S / T kernels for a list of `num_edges` edges (pangnn_decoder_chunk_tiles_for: 16 for
     E >= 1e6, fewer for short lists so that a mini-batch still spreads over the chip); None: the maximum"""

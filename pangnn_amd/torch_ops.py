@@ -11,7 +11,7 @@ registers, on the same ops,
     stored (half the bytes) with fp32 weights / accumulation / result; float16 rows are promoted to fp32 (the kernels
     have no fp16 row format); everything else runs in fp32.
 The per-step operators of the train step that read a graph (gcn_propagate, embed_conv_in[_linear], embed_propagate,
-decoder_loss, decoder_mlp, edge_score, edge_score_loss and their backward ops) are C++ too since round 5 (csrc/graph_ops.cpp: schema, HIP implementation,
+decoder_loss, decoder_mlp, edge_score, edge_score_loss, edge_conv and their backward ops) are C++ too since round 5 (csrc/graph_ops.cpp: schema, HIP implementation,
 autograd formula, and the structure registry they look a graph up in by the identity of its `edge_index` tensor); the second
 half of this module holds their fake kernels, the registry's build-on-miss hook and the wrappers `functional` calls with this
 package's structure objects (`functional.USE_DISPATCHER_OPS`; PANGNN_DISPATCHER_OPS=auto: only when a tracer / dispatch mode
@@ -259,6 +259,17 @@ def _(z, edge_index, mode, y, pos_weight, denom):
     return f(), f(e), f(e), f(z.shape[0] if mode == 1 else 0, 2)
 
 
+@torch.library.register_fake("pangnn::edge_conv")
+def _(u, v, w2, b2, edge_index):
+    return u.new_empty(u.shape, dtype=torch.float32), u.new_empty(u.shape, dtype=torch.int32)
+
+
+@torch.library.register_fake("pangnn::edge_conv_backward")
+def _(g, arg, u, v, w2, edge_index):
+    f = lambda *s: g.new_empty(s, dtype=torch.float32)           # noqa: E731
+    return f(*u.shape), f(*v.shape), f(*w2.shape), f(w2.shape[0])
+
+
 # ---------------------------------------------------------------------------------------------- wrappers taking structures
 _N = _G
 
@@ -315,3 +326,8 @@ def edge_score_loss(z, st, mode, y, pos_weight, denom):
     _ready(st, _N.NEED_BY_DST | _N.NEED_BY_SRC)
     out = ops.edge_score_loss(z, st._key_tensor, int(mode), y, pos_weight, int(denom))
     return out[0], out[1]
+
+
+def edge_conv(u, v, w2, b2, st):
+    _ready(st, _N.NEED_BY_DST | _N.NEED_BY_SRC)          # the backward walks both CSR orders
+    return ops.edge_conv(u, v, w2, b2, st._key_tensor)
