@@ -172,10 +172,21 @@ class _Propagate(torch.autograd.Function):
         return gx, gb, None, None, None, None
 
 
-# The per-step operators (dense layer, GCN propagate, first layer by linearity, training / inference decoder, criterion)
-# are registered dispatcher ops `torch.ops.pangnn.*` (torch_ops.py: fake kernels, autograd formulas built from registered
-# ops) — what FakeTensor tracing / torch.compile / any TorchDispatchMode need to see them.  Same kernels and the same host
-# code as the ctypes autograd.Functions in this file, bit-identical results.  USE_DISPATCHER_OPS (PANGNN_DISPATCHER_OPS):
+# The per-step operators (dense layer, GCN propagate, first layer by linearity, training / inference decoder, weightless
+# decoders, fused EdgeConv, criterion) are registered dispatcher ops `torch.ops.pangnn.*` (csrc/torch_ops.cpp,
+# csrc/graph_ops.cpp; torch_ops.py holds their fake kernels) — what FakeTensor tracing / torch.compile / any
+# TorchDispatchMode need to see them.
+# The rule: an operator is written ONCE, as its dispatcher op, and its function here goes straight to it — linear,
+# bce_with_logits, edge_score, edge_score_loss, edge_conv.  A ctypes autograd.Function twin in this file (same kernels, same
+# host steps, bit-identical results) exists only where one of three things needs it, because the ops cannot serve it:
+#   a partitioned shard   its rectangular structures have no tensor-only description (the registry finds a graph by
+#                         edge_index and target rows): propagate, embed_propagate, embed_conv_in, embed_conv_in_linear, the
+#                         MLP decoder (decoder_mlp / decoder_loss);
+#   the kernel timer      bench.py's KERNEL_TIMER records event pairs around tagged launches on the ctypes route: propagate
+#                         (sim.fwd / sim.bwd), embed_propagate, the MLP decoder (dec.*);
+#   strict-fp32 mode      DECODER_PRECISION = 0: the MLP decoder.
+# An operator that none of the three reach has a single route, the dispatcher op, and raises on a rectangular structure.
+# USE_DISPATCHER_OPS (PANGNN_DISPATCHER_OPS) chooses the route of the operators that HAVE a twin:
 #   True / "1" (default since round 4)  every per-step operator of a whole (square) graph goes through its registered op —
 #                     eager, traced or captured alike: ONE route.  The registered-op wrapper (torch.library's autograd
 #                     plumbing) costs ~25 us of host time per call: nothing on a whole-graph step (12.83 vs 12.88 ms), nothing
@@ -185,8 +196,7 @@ class _Propagate(torch.autograd.Function):
 #   "auto"            through the ops only when somebody can observe them — torch.compile is tracing, or a dispatch /
 #                     function mode is active (FakeTensorMode, make_fx, a TorchDispatchMode) — and straight to the
 #                     autograd.Functions otherwise;
-#   False / "0"       never (the route a partitioned shard always takes: its rectangular structures have no tensor-only
-#                     description).
+#   False / "0"       never (the route a partitioned shard always takes).
 _mode = os.environ.get("PANGNN_DISPATCHER_OPS", "1").lower()
 USE_DISPATCHER_OPS = "auto" if _mode == "auto" else False if _mode in ("0", "false", "off") else True
 _dispatch_modes = getattr(torch._C, "_len_torch_dispatch_stack", lambda: 0)
@@ -204,6 +214,14 @@ def _via_ops(st: Optional[EdgeStructure] = None, tag=None) -> bool:
     if use == "auto":
         use = observed()
     return bool(use) and (st is None or st.num_src == st.num_nodes) and (KERNEL_TIMER is None or tag is None)
+
+
+def _whole_graph(op: str, st: EdgeStructure) -> None:
+    """an operator whose only route is its dispatcher op: the registry finds a graph by (edge_index, target rows), which
+    describes whole (square) graphs only"""
+    if st.num_src != st.num_nodes:
+        raise ValueError(f"{op}: a whole (square) graph is needed, got a structure of {st.num_src} source and "
+                         f"{st.num_nodes} target rows")
 
 
 def propagate(x, bias, st: EdgeStructure, norm: GcnNorm, tag=None, out_dtype=None):
@@ -419,75 +437,6 @@ FUSE_EDGE_CONV = os.environ.get("PANGNN_FUSE_EDGE_CONV", "1") != "0"
 EDGE_CONV_WIDTHS = (64, 128)
 
 
-def _edge_conv_scratch(lib, e: int, out: int, backward: bool, dev) -> torch.Tensor:
-    return torch.empty(max(int(lib.pangnn_edge_conv_scratch_bytes(e, out, int(backward))), 16), dtype=torch.uint8, device=dev)
-
-
-def edge_conv_max_fwd(u, v, w2, b2, st: EdgeStructure):
-    """(out [N, out] f32, arg [N, out] i32) of pangnn_edge_conv_fwd_f32: out[i] = b2 + max over in-edges (j -> i) of
-    W2 relu(u[i] + v[j]), 0 / -1 on rows without in-edges"""
-    lib = _lib.load()
-    _lib.require_device(u, v, w2, b2)
-    u, v, w2, b2 = _rows_f32(u), _rows_f32(v), _f32c(w2), _f32c(b2)
-    n, f = st.num_nodes, w2.shape[0]
-    if f not in EDGE_CONV_WIDTHS or tuple(w2.shape) != (f, f) or tuple(u.shape) != (n, f) or tuple(v.shape) != (n, f) \
-            or st.num_src != n:
-        raise ValueError(f"edge_conv: out width {f} (64 / 128), u / v [N, out] of a whole graph; got u {tuple(u.shape)}, "
-                         f"v {tuple(v.shape)}, w2 {tuple(w2.shape)}, N = {n}")
-    d = st.by_dst
-    out = torch.empty(n, f, dtype=torch.float32, device=u.device)
-    arg = torch.empty(n, f, dtype=torch.int32, device=u.device)
-    with _lib.device_guard(u.device):
-        ws = _edge_conv_scratch(lib, st.num_edges, f, False, u.device)
-        _lib.check(lib.pangnn_edge_conv_fwd_f32(u.data_ptr(), u.stride(0), v.data_ptr(), v.stride(0), n, w2.data_ptr(),
-                                                b2.data_ptr(), f, d.rowptr.data_ptr(), _lib.ptr(d.other), _lib.ptr(d.perm),
-                                                st.edge_index.data_ptr(), st.num_edges, st.num_edges, out.data_ptr(),
-                                                arg.data_ptr(), f, ws.data_ptr(), ws.numel(), _lib.stream_ptr()),
-                   "pangnn_edge_conv_fwd_f32")
-    return out, arg
-
-
-def edge_conv_max_bwd(g, arg, u, v, w2, st: EdgeStructure):
-    """(gu, gv [N, out], gW2 [out, out], gb2 [out]) of pangnn_edge_conv_bwd_f32; gb2 = column sums of g over the rows that
-    have in-edges"""
-    lib = _lib.load()
-    g, u, v, w2 = _rows_f32(g), _rows_f32(u), _rows_f32(v), _f32c(w2)
-    n, f = st.num_nodes, w2.shape[0]
-    d, s = st.by_dst, st.by_src
-    gu = torch.empty(n, f, dtype=torch.float32, device=g.device)
-    gv = torch.empty(n, f, dtype=torch.float32, device=g.device)
-    gw2 = torch.empty(f, f, dtype=torch.float32, device=g.device)
-    with _lib.device_guard(g.device):
-        ws = _edge_conv_scratch(lib, st.num_edges, f, True, g.device)
-        _lib.check(lib.pangnn_edge_conv_bwd_f32(g.data_ptr(), g.stride(0), arg.data_ptr(), u.data_ptr(), u.stride(0),
-                                                v.data_ptr(), v.stride(0), n, w2.data_ptr(), f, d.rowptr.data_ptr(),
-                                                _lib.ptr(d.other), _lib.ptr(d.perm), s.rowptr.data_ptr(), _lib.ptr(s.other),
-                                                _lib.ptr(s.perm), st.edge_index.data_ptr(), st.num_edges, st.num_edges,
-                                                gu.data_ptr(), gv.data_ptr(), f, gw2.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                _lib.stream_ptr()), "pangnn_edge_conv_bwd_f32")
-    gb2 = colsum(g.masked_fill(arg[:, :1] < 0, 0.0))
-    return gu, gv, gw2, gb2
-
-
-class _EdgeConvMax(torch.autograd.Function):
-    """the edge part of the fused EdgeConv on node-level operands u, v (edge_conv_max_fwd / _bwd); `arg` is saved for the
-    backward and handed out non-differentiable"""
-
-    @staticmethod
-    def forward(ctx, u, v, w2, b2, st: EdgeStructure):
-        out, arg = edge_conv_max_fwd(u, v, w2, b2, st)
-        ctx.st = st
-        ctx.save_for_backward(arg, u, v, w2)
-        ctx.mark_non_differentiable(arg)
-        return out, arg
-
-    @staticmethod
-    def backward(ctx, g, _g_arg):
-        arg, u, v, w2 = ctx.saved_tensors
-        gu, gv, gw2, gb2 = edge_conv_max_bwd(g, arg, u, v, w2, ctx.st)
-        return gu, gv, gw2, gb2, None
-
-
 def edge_conv(x, w1, b1, w2, b2, st: EdgeStructure, return_arg: bool = False):
     """EdgeConv's max over in-edges of mlp(cat[x_i, x_j - x_i]) with mlp = Linear(2C, out), ReLU, Linear(out, out), out in
     {64, 128}, without any [E, .] tensor.  The first Linear is taken at node level by linearity: with w1 = [Wa | Wb],
@@ -499,14 +448,12 @@ def edge_conv(x, w1, b1, w2, b2, st: EdgeStructure, return_arg: bool = False):
     if w1.shape[1] != 2 * c or w2.shape[0] not in EDGE_CONV_WIDTHS:
         raise ValueError(f"edge_conv: w1 must be [out, 2 * {c}] and out 64 or 128, got w1 {tuple(w1.shape)}, "
                          f"w2 {tuple(w2.shape)}")
+    _whole_graph("edge_conv", st)
     wa, wb = w1[:, :c], w1[:, c:]
     u = linear(x, (wa - wb).contiguous(), b1)
     v = linear(x, wb.contiguous(), None)
-    if _via_ops(st):
-        from . import torch_ops
-        out, arg = torch_ops.edge_conv(u, v, w2, b2, st)
-    else:
-        out, arg = _EdgeConvMax.apply(u, v, w2, b2, st)
+    from . import torch_ops
+    out, arg = torch_ops.edge_conv(u, v, w2, b2, st)      # the only route: pangnn::edge_conv (csrc/graph_ops.cpp)
     return (out, arg) if return_arg else out
 
 
@@ -934,118 +881,23 @@ def edge_score_supported(d: int) -> bool:
     return bool(_lib.load().pangnn_edge_score_supported(int(d)))
 
 
-def _score_fwd(z, st: EdgeStructure, mode: int, y=None, pw=None, denom=0):
-    """(logits, norms, loss, g_logits) of pangnn_edge_score[_loss]_mixed on rows as stored"""
-    lib = _lib.load()
-    e, n, d = st.num_edges, z.shape[0], z.shape[1]
-    dev = z.device
-    logits = torch.empty(e, dtype=torch.float32, device=dev)
-    norms = torch.empty(n if mode == 1 else 0, 2, dtype=torch.float32, device=dev)
-    nrm = norms.data_ptr() if mode == 1 else None
-    with _lib.device_guard(dev):
-        if y is None:
-            _lib.check(lib.pangnn_edge_score_mixed(z.data_ptr(), _dt(z), z.stride(0), n, st.edge_index.data_ptr(), e, e, d, mode,
-                                                   nrm, logits.data_ptr(), _lib.stream_ptr()), "pangnn_edge_score_mixed")
-            return logits, norms, None, None
-        loss = torch.empty(1, dtype=torch.float32, device=dev)
-        g_logits = torch.empty(e, dtype=torch.float32, device=dev)
-        parts = torch.empty(_SCORE_LOSS_PARTS, dtype=torch.float32, device=dev)
-        _lib.check(lib.pangnn_edge_score_loss_mixed(z.data_ptr(), _dt(z), z.stride(0), n, st.edge_index.data_ptr(), e, e, d, mode,
-                                                    y.data_ptr(), _lib.ptr(pw), int(denom), nrm, logits.data_ptr(),
-                                                    loss.data_ptr(), g_logits.data_ptr(), parts.data_ptr(), _lib.stream_ptr()),
-                   "pangnn_edge_score_loss_mixed")
-    return logits, norms, loss.view(()), g_logits
-
-
-_SCORE_LOSS_PARTS = 4096    # PANGNN_EDGE_SCORE_LOSS_PARTS
-
-
-def _score_bwd(z, st: EdgeStructure, mode: int, g, logits, norms, g_scale=None):
-    """dL/dz (fp32) of pangnn_edge_score_bwd_mixed: one wave per node over both CSR orders, hub rows as segments"""
-    lib = _lib.load()
-    n, d, e = z.shape[0], z.shape[1], st.num_edges
-    dev = z.device
-    gz = torch.empty(n, d, dtype=torch.float32, device=dev)
-    args, keep = [], []
-    for csr in (st.by_src, st.by_dst):
-        args += [csr.rowptr.data_ptr(), csr.other.data_ptr(), csr.perm.data_ptr()]
-        long = csr.long_rows()
-        if long is None:
-            args += [None, None, 0, None]
-        else:
-            seg_ptr, parts_rowptr = long
-            nseg = seg_ptr.shape[0] - 1
-            keep.append(torch.empty(nseg * (d + 1), dtype=torch.float32, device=dev))   # partial rows of the segments
-            args += [seg_ptr.data_ptr(), parts_rowptr.data_ptr(), nseg, keep[-1].data_ptr()]
-    with _lib.device_guard(dev):
-        _lib.check(lib.pangnn_edge_score_bwd_mixed(z.data_ptr(), _dt(z), z.stride(0), n, e, d, mode, *args, g.data_ptr(),
-                                                   _lib.ptr(logits if mode == 1 else None), _lib.ptr(norms if mode == 1 else None),
-                                                   _lib.ptr(g_scale), gz.data_ptr(), d, _lib.stream_ptr()),
-                   "pangnn_edge_score_bwd_mixed")
-    return gz
-
-
-class _EdgeScore(torch.autograd.Function):
-    """logits[e] = z[src_e] . z[dst_e] (mode 0) or cosine_similarity(z[src_e], z[dst_e]) (mode 1), rows gathered as stored;
-    backward: one node pass over both CSR orders (weightless decoders)"""
-
-    @staticmethod
-    def forward(ctx, z, st: EdgeStructure, mode):
-        _lib.require_device(z)
-        zr = _rows_any(z)
-        logits, norms, _, _ = _score_fwd(zr, st, mode)
-        ctx.st, ctx.mode, ctx.dtype = st, mode, z.dtype
-        ctx.save_for_backward(zr, logits, norms)
-        return logits
-
-    @staticmethod
-    def backward(ctx, g):
-        zr, logits, norms = ctx.saved_tensors
-        gz = _score_bwd(zr, ctx.st, ctx.mode, _f32c(g), logits, norms)
-        return gz.to(ctx.dtype), None, None
-
-
-class _EdgeScoreLoss(torch.autograd.Function):
-    """(mean BCEWithLogits(pos_weight) over `denom`, detached logits) of the weightless decoders in one edge pass; backward is
-    one node pass scaled by the upstream gradient, read on the device (no sync, no unit-gradient special case)"""
-
-    @staticmethod
-    def forward(ctx, z, st: EdgeStructure, mode, y, pos_weight, denom):
-        _lib.require_device(z, y, pos_weight)
-        zr = _rows_any(z)
-        pw = None if pos_weight is None else _f32c(pos_weight).reshape(-1)
-        logits, norms, loss, g_logits = _score_fwd(zr, st, mode, _f32c(y), pw, denom)
-        ctx.st, ctx.mode, ctx.dtype = st, mode, z.dtype
-        ctx.save_for_backward(zr, logits, norms, g_logits)
-        ctx.mark_non_differentiable(logits)
-        return loss, logits
-
-    @staticmethod
-    def backward(ctx, go, _go_logits):
-        zr, logits, norms, g_logits = ctx.saved_tensors
-        gz = _score_bwd(zr, ctx.st, ctx.mode, g_logits, logits, norms, _f32c(go).reshape(-1))
-        return gz.to(ctx.dtype), None, None, None, None, None
-
-
 def edge_score(z, st: EdgeStructure, mode: str):
     """per-edge logits of the `dot` / `cosine` decoder (fp32 [E]); dL/dz comes back in z's dtype"""
     m = SCORE_MODES[mode]
+    _whole_graph("edge_score", st)
     _lib.require_device(z)
-    if _via_ops(st):
-        from . import torch_ops
-        return torch_ops.edge_score(z, st, m)
-    return _EdgeScore.apply(z, st, m)
+    from . import torch_ops
+    return torch_ops.edge_score(z, st, m)                # the only route: pangnn::edge_score (csrc/graph_ops.cpp)
 
 
 def edge_score_loss(z, st: EdgeStructure, mode: str, y, pos_weight=None, denom=None):
     """(loss, detached logits) = (BCEWithLogitsLoss(pos_weight)(decoder(z), y) averaged over `denom` edges, logits)"""
     m = SCORE_MODES[mode]
+    _whole_graph("edge_score_loss", st)
     _lib.require_device(z, y, pos_weight)
     denom = st.num_edges if denom is None else denom
-    if _via_ops(st):
-        from . import torch_ops
-        return torch_ops.edge_score_loss(z, st, m, y, pos_weight, denom)
-    return _EdgeScoreLoss.apply(z, st, m, y, pos_weight, denom)
+    from . import torch_ops
+    return torch_ops.edge_score_loss(z, st, m, y, pos_weight, denom)     # the only route: pangnn::edge_score_loss
 
 
 @torch.compiler.assume_constant_result

@@ -14,8 +14,10 @@ The per-step operators of the train step that read a graph (gcn_propagate, embed
 decoder_loss, decoder_mlp, edge_score, edge_score_loss, edge_conv and their backward ops) are C++ too since round 5 (csrc/graph_ops.cpp: schema, HIP implementation,
 autograd formula, and the structure registry they look a graph up in by the identity of its `edge_index` tensor); the second
 half of this module holds their fake kernels, the registry's build-on-miss hook and the wrappers `functional` calls with this
-package's structure objects (`functional.USE_DISPATCHER_OPS`; PANGNN_DISPATCHER_OPS=auto: only when a tracer / dispatch mode
-observes the calls, =0: never — the ctypes autograd.Functions: same kernels, same results).
+package's structure objects.  edge_score, edge_score_loss and edge_conv have no other route, like linear and bce_with_logits;
+for propagate, the first-layer ops and the MLP decoder, which keep a ctypes autograd.Function twin (same kernels, same
+results), `functional.USE_DISPATCHER_OPS` chooses: PANGNN_DISPATCHER_OPS=auto: the ops only when a tracer / dispatch mode
+observes the calls, =0: never.
 There is no CPU implementation: the ops raise on CPU tensors.
 """
 from __future__ import annotations
@@ -26,11 +28,6 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROW_DTYPES = (torch.float32, torch.bfloat16, torch.float16)       # indexed by PANGNN_DTYPE_*
-
-
-def _code(dtype) -> int:
-    """PANGNN_DTYPE_* of a torch dtype (None: f32)"""
-    return 1 if dtype == torch.bfloat16 else 2 if dtype == torch.float16 else 0
 
 TLIB_PATH = os.environ.get("PANGNN_TORCH_LIB") or os.path.join(_HERE, "libpangnn_torch.so")   # override: the host-sanitizer build
 
@@ -271,9 +268,6 @@ def _(g, arg, u, v, w2, edge_index):
 
 
 # ---------------------------------------------------------------------------------------------- wrappers taking structures
-_N = _G
-
-
 def _ready(st, need, norm=None, x=None):
     """make `st` findable by identity (Python cache and native registry) with the tables `need` names; the weight tensor the
     op is keyed on.  A tensor-only stand-in (graph.TracedStructure, while torch.compile traces) passes through."""
@@ -287,47 +281,47 @@ def _ready(st, need, norm=None, x=None):
 
 def gcn_propagate(x, bias, st, norm, allow_band=False, out_dtype=None):
     band = bool(allow_band) and getattr(norm, "weight_ref", None) is None and x.dim() == 2 and x.shape[1] in (64, 128)
-    w = _ready(st, _N.NEED_BY_DST | _N.NEED_NORM | (_N.NEED_BAND if band else 0), norm)
-    return ops.gcn_propagate(x, bias, st._key_tensor, w, bool(allow_band), _code(out_dtype))
+    w = _ready(st, _G.NEED_BY_DST | _G.NEED_NORM | (_G.NEED_BAND if band else 0), norm)
+    return ops.gcn_propagate(x, bias, st._key_tensor, w, bool(allow_band), _PF.dtype_code(out_dtype))
 
 
 def embed_conv_in(x_tab, w, b, w_in, b_in, st, norm, out_dtype=None):
-    wt = _ready(st, _N.NEED_BY_DST | _N.NEED_NORM | _N.NEED_ACTIONS, norm, x_tab)
-    return ops.embed_conv_in(x_tab, w, b, w_in, b_in, st._key_tensor, wt, _code(out_dtype))
+    wt = _ready(st, _G.NEED_BY_DST | _G.NEED_NORM | _G.NEED_ACTIONS, norm, x_tab)
+    return ops.embed_conv_in(x_tab, w, b, w_in, b_in, st._key_tensor, wt, _PF.dtype_code(out_dtype))
 
 
 def embed_conv_in_linear(x_tab, w, b, w_in, b_in, w_out, bias_out, st, norm):
-    wt = _ready(st, _N.NEED_BY_DST | _N.NEED_NORM | _N.NEED_ACTIONS, norm, x_tab)
+    wt = _ready(st, _G.NEED_BY_DST | _G.NEED_NORM | _G.NEED_ACTIONS, norm, x_tab)
     return ops.embed_conv_in_linear(x_tab, w, b, w_in, b_in, w_out, bias_out, st._key_tensor, wt)
 
 
 def embed_propagate(x_tab, w, b, st, norm):
-    wt = _ready(st, _N.NEED_BY_DST | _N.NEED_NORM | _N.NEED_ACTIONS, norm, x_tab)
+    wt = _ready(st, _G.NEED_BY_DST | _G.NEED_NORM | _G.NEED_ACTIONS, norm, x_tab)
     return ops.embed_propagate(x_tab, w, b, st._key_tensor, wt)
 
 
 def decoder_loss_pq(pq, st, extra, cvec, w2, b2, w3, b3, y, pos_weight, denom, live=None):
-    _ready(st, _N.NEED_BY_DST | _N.NEED_RUNSUM | _N.NEED_PLAN_DST)
+    _ready(st, _G.NEED_BY_DST | _G.NEED_RUNSUM | _G.NEED_PLAN_DST)
     out = ops.decoder_loss(pq, st._key_tensor, extra, cvec, w2, b2, w3, b3, y, pos_weight, int(denom), live)
     return out[0], out[1]
 
 
 def decoder_mlp_pq(pq, st, extra, cvec, w2, b2, w3, b3):
-    _ready(st, _N.NEED_ENTRY)
+    _ready(st, _G.NEED_ENTRY)
     return ops.decoder_mlp(pq, st._key_tensor, extra, cvec, w2, b2, w3, b3)
 
 
 def edge_score(z, st, mode):
-    _ready(st, _N.NEED_BY_DST | _N.NEED_BY_SRC)          # the backward walks both CSR orders
+    _ready(st, _G.NEED_BY_DST | _G.NEED_BY_SRC)          # the backward walks both CSR orders
     return ops.edge_score(z, st._key_tensor, int(mode))[0]
 
 
 def edge_score_loss(z, st, mode, y, pos_weight, denom):
-    _ready(st, _N.NEED_BY_DST | _N.NEED_BY_SRC)
+    _ready(st, _G.NEED_BY_DST | _G.NEED_BY_SRC)
     out = ops.edge_score_loss(z, st._key_tensor, int(mode), y, pos_weight, int(denom))
     return out[0], out[1]
 
 
 def edge_conv(u, v, w2, b2, st):
-    _ready(st, _N.NEED_BY_DST | _N.NEED_BY_SRC)          # the backward walks both CSR orders
+    _ready(st, _G.NEED_BY_DST | _G.NEED_BY_SRC)          # the backward walks both CSR orders
     return ops.edge_conv(u, v, w2, b2, st._key_tensor)

@@ -90,6 +90,20 @@ def test_host_argument_checks_refuse_before_any_launch():
     assert b"pangnn_edge_score_bwd_mixed" in L.pangnn_last_error()
 
 
+def test_a_rectangular_structure_is_refused_on_the_host():
+    """edge_score / edge_score_loss go through ops that find a graph by (edge_index, target rows): a shard's structure with
+    other source rows raises before anything is launched"""
+    from pangnn_amd import functional as PF
+    from pangnn_amd.graph import EdgeStructure
+    st = EdgeStructure(torch.tensor([[0, 6, 3], [1, 2, 4]]), 5, num_src=7)
+    z = torch.randn(7, 16)
+    for mode in MODES:
+        with pytest.raises(ValueError, match="edge_score: "):
+            PF.edge_score(z, st, mode)
+        with pytest.raises(ValueError, match="edge_score_loss: "):
+            PF.edge_score_loss(z, st, mode, torch.zeros(3))
+
+
 # ---------------------------------------------------------------------------------------------- GPU: kernel level
 def _dev():
     return torch.device("cuda:0")
@@ -246,26 +260,66 @@ def test_two_byte_rows_are_bit_identical_to_f32_on_the_up_converted_rows(dtype, 
             assert z16.grad.dtype == dtype and torch.equal(z16.grad, z32.grad.to(dtype)), tag
 
 
+def _raw_kernels(z, st, mode, y=None, pw=None, g=None, g_scale=None):
+    """the C entry points on the structure's own tables: (logits, dL/dz) of pangnn_edge_score_mixed with the upstream gradient
+    `g`, or with `y` (loss, logits, dL/dz) of pangnn_edge_score_loss_mixed — dL/dz from pangnn_edge_score_bwd_mixed either way,
+    hub rows passed as the segments of CSR.long_rows"""
+    from pangnn_amd import _lib
+    L = _lib.load()
+    m = {"dot": 0, "cosine": 1}[mode]
+    n, d, e = z.shape[0], z.shape[1], st.num_edges
+    f = lambda *s: torch.empty(*s, dtype=torch.float32, device=z.device)                      # noqa: E731
+    logits, norms, loss, gz = f(e), f(n if m else 0, 2), f(1), f(n, d)
+    nrm = norms.data_ptr() if m else None
+    head = (z.data_ptr(), 0, z.stride(0), n, st.edge_index.data_ptr(), e, e, d, m)
+    with _lib.device_guard(z.device):
+        if y is None:
+            _lib.check(L.pangnn_edge_score_mixed(*head, nrm, logits.data_ptr(), _lib.stream_ptr()), "pangnn_edge_score_mixed")
+        else:
+            g, parts = f(e), f(4096)                                                          # PANGNN_EDGE_SCORE_LOSS_PARTS
+            _lib.check(L.pangnn_edge_score_loss_mixed(*head, y.data_ptr(), pw.data_ptr(), e, nrm, logits.data_ptr(),
+                                                      loss.data_ptr(), g.data_ptr(), parts.data_ptr(), _lib.stream_ptr()),
+                       "pangnn_edge_score_loss_mixed")
+        orders, keep = [], []
+        for csr in (st.by_src, st.by_dst):
+            orders += [csr.rowptr.data_ptr(), csr.other.data_ptr(), csr.perm.data_ptr()]
+            long = csr.long_rows()
+            if long is None:
+                orders += [None, None, 0, None]
+            else:
+                nseg = long[0].shape[0] - 1
+                keep.append(f(nseg * (d + 1)))                                                # partial rows of the segments
+                orders += [long[0].data_ptr(), long[1].data_ptr(), nseg, keep[-1].data_ptr()]
+        _lib.check(L.pangnn_edge_score_bwd_mixed(z.data_ptr(), 0, z.stride(0), n, e, d, m, *orders, g.data_ptr(),
+                                                 logits.data_ptr() if m else None, nrm, _lib.ptr(g_scale), gz.data_ptr(), d,
+                                                 _lib.stream_ptr()), "pangnn_edge_score_bwd_mixed")
+    return (logits, gz) if y is None else (loss.view(()), logits, gz)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("mode", MODES)
-def test_dispatcher_route_is_bit_identical_to_ctypes_route(mode, monkeypatch):
+def test_registered_ops_return_exactly_what_the_kernels_return(mode):
+    """functional.edge_score / edge_score_loss have one route, the registered ops: their results and gradients are, bit for
+    bit, those of the C entry points called here with the structure's tables"""
     from pangnn_amd import functional as PF
     tag, n, ei = _graph_cases()[-1]                          # the star: hub rows as segments
     eid = ei.to(_dev())
+    st = _st(eid, n)
+    assert st.by_dst.long_rows() is not None or st.by_src.long_rows() is not None
     z = _scaled_rows(n, 64, seed=9)
     y = (torch.rand(ei.shape[1]) < 0.4).float().to(_dev())
     pw = torch.tensor(1.7, device=_dev())
-    res = []
-    for use in (False, True):
-        monkeypatch.setattr(PF, "USE_DISPATCHER_OPS", use)
-        za = z.to(_dev()).requires_grad_(True)
-        out = PF.edge_score(za, _st(eid, n), mode)
-        out.backward(torch.linspace(-1, 1, ei.shape[1], device=_dev()))
-        zb = z.to(_dev()).requires_grad_(True)
-        loss, logits = PF.edge_score_loss(zb, _st(eid, n), mode, y, pw, ei.shape[1])
-        loss.backward()
-        res.append((out.detach(), za.grad, loss.detach(), logits, zb.grad))
-    for a, b in zip(*res):
+    g = torch.linspace(-1, 1, ei.shape[1], device=_dev())
+    za = z.to(_dev()).requires_grad_(True)
+    out = PF.edge_score(za, st, mode)
+    out.backward(g)
+    zb = z.to(_dev()).requires_grad_(True)
+    loss, logits = PF.edge_score_loss(zb, st, mode, y, pw, ei.shape[1])
+    loss.backward()
+    zr = z.to(_dev())
+    one = torch.ones(1, device=_dev())                       # loss.backward(): the upstream gradient the op hands the kernel
+    raw = _raw_kernels(zr, st, mode, g=g) + _raw_kernels(zr, st, mode, y=y, pw=pw.reshape(1), g_scale=one)
+    for a, b in zip((out.detach(), za.grad, loss.detach(), logits, zb.grad), raw):
         assert torch.equal(a, b)
 
 

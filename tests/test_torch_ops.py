@@ -197,6 +197,13 @@ def test_dispatcher_propagate_equals_ctypes_path_and_oracle():
     assert torch.equal(rp, st.by_dst.rowptr) and torch.equal(ot, st.by_dst.other) and torch.equal(pm, st.by_dst.perm)
     dis, ns, no = torch.ops.pangnn.gcn_norm(rp, ot, pm, w.to(dev))
     assert torch.equal(ns, norm.by_dst) and torch.equal(no, norm.orig)
+    # an operator without a ctypes twin (edge_score) takes its registered op whatever the switch says
+    default = PF.edge_score(x0.to(dev), st, "cosine")
+    old, PF.USE_DISPATCHER_OPS = PF.USE_DISPATCHER_OPS, False
+    try:
+        assert torch.equal(PF.edge_score(x0.to(dev), st, "cosine"), default)
+    finally:
+        PF.USE_DISPATCHER_OPS = old
 
 
 @pytest.mark.gpu
