@@ -672,6 +672,40 @@ int    pangnn_edge_conv_bwd_f32(const float* g, int64_t ldg, const int32_t* arg,
                                 const int64_t* edge_index, int64_t ld, int64_t num_edges, float* gu, float* gv,
                                 int64_t ldgrad, float* gw2, void* scratch, int64_t scratch_bytes, pangnn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * A structure derived by filtering (csrc/edge_filter.hip): the sub-sampled graph of sub_sample_graph_edges (src/helper.py:
+ * 16-68, pangnn.py:190) — edge list, per-edge arrays and CSR orders of the kept edges — from the PARENT's tables, by
+ * order-preserving compaction instead of a sort.  Edge e is kept when keep[e] != 0; `keep` is read at its stored width,
+ * keep_itemsize = 1 (one byte per edge) or 4 (one 32-bit word per edge).
+ * Inputs: the parent's edge_index[2][ld] and its by-target CSR of pangnn_csr_build(group_by = 1) (rowptr [num_nodes + 1],
+ * other, perm); optionally its by-source CSR (group_by = 0) — three pointers, all set or all NULL; up to two per-edge f32
+ * arrays attr0 / attr1 (nullable, each with its output).  `num_kept` is the number of kept edges as the HOST knows it: every
+ * output is sized by it.
+ * Outputs: child_edge_index[2][child_ld] = the kept edges in the caller's order, child_attr0 / child_attr1 [num_kept],
+ * kept_id [num_kept] int32 = the parent edge id of every child edge (ascending), and for each CSR order given the child's
+ * rowptr [num_nodes + 1] / other / perm [num_kept], entry for entry what pangnn_csr_build makes of child_edge_index (the sort
+ * and the compaction are both stable).  count[0] = the number of kept edges as counted on the device; status[0] = 0, or bit 0:
+ * count != num_kept, bit 1: a parent perm entry outside [0, num_edges) (the entry counts as dropped) or a parent rowptr entry
+ * outside [0, num_edges] (clamped).  With a wrong num_kept nothing is written outside the num_kept entries of an output:
+ * surplus edges are dropped, a missing tail is zero-filled and belongs to no row.
+ * num_edges == 0, num_kept == 0 (per-edge outputs may then be NULL) and num_kept == num_edges write every output.
+ * Integer scans (rocPRIM) and plain stores: bitwise reproducible.  num_edges or num_nodes >= 2^31: PANGNN_E_TOOLARGE.
+ * `workspace`: pangnn_structure_filter_workspace_bytes(num_edges) bytes, 16-byte aligned (0 from the query: failure — it
+ * asks rocPRIM for the scans' temporary size, which needs a device); smaller: PANGNN_E_WORKSPACE.
+ * ---------------------------------------------------------------------------------------- */
+int64_t pangnn_structure_filter_workspace_bytes(int64_t num_edges);
+int    pangnn_structure_filter(const int64_t* edge_index, int64_t ld, int64_t num_edges, int64_t num_nodes,
+                               const void* keep, int keep_itemsize, int64_t num_kept,
+                               const int64_t* rowptr_dst, const int32_t* other_dst, const int32_t* perm_dst,
+                               const int64_t* rowptr_src, const int32_t* other_src, const int32_t* perm_src,
+                               const float* attr0, const float* attr1,
+                               int64_t* child_edge_index, int64_t child_ld, int32_t* kept_id,
+                               float* child_attr0, float* child_attr1,
+                               int64_t* child_rowptr_dst, int32_t* child_other_dst, int32_t* child_perm_dst,
+                               int64_t* child_rowptr_src, int32_t* child_other_src, int32_t* child_perm_src,
+                               int32_t* count, int32_t* status, void* workspace, int64_t workspace_bytes,
+                               pangnn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,7 +14,8 @@ from .deferred import BCEWithLogitsLoss, DeferredLogits        # noqa: E402
 from .gnn import AlternateGCN                                 # noqa: E402
 from .graph import EdgeStructure, structure_of                # noqa: E402
 from .predict import predict_homolog_genes                    # noqa: E402
+from .sampling import filter_edges, sub_sample_graph_edges     # noqa: E402
 
 __all__ = ["AlternateGCN", "GCNConv", "MessagePassing", "EdgeConv", "Data", "Batch", "DataLoader",
            "EdgeStructure", "structure_of", "BCEWithLogitsLoss", "DeferredLogits",
-           "predict_homolog_genes"]
+           "predict_homolog_genes", "filter_edges", "sub_sample_graph_edges"]

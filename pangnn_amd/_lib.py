@@ -133,6 +133,13 @@ SIGNATURES = {
     # edge_index, ld, num_edges, gu, gv, ldgrad, gw2, scratch, scratch_bytes, stream)
     "pangnn_edge_conv_bwd_f32": (C.c_int, [_p, _i64, _p, _p, _i64, _p, _i64, _i64, _p, _i32, _p, _p, _p, _p, _p, _p,
                                            _p, _i64, _i64, _p, _p, _i64, _p, _p, _i64, _p]),
+    # a structure derived by filtering (csrc/edge_filter.hip): (edge_index, ld, num_edges, num_nodes, keep, keep_itemsize,
+    # num_kept, parent by-target rowptr / other / perm, parent by-source rowptr / other / perm, attr0, attr1, child
+    # edge_index, child ld, kept_id, child attr0 / attr1, child by-target rowptr / other / perm, child by-source rowptr /
+    # other / perm, count, status, workspace, bytes, stream)
+    "pangnn_structure_filter_workspace_bytes": (_i64, [_i64]),
+    "pangnn_structure_filter": (C.c_int, [_p, _i64, _i64, _i64, _p, C.c_int, _i64, _p, _p, _p, _p, _p, _p, _p, _p,
+                                          _p, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _p]),
 }
 
 ABI_VERSION = 3          # PANGNN_ABI_VERSION of include/pangnn_hip.h this binding was written against

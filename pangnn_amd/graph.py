@@ -128,7 +128,8 @@ class EdgeStructure:
         `hints` (optional; set by producers that KNOW them, e.g. SubGraphDataset.batch): {"valid_ids": True} — every id
         is inside [0, num_nodes), skip the range check and its host read-back; {"sorted_by_src": bool} — whether the
         list is source-sorted, skip that test's host read-back; {"band_width": k} — whether the list is the whole-graph
-        positional-neighbour pattern (0: it is not), skip that comparison's host read-back.  With all of them a structure
+        positional-neighbour pattern (0: it is not), skip that comparison's host read-back; {"short_rows": bool} — whether
+        no row exceeds LONG_ROW (default: what "valid_ids" says), skip the longest row's host read-back.  With all of them a structure
         is built without any device -> host synchronisation (a fresh mini-batch per step, pangnn.py:152-216)."""
         self.hints = dict(hints or {})
         self._key_tensor = edge_index        # the caches are keyed on THIS tensor's address: keep it alive
@@ -143,6 +144,102 @@ class EdgeStructure:
         self._band: Optional[int] = None
         self._small_built = False
         self._native = 0                     # NEED_* bits already pushed to the native registry (push_native)
+
+    @classmethod
+    def filtered(cls, parent: "EdgeStructure", keep: torch.Tensor, num_kept: Optional[int] = None, arrays=()):
+        """The structure of the kept edges of `parent` (keep[e] != 0), DERIVED from the parent's tables by an
+        order-preserving compaction instead of two sorts (pangnn_structure_filter, csrc/edge_filter.hip): a fresh
+        sub-sample of a whole graph per step (sampling.sub_sample_graph_edges, pangnn.py:190).
+        Returns (child, kept_id int32 [E'], [compacted array for each of `arrays`]): child.edge_index holds the kept edges
+        in the caller's order, kept_id the parent edge id of every child edge, `arrays` are up to two per-edge fp32
+        tensors ([E], e.g. edge_attr and y) compacted alongside.  The child gets the by-target CSR always and the
+        by-source CSR if the parent holds it (a missing order is built lazily, as ever) — the tables build_csr would make
+        of child.edge_index, entry for entry — and the hints the parent vouches for: valid ids, the parent's
+        sorted-by-source answer (a subsequence of a sorted list is sorted), no band, short rows where the parent's are
+        (a CSR order of the parent with hub rows leaves the child's to decide for itself: one read-back on first use).
+        `keep`: [E] bool / uint8 / int8 / int32 are read as stored, any other dtype through one `!= 0` pass.
+        `num_kept`: the number of kept edges where the caller knows it: nothing is then read back, and
+        child.filter_state (int32 [2]: the device's count, a status word that is non-zero when the count differs) says
+        whether it was right — `child.check_filter()` reads it.  Without it the count costs one device -> host read.
+        Square structures only: a partitioned shard's rectangular structure raises ValueError."""
+        if parent.num_src != parent.num_nodes:
+            raise ValueError("EdgeStructure.filtered needs a square structure (a whole graph or a collated batch), not a "
+                             "partitioned shard's")
+        lib = _lib.load()
+        ei, e, n = parent.edge_index, parent.num_edges, parent.num_nodes
+        _lib.require_device(ei, keep, *arrays)
+        keep = keep.detach().reshape(-1)
+        if keep.numel() != e:
+            raise ValueError(f"{keep.numel()} keep entries for {e} edges")
+        if keep.dtype not in (torch.bool, torch.uint8, torch.int8, torch.int32):
+            keep = keep != 0
+        keep = keep.contiguous()
+        if len(arrays) > 2:
+            raise ValueError("at most two per-edge arrays are compacted alongside")
+        for a in arrays:
+            if a.dtype != torch.float32 or a.dim() != 1 or a.shape[0] != e or not a.is_contiguous():
+                raise ValueError(f"a per-edge array must be contiguous float32 [{e}], got {a.dtype} {tuple(a.shape)}")
+        known = num_kept is not None
+        kept = int(num_kept) if known else int(torch.count_nonzero(keep))           # the one read-back
+        if not 0 <= kept <= e:
+            raise ValueError(f"num_kept = {kept} of {e} edges")
+        dev = ei.device
+        d = parent.by_dst
+        s = parent._by_src
+        c_ei = torch.empty((2, kept), dtype=torch.int64, device=dev)
+        kept_id = torch.empty(kept, dtype=torch.int32, device=dev)
+        outs = [torch.empty(kept, dtype=torch.float32, device=dev) for _ in arrays]
+        orders = 2 if s is not None else 1
+        ka, na = -(-kept // 4) * 4, -(-(n + 1) // 2) * 2                            # 16-byte aligned segments
+        i32 = torch.empty(2 * orders * ka + 4, dtype=torch.int32, device=dev)
+        i64 = torch.empty(orders * na, dtype=torch.int64, device=dev)
+        tabs = [CSR(i64[o * na:o * na + n + 1], i32[2 * o * ka:2 * o * ka + kept], i32[(2 * o + 1) * ka:(2 * o + 1) * ka + kept])
+                for o in range(orders)]
+        state = i32[2 * orders * ka:2 * orders * ka + 2]
+        a_in, a_out = list(arrays) + [None, None], outs + [None, None]
+        with _lib.device_guard(dev):
+            ws_bytes = lib.pangnn_structure_filter_workspace_bytes(e)
+            if ws_bytes == 0:
+                raise _lib.PangnnHipError("pangnn_structure_filter_workspace_bytes failed")
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            c_d, c_s = tabs[0], (tabs[1] if orders == 2 else None)
+            _lib.check(lib.pangnn_structure_filter(
+                _lib.ptr(ei) if e else None, e, e, n, _lib.ptr(keep) if e else None, keep.element_size(), kept,
+                d.rowptr.data_ptr(), _lib.ptr(d.other) if e else None, _lib.ptr(d.perm) if e else None,
+                None if s is None else s.rowptr.data_ptr(), None if s is None else s.other.data_ptr(),
+                None if s is None else s.perm.data_ptr(), _lib.ptr(a_in[0]), _lib.ptr(a_in[1]),
+                c_ei.data_ptr() if kept else None, kept, kept_id.data_ptr() if kept else None,
+                _lib.ptr(a_out[0]), _lib.ptr(a_out[1]),
+                c_d.rowptr.data_ptr(), c_d.other.data_ptr() if kept else None, c_d.perm.data_ptr() if kept else None,
+                None if c_s is None else c_s.rowptr.data_ptr(),
+                c_s.other.data_ptr() if (c_s is not None and kept) else None,
+                c_s.perm.data_ptr() if (c_s is not None and kept) else None,
+                state.data_ptr(), state[1:].data_ptr(), ws.data_ptr(), ws_bytes, _lib.stream_ptr()),
+                "pangnn_structure_filter")
+        # what the parent knows holds for every subsequence of its list: sortedness, and rows no longer than LONG_ROW (both
+        # decided once per PARENT — a read-back each the first time — so that a child per step costs none)
+        short = [c.long_rows(parent._small_built or parent._vouched_short()) is None for c in (d, s) if c is not None]
+        hints = {"valid_ids": True, "band_width": 0, "short_rows": len(short) == 2 and all(short)}
+        if e:
+            hints["sorted_by_src"] = parent.sorted_by_src()
+        child = cls(c_ei, n, hints=hints)
+        child._by_dst, child._by_src = tabs[0], (tabs[1] if orders == 2 else None)
+        for c, is_short in zip(tabs, short):
+            if is_short:
+                c.__dict__["_long"] = False
+        child.filter_state, child._filter_claim = state, (kept if known else None)
+        return child, kept_id, outs
+
+    def check_filter(self):
+        """for a structure made by `filtered(..., num_kept=k)`: raise ValueError unless the mask had exactly k entries set
+        (one device -> host read; the tables of a structure that fails this are not to be used)"""
+        if getattr(self, "_filter_claim", None) is not None:
+            count, status = self.filter_state.tolist()
+            if status & 1:
+                raise ValueError(f"keep has {count} entries set, num_kept said {self._filter_claim}")
+            if status:
+                raise ValueError("the parent structure's tables are inconsistent")
+        return self
 
     def _small_build(self) -> bool:
         """A small square structure (a mini-batch of sub-graphs): both CSR orders and the S / T kernels' chunk plans of both
@@ -196,7 +293,7 @@ class EdgeStructure:
                                      num_rows=self.num_nodes)
             if self.num_nodes < nmax and self.num_edges and int(self.edge_index[1].max()) >= self.num_nodes:
                 raise ValueError("target id outside the local row range")
-            if self.hints.get("valid_ids", False):       # a producer-vouched list (a collated batch): built without any
+            if self._vouched_short():                    # a producer-vouched list (a collated batch): built without any
                 self._by_dst.__dict__["_long"] = False   # read-back, so no read-back of the longest row either
         return self._by_dst
 
@@ -207,9 +304,26 @@ class EdgeStructure:
         if self._by_src is None:
             nmax = max(self.num_nodes, self.num_src)
             self._by_src = build_csr(self.edge_index, nmax, 0, validate=False, num_rows=self.num_src)
-            if self.hints.get("valid_ids", False):
+            if self._vouched_short():
                 self._by_src.__dict__["_long"] = False
         return self._by_src
+
+    def _vouched_short(self) -> bool:
+        """the producer vouches that no row exceeds LONG_ROW: {"short_rows": bool} where it says so (a filtered structure
+        inherits what its parent knows), else whatever vouches for the ids (a collated batch of small sub-graphs)"""
+        return bool(self.hints.get("short_rows", self.hints.get("valid_ids", False)))
+
+    def sorted_by_src(self) -> bool:
+        """the caller's edge order is sorted by source (decided once: the producer's hint, or one host read-back)"""
+        if self._runsum is None:
+            src, e = self.edge_index[0], self.num_edges
+            if e == 0:
+                self._runsum = False
+            elif "sorted_by_src" in self.hints:
+                self._runsum = {} if self.hints["sorted_by_src"] else False
+            else:
+                self._runsum = {} if bool((src[1:] >= src[:-1]).all()) else False
+        return self._runsum is not False
 
     def band_width(self) -> int:
         """k > 0 if this edge list IS the positional-neighbour graph of a whole genome set as the reference builds it
@@ -276,15 +390,7 @@ class EdgeStructure:
         training kernels can emit (include/pangnn_hip.h, `part_buf` / `part_off`), else None.
           part_off[c]    index of chunk c's first part
           part_rowptr[s] parts of source s are [part_rowptr[s], part_rowptr[s+1])   (consecutive: sorted)"""
-        if self._runsum is None:
-            src, e = self.edge_index[0], self.num_edges
-            if e == 0:
-                self._runsum = False
-            elif "sorted_by_src" in self.hints:
-                self._runsum = {} if self.hints["sorted_by_src"] else False
-            else:
-                self._runsum = {} if bool((src[1:] >= src[:-1]).all()) else False
-        if self._runsum is False:
+        if not self.sorted_by_src():
             return None
         ct = int(chunk_tiles)
         if ct not in self._runsum:
@@ -326,7 +432,7 @@ class EdgeStructure:
         todo = need & _STRUCT_BITS & ~have
         if todo or not (have & NEED_ENTRY):
             by_dst, by_src, band, srt, plan = [], [], -1, -1, None
-            short = self._small_built or bool(self.hints.get("valid_ids", False))
+            short = self._small_built or self._vouched_short()
             if todo & NEED_BY_DST:
                 c = self.by_dst
                 by_dst = [c.rowptr, c.other, c.perm] + list(c.long_rows(short) or ())
