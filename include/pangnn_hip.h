@@ -706,6 +706,42 @@ int    pangnn_structure_filter(const int64_t* edge_index, int64_t ld, int64_t nu
                                int32_t* count, int32_t* status, void* workspace, int64_t workspace_bytes,
                                pangnn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The decoder's run-sum plan of a CSR order from its row pointer (csrc/csr_plan.hip): the tables that
+ * EdgeStructure._plan_of_sorted_keys (pangnn_amd/graph.py, the written definition) makes of the sorted keys, entry for entry,
+ * without the keys: `part_buf` / `part_off` of the training decoder above, `part_rowptr` of its part sums.
+ * Input: rowptr [n_rows + 1] int64, non-decreasing, rowptr[0] == 0, rowptr[n_rows] == num_edges (a rectangular structure's
+ * trimmed row pointer is fine); num_edges >= 1, n_rows >= 1; span = 32 * chunk_tiles (anything else: PANGNN_E_BADARG).
+ * With c[r] = (rowptr[r + 1] > rowptr[r] && rowptr[r] % span != 0), Cin / Cex its inclusive / exclusive prefix sums:
+ *   keys [num_edges] int32          the row of every sorted entry
+ *   part_off [ceil(E / span)] int32 part_off[ch] = ch + Cin[row of entry ch * span]
+ *   part_rowptr [n_rows + 1] int64  rowptr[r] / span + Cex[r] + (rowptr[r] % span != 0) while rowptr[r] < E, else last + 1
+ *   last [1] int64                  the last part id, (E - 1) / span + sum(c)
+ * A rowptr that breaks the contract yields unspecified tables, but no access outside the arrays as sized above.
+ * One integer scan over the rows (rocPRIM) and one launch with plain stores: bitwise reproducible, nothing read back.
+ * num_edges or n_rows >= 2^31: PANGNN_E_TOOLARGE.  `workspace`: pangnn_csr_plan_workspace_bytes(n_rows) bytes, 16-byte
+ * aligned (0 from the query: failure — it asks rocPRIM for the scan's temporary size, which needs a device); smaller:
+ * PANGNN_E_WORKSPACE.
+ * ---------------------------------------------------------------------------------------- */
+int64_t pangnn_csr_plan_workspace_bytes(int64_t n_rows);
+int    pangnn_csr_plan(const int64_t* rowptr, int64_t n_rows, int64_t num_edges, int32_t span, int32_t* keys,
+                       int32_t* part_off, int64_t* part_rowptr, int64_t* last, void* workspace, int64_t workspace_bytes,
+                       pangnn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The mask of the k smallest keys (csrc/mask_select.hip): keep[i] = 0 for exactly the k entries that come first in
+ * (key, index) order — among equal keys the lower index loses — and 1 for the others.  keys [n] int64 with
+ * 0 <= key < 2^63, 16-byte aligned, only read (preserved); keep [n] one byte each, 4-byte aligned; 0 <= k <= n is the
+ * host's number (k > n: PANGNN_E_BADARG).  k == 0 writes all ones, k == n all zeros, n == 0 nothing.
+ * A radix select over histograms (integer atomics only) and one mask pass; ranks among keys tied with the k-th smallest
+ * come from fixed index ranges, never from an arrival order: the mask is a function of (keys, k).  Nothing is read back.
+ * n >= 2^31: PANGNN_E_TOOLARGE.  `workspace`: pangnn_mask_k_smallest_workspace_bytes(n) bytes (a few KB, 0: n out of
+ * range), 16-byte aligned; smaller: PANGNN_E_WORKSPACE.
+ * ---------------------------------------------------------------------------------------- */
+int64_t pangnn_mask_k_smallest_workspace_bytes(int64_t n);
+int    pangnn_mask_k_smallest_i64(const int64_t* keys, int64_t n, int64_t k, uint8_t* keep, void* workspace,
+                                  int64_t workspace_bytes, pangnn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -140,6 +140,13 @@ SIGNATURES = {
     "pangnn_structure_filter_workspace_bytes": (_i64, [_i64]),
     "pangnn_structure_filter": (C.c_int, [_p, _i64, _i64, _i64, _p, C.c_int, _i64, _p, _p, _p, _p, _p, _p, _p, _p,
                                           _p, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _p]),
+    # the decoder's run-sum plan from a row pointer (csrc/csr_plan.hip): (rowptr, n_rows, num_edges, span, keys, part_off,
+    # part_rowptr, last, workspace, bytes, stream)
+    "pangnn_csr_plan_workspace_bytes": (_i64, [_i64]),
+    "pangnn_csr_plan": (C.c_int, [_p, _i64, _i64, _i32, _p, _p, _p, _p, _p, _i64, _p]),
+    # the mask of the k smallest keys (csrc/mask_select.hip): (keys, n, k, keep, workspace, bytes, stream)
+    "pangnn_mask_k_smallest_workspace_bytes": (_i64, [_i64]),
+    "pangnn_mask_k_smallest_i64": (C.c_int, [_p, _i64, _i64, _p, _p, _i64, _p]),
 }
 
 ABI_VERSION = 3          # PANGNN_ABI_VERSION of include/pangnn_hip.h this binding was written against

@@ -22,6 +22,10 @@ from . import _lib
 # mini-batch sized square structures are built by one launch (EdgeStructure._small_build); False: always the general
 # radix-sort build + index-op plans (what the parity tests compare the small build with)
 SMALL_STRUCTURE = os.environ.get("PANGNN_SMALL_STRUCTURE", "1") != "0"
+# the decoder's run-sum plans of a structure that takes the general build come from its row pointers in one scan + one launch
+# (pangnn_csr_plan, EdgeStructure._plan_of_rowptr); False: the index-op route (_plan_of_sorted_keys: the definition the
+# kernel is tested against), for A/B
+PLAN_KERNEL = os.environ.get("PANGNN_PLAN_KERNEL", "1") != "0"
 
 
 # components of a structure as the native registry (csrc/graph_ops.cpp) names them: bits of `push_native(need)` and of
@@ -373,16 +377,52 @@ class EdgeStructure:
         plan.n_parts_exact = lambda: int(plan._last) + 1
         return plan
 
+    @staticmethod
+    def _plan_of_rowptr(rowptr: torch.Tensor, num_edges: int, chunk_tiles: int = 1):
+        """The plan `_plan_of_sorted_keys` makes of a CSR order's keys, from that order's row pointer alone (device tensors;
+        pangnn_csr_plan, csrc/csr_plan.hip): the keys are non-decreasing, so the key changes sit at rowptr[r] of the
+        non-empty rows — one scan over the rows and one write of `keys`, no pass over a key array.  Same fields, dtypes and
+        shapes, entry for entry (tests/test_csr_plan.py)."""
+        from types import SimpleNamespace
+        lib = _lib.load()
+        e, n_rows, ct = int(num_edges), rowptr.shape[0] - 1, int(chunk_tiles)
+        span = 32 * ct
+        nc = (e + span - 1) // span
+        dev = rowptr.device
+        rowptr = rowptr if rowptr.is_contiguous() else rowptr.contiguous()
+        keys = torch.empty(e, dtype=torch.int32, device=dev)
+        part_off = torch.empty(nc, dtype=torch.int32, device=dev)
+        i64 = torch.empty(n_rows + 2, dtype=torch.int64, device=dev)
+        part_rowptr, last = i64[:n_rows + 1], i64[n_rows + 1:]
+        with _lib.device_guard(dev):
+            ws_bytes = lib.pangnn_csr_plan_workspace_bytes(n_rows)
+            if ws_bytes == 0:
+                raise _lib.PangnnHipError("pangnn_csr_plan_workspace_bytes failed")
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            _lib.check(lib.pangnn_csr_plan(rowptr.data_ptr(), n_rows, e, span, keys.data_ptr(), part_off.data_ptr(),
+                                           part_rowptr.data_ptr(), last.data_ptr(), ws.data_ptr(), ws_bytes,
+                                           _lib.stream_ptr()), "pangnn_csr_plan")
+        plan = SimpleNamespace(n_parts=nc + min(n_rows, e), part_off=part_off, part_rowptr=part_rowptr, keys=keys,
+                               chunk_tiles=ct, _last=last)
+        plan.n_parts_exact = lambda: int(plan._last) + 1
+        return plan
+
     def csr_plan(self, by: str, chunk_tiles: int = 1):
         """run-sum plan of the CSR order `by` in {"dst", "src"} (pangnn_decoder_dgrad_f32: perm = that CSR's perm)"""
         cache = self.__dict__.setdefault("_csr_plans", {})
         key = (by, int(chunk_tiles))
         if key not in cache:
             csr = self.by_dst if by == "dst" else self.by_src
+            if key in cache:                             # (the small build, just triggered, made the plans too)
+                return cache[key]
             n_rows = self.num_nodes if by == "dst" else self.num_src
-            keys = self.edge_index[1 if by == "dst" else 0][csr.perm.long()] if self.num_edges else \
-                self.edge_index.new_empty(0)
-            cache[key] = self._plan_of_sorted_keys(keys, n_rows, chunk_tiles) if self.num_edges else None
+            if not self.num_edges:
+                cache[key] = None
+            elif PLAN_KERNEL and csr.rowptr.is_cuda:
+                cache[key] = self._plan_of_rowptr(csr.rowptr, self.num_edges, chunk_tiles)
+            else:
+                keys = self.edge_index[1 if by == "dst" else 0][csr.perm.long()]
+                cache[key] = self._plan_of_sorted_keys(keys, n_rows, chunk_tiles)
         return cache[key]
 
     def runsum_plan(self, chunk_tiles: int = 1):
@@ -398,8 +438,19 @@ class EdgeStructure:
             # order is this plan
             self._small_build()              # no-op unless applicable and nothing is built yet
             small = self.__dict__.get("_csr_plans", {}).get(("src", ct)) if self._small_built else None
-            self._runsum[ct] = small if small is not None else \
-                self._plan_of_sorted_keys(self.edge_index[0], self.num_src, ct)
+            if small is not None:
+                self._runsum[ct] = small
+            elif PLAN_KERNEL and self.edge_index.is_cuda:
+                # the list is its own by-source order: that order's row pointer where it is held (a filtered child always
+                # holds it), else the first entry of every source by one N-sized search of the sorted sources — no sort
+                if self._by_src is not None:
+                    rowptr = self._by_src.rowptr
+                else:
+                    src = self.edge_index[0]
+                    rowptr = torch.searchsorted(src, torch.arange(self.num_src + 1, device=src.device, dtype=src.dtype))
+                self._runsum[ct] = self._plan_of_rowptr(rowptr, self.num_edges, ct)
+            else:
+                self._runsum[ct] = self._plan_of_sorted_keys(self.edge_index[0], self.num_src, ct)
         return self._runsum[ct]
 
     def native_has(self, need: int, norm=None, x=None) -> bool:

@@ -31,13 +31,18 @@ garbage-collected, so `batch = sub_sample_graph_edges(...)` in a loop does not a
 """
 from __future__ import annotations
 
+import os
 import weakref
 from typing import Optional
 
 import torch
 
+from . import _lib
 from . import graph as _G
 from .data import Data
+
+# the device draw marks the k smallest keys with a selection kernel (mask_k_smallest); False: torch.topk, for A/B
+MASK_KERNEL = os.environ.get("PANGNN_MASK_KERNEL", "1") != "0"
 
 
 def _num_nodes(graph) -> int:
@@ -148,17 +153,42 @@ def _negatives(graph, y: torch.Tensor) -> int:
     return hit[1]
 
 
+def mask_k_smallest(keys: torch.Tensor, k: int) -> torch.Tensor:
+    """keep bool [n] for device keys int64 [n], 0 <= key < 2^63: False for exactly the k entries that come first in
+    (key, index) order, True elsewhere (pangnn_mask_k_smallest_i64, csrc/mask_select.hip: a radix select, no sort, nothing
+    read back; `keys` is only read).  With distinct keys: the complement of torch.topk(keys, k, largest=False)."""
+    _lib.require_device(keys)
+    if keys.dtype != torch.int64 or keys.dim() != 1:
+        raise ValueError(f"keys must be int64 [n], got {keys.dtype} {tuple(keys.shape)}")
+    n, k = keys.shape[0], int(k)
+    if not 0 <= k <= n:
+        raise ValueError(f"k = {k} of {n} keys")
+    keys = keys if keys.is_contiguous() and keys.data_ptr() % 16 == 0 else keys.clone(memory_format=torch.contiguous_format)
+    lib = _lib.load()
+    keep = torch.empty(n, dtype=torch.uint8, device=keys.device)
+    if n:
+        with _lib.device_guard(keys.device):
+            ws_bytes = lib.pangnn_mask_k_smallest_workspace_bytes(n)
+            if ws_bytes == 0:
+                raise _lib.PangnnHipError("pangnn_mask_k_smallest_workspace_bytes failed")
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=keys.device)
+            _lib.check(lib.pangnn_mask_k_smallest_i64(keys.data_ptr(), n, k, keep.data_ptr(), ws.data_ptr(), ws_bytes,
+                                                      _lib.stream_ptr()), "pangnn_mask_k_smallest_i64")
+    return keep.view(torch.bool)
+
+
 def draw_keep_mask(graph, fraction: float = 0.8, sample_pos_edges: bool = False, generator=None):
     """(keep bool [E], E') of sub_sample_graph_edges: exactly int(E * (1 - fraction)) entries False, drawn uniformly without
-    replacement from the negatives (or from all edges) on the graph's device.  Plain torch: one 62-bit random key per
-    edge, a positive's key replaced by a larger constant, the k smallest keys lose (ties between keys are 2^-62 events, so
-    the subset is a function of the seed; nothing of size E is kept between calls)."""
+    replacement from the negatives (or from all edges) on the graph's device.  One 62-bit random key per edge, a
+    positive's key replaced by a larger constant, the k smallest keys lose (ties between keys are 2^-62 events, so the
+    subset is a function of the seed; nothing of size E is kept between calls).  On the device the k smallest are marked
+    by a selection kernel (mask_k_smallest; MASK_KERNEL = False: torch.topk and an indexed store, the same mask); CPU
+    tensors take the torch route."""
     ei = _check_graph(graph)
     e, dev = ei.shape[1], ei.device
     if not 0.0 <= fraction <= 1.0:
         raise ValueError(f"fraction = {fraction}")
     k = int(e * (1 - fraction))
-    keep = torch.ones(e, dtype=torch.bool, device=dev)
     y = None
     if not sample_pos_edges:
         y = getattr(graph, "y", None)
@@ -170,11 +200,15 @@ def draw_keep_mask(graph, fraction: float = 0.8, sample_pos_edges: bool = False,
                              f"positive — lower the positive share, lower `fraction`, or pass sample_pos_edges=True")
         if pool < k:
             raise ValueError(f"{k} edges to remove but only {pool} negatives")
-    if k > 0:
-        keys = torch.empty(e, dtype=torch.int64, device=dev).random_(0, 1 << 62, generator=generator)
-        if y is not None:
-            keys.masked_fill_(y.reshape(-1) != 0, 1 << 62)    # k <= the number of negatives: never among the k smallest
-        keep[torch.topk(keys, k, largest=False, sorted=False).indices] = False
+    if k == 0:
+        return torch.ones(e, dtype=torch.bool, device=dev), e
+    keys = torch.empty(e, dtype=torch.int64, device=dev).random_(0, 1 << 62, generator=generator)
+    if y is not None:
+        keys.masked_fill_(y.reshape(-1) != 0, 1 << 62)        # k <= the number of negatives: never among the k smallest
+    if MASK_KERNEL and keys.is_cuda:
+        return mask_k_smallest(keys, k), e - k
+    keep = torch.ones(e, dtype=torch.bool, device=dev)
+    keep[torch.topk(keys, k, largest=False, sorted=False).indices] = False
     return keep, e - k
 
 

@@ -1,0 +1,165 @@
+"""pangnn_csr_plan (csrc/csr_plan.hip): the decoder's run-sum plan from a row pointer, against the written definition
+EdgeStructure._plan_of_sorted_keys on the expanded keys, and through EdgeStructure.csr_plan / runsum_plan against the
+torch route (graph.PLAN_KERNEL off).  Every comparison is exact: same dtypes, torch.equal."""
+import pytest
+import torch
+
+import pangnn_amd
+from conftest import load_golden, random_graph
+from pangnn_amd import _lib, graph as G, sub_sample_graph_edges
+from pangnn_amd.data import Data
+from pangnn_amd.graph import EdgeStructure
+from pangnn_amd.sampling import release
+from pangnn_amd.train import make_optimizer, train_step
+from test_plan_mask_host import edge_counts, keys_of, layouts
+
+pytestmark = pytest.mark.gpu
+DEV = torch.device("cuda")
+LAYOUTS = ["hub_alone", "hub_among_empty_rows", "one_entry_per_row", "rows_on_chunk_boundaries", "empty_front_back_middle",
+           "heavy_tailed"]
+
+
+def plans_equal(got, want, what=""):
+    for f in ("keys", "part_off", "part_rowptr", "_last"):
+        a, b = getattr(got, f), getattr(want, f)
+        assert a.dtype == b.dtype and a.shape == b.shape and torch.equal(a, b), (what, f)
+    assert got.n_parts == want.n_parts and got.chunk_tiles == want.chunk_tiles, what
+    assert got.n_parts_exact() == want.n_parts_exact() <= got.n_parts, what
+
+
+def tiles_for(e, which):
+    return {"one": 1, "sixteen": 16, "for_e": int(_lib.load().pangnn_decoder_chunk_tiles_for(e))}[which]
+
+
+def sizes(which):
+    """(E, chunk_tiles): E in {1, span - 1, span, span + 1, 2 span, 3 span + 7, 70001} of the span that goes with it"""
+    if which != "for_e":
+        return [(e, tiles_for(e, which)) for e in edge_counts(32 * tiles_for(0, which))]
+    # the chunk size is a function of E here: every E that stands in one of those relations to its OWN span
+    every = sorted({e for span in range(32, 1024 + 1, 32) for e in edge_counts(span)})
+    return [(e, tiles_for(e, which)) for e in every if e in edge_counts(32 * tiles_for(e, which))]
+
+
+@pytest.mark.parametrize("name", LAYOUTS)
+@pytest.mark.parametrize("which", ["one", "for_e", "sixteen"])
+def test_the_plan_of_a_rowptr_is_the_plan_of_its_keys(which, name):
+    cases = sizes(which)
+    assert {1, 70001} <= {e for e, _ in cases} and len(cases) >= 7
+    for e, ct in cases:
+        rowptr = layouts(e, 32 * ct)[name].to(DEV)
+        n_rows = rowptr.numel() - 1
+        want = EdgeStructure._plan_of_sorted_keys(keys_of(rowptr), n_rows, ct)
+        got = EdgeStructure._plan_of_rowptr(rowptr, e, ct)
+        plans_equal(got, want, (name, e, ct))
+        again = EdgeStructure._plan_of_rowptr(rowptr, e, ct)                  # two calls: bit-identical tables
+        plans_equal(again, got, (name, e, ct, "again"))
+
+
+def _golden(name="cfg2_sim_1000x5"):
+    f = load_golden(name)
+    return Data(x=torch.from_numpy(f["whole_x"]).to(DEV), edge_index=torch.from_numpy(f["whole_edge_index"]).to(DEV),
+                edge_attr=torch.from_numpy(f["whole_edge_attr"]).to(DEV), y=torch.from_numpy(f["whole_y"]).to(DEV),
+                neighbour_edge_index=torch.from_numpy(f["whole_neighbour_edge_index"]).to(DEV))
+
+
+def _edge_lists():
+    ei, _ = random_graph(900, 9000, seed=3)
+    by_src = ei[:, torch.sort(ei[0], stable=True).indices].contiguous()
+    g = _golden()
+    return {"random": (ei, 900), "random_sorted_by_source": (by_src, 900), "golden": (g.edge_index.cpu(), g.x.shape[0])}
+
+
+@pytest.mark.parametrize("small", [False, True])
+@pytest.mark.parametrize("case", ["random", "random_sorted_by_source", "golden"])
+def test_structures_get_the_plans_of_the_torch_route(case, small, monkeypatch):
+    ei, n = _edge_lists()[case]
+    monkeypatch.setattr(G, "SMALL_STRUCTURE", small)
+    e = ei.shape[1]
+    for ct in sorted({1, 16, tiles_for(e, "for_e")}):
+        for hold_src in (False, True):
+            sts = []
+            for kernel in (True, False):
+                monkeypatch.setattr(G, "PLAN_KERNEL", kernel)
+                st = EdgeStructure(ei.to(DEV), n)
+                if hold_src:
+                    st.by_src
+                sts.append((st, st.runsum_plan(ct), st.csr_plan("dst", ct), st.csr_plan("src", ct)))
+            (a, ra, da, sa), (b, rb, db, sb) = sts
+            srt = bool((ei[0, 1:] >= ei[0, :-1]).all())
+            assert srt == (case == "random_sorted_by_source") or case == "golden"
+            assert (ra is None) == (rb is None) == (not srt)
+            if ra is not None:
+                plans_equal(ra, rb, (case, ct, "runsum"))
+                plans_equal(ra, sa, (case, ct, "a source-sorted list is its own by-source order"))
+            plans_equal(da, db, (case, ct, "dst"))
+            plans_equal(sa, sb, (case, ct, "src"))
+
+
+def test_runsum_plan_of_a_sorted_list_sorts_nothing(monkeypatch):
+    ei, n = _edge_lists()["random_sorted_by_source"]
+    monkeypatch.setattr(G, "SMALL_STRUCTURE", False)
+
+    def no_sort(*a, **k):
+        raise AssertionError("runsum_plan built a CSR order")
+
+    monkeypatch.setattr(G, "build_csr", no_sort)
+    st = EdgeStructure(ei.to(DEV), n)
+    plan = st.runsum_plan(16)
+    assert st._by_src is None and st._by_dst is None
+    plans_equal(plan, EdgeStructure._plan_of_sorted_keys(st.edge_index[0], n, 16))
+    empty = EdgeStructure(torch.zeros(2, 0, dtype=torch.int64, device=DEV), 5)
+    assert empty.runsum_plan(16) is None
+
+
+def test_an_empty_structure_has_no_plan():
+    empty = EdgeStructure(torch.zeros(2, 0, dtype=torch.int64, device=DEV), 5)
+    assert empty.csr_plan("dst", 16) is None and empty.csr_plan("src", 1) is None
+
+
+def test_a_rectangular_structure(monkeypatch):
+    """a destination-partitioned shard: local target ids, global source ids (num_src > num_nodes)"""
+    gen = torch.Generator().manual_seed(5)
+    n_dst, n_src, e = 300, 1100, 5000
+    src = torch.sort(torch.randint(0, n_src - 40, (e,), generator=gen)).values        # (the last sources have no edge)
+    dst = torch.randint(0, n_dst, (e,), generator=gen)
+    ei = torch.stack([src, dst]).to(DEV)
+    for ct in (1, 16):
+        sts = []
+        for kernel in (True, False):
+            monkeypatch.setattr(G, "PLAN_KERNEL", kernel)
+            st = EdgeStructure(ei, n_dst, num_src=n_src)
+            sts.append((st.csr_plan("dst", ct), st.csr_plan("src", ct), st.runsum_plan(ct)))
+        for got, want, by in zip(sts[0], sts[1], ("dst", "src", "runsum")):
+            plans_equal(got, want, (by, ct))
+        assert sts[0][0].part_rowptr.shape[0] == n_dst + 1 and sts[0][1].part_rowptr.shape[0] == n_src + 1
+
+
+def _sub_sampled_step(skip, kernel, monkeypatch):
+    G.clear_cache()
+    monkeypatch.setattr(G, "PLAN_KERNEL", kernel)
+    g = _golden()
+    torch.manual_seed(0)
+    model = pangnn_amd.AlternateGCN(DEV, None, False, dims=[64, 128], skip_connections=skip, decoder="mlp")
+    opt = make_optimizer(model)
+    pw = ((g.y == 0).sum() / g.y.sum()).float()
+    batch = sub_sample_graph_edges(g, DEV, fraction=0.8, generator=torch.Generator(device=DEV).manual_seed(17))
+    loss, logits = train_step(model, opt, batch, batch.y, pw)
+    out = loss.clone(), logits.clone(), [p.detach().clone() for p in model.parameters()]
+    release(batch)
+    return out
+
+
+@pytest.mark.parametrize("skip", [False, True])
+def test_a_sub_sampled_step_needs_no_index_op_plan(skip, monkeypatch):
+    monkeypatch.setattr(G, "SMALL_STRUCTURE", False)              # the general route: the plans are built on first use
+    want = _sub_sampled_step(skip, False, monkeypatch)
+
+    def refuse(*a, **k):
+        raise AssertionError("the step took the index-op plan route")
+
+    monkeypatch.setattr(EdgeStructure, "_plan_of_sorted_keys", staticmethod(refuse))
+    got = _sub_sampled_step(skip, True, monkeypatch)
+    assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
+    assert len(got[2]) == len(want[2]) > 0
+    for a, b in zip(got[2], want[2]):
+        assert torch.equal(a, b)

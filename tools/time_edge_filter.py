@@ -5,7 +5,9 @@ One process, device events on the stream, the two routes alternated call by call
       pangnn_structure_filter (EdgeStructure.filtered, num_kept known: no read-back);
   (b) what the same tables cost before: build_csr (stable radix sort) for both orders on the compacted edge_index, without
       the validity read-back — the compaction of the edge list itself (torch boolean indexing) is timed apart as (b');
-  (c) drawing the exact-count mask (sampling.draw_keep_mask: plain torch);
+  (c) drawing the exact-count mask (sampling.draw_keep_mask) with the selection kernel and with torch.topk;
+  (e) what a fresh structure costs its first step, part by part: the GCN normalisation, the first layer's node vectors and
+      the decoder's run-sum plan of each order, the plans with graph.PLAN_KERNEL on and off;
   (d) a full train_step on a fresh sub-sample per step (draw + derive + step + release) against the unsampled step on the
       parent graph — the sampled route on a graph object that is only ever sub-sampled — and the sampled step in parts: the sub-sample call, the step on the fresh structure, the same step again.
 
@@ -100,7 +102,15 @@ def main():
     child_ei = child.edge_index
     del child, kept_id, outs, d, s, ref
 
-    ta, tb, tbc, tc = [], [], [], []
+    def draw(kernel):
+        sampling.MASK_KERNEL = kernel
+        try:
+            return sampling.draw_keep_mask(g, a.fraction, generator=gen)
+        finally:
+            sampling.MASK_KERNEL = mask_default
+
+    mask_default = sampling.MASK_KERNEL
+    ta, tb, tbc, tc, tct = [], [], [], [], []
     for it in range(a.warmup + a.steps):
         ms_a, out = _event_ms(route_a)
         del out
@@ -108,10 +118,12 @@ def main():
         del out
         ms_bc, out = _event_ms(compaction)
         del out
-        ms_c, out = _event_ms(lambda: sampling.draw_keep_mask(g, a.fraction, generator=gen))
+        ms_c, out = _event_ms(lambda: draw(True))
+        del out
+        ms_ct, out = _event_ms(lambda: draw(False))
         del out
         if it >= a.warmup:
-            ta.append(ms_a), tb.append(ms_b), tbc.append(ms_bc), tc.append(ms_c)
+            ta.append(ms_a), tb.append(ms_b), tbc.append(ms_bc), tc.append(ms_c), tct.append(ms_ct)
     # (a): per order  perm 4 + keep gather 1 + pos write 4 | pos 8 + perm 4 + other 4 + (new_id gather 4 + 8 written) per kept;
     # edge list  keep 1 + new_id write 4 | new_id 8 + (16 + 8 read, 16 + 8 + 4 written) per kept;  rowptr 16 per node
     bytes_a = 2 * (e * (4 + 1 + 4 + 8 + 4 + 4) + kept * 12 + n * 16) + e * (1 + 4 + 8) + kept * 52
@@ -120,9 +132,71 @@ def main():
               achieved_TBps=bytes_a / sa["ms"] / 1e9, bound_ms_at_8TBps=bytes_a / HBM_BPS * 1e3))
     emit(dict(what="b_build_csr_both_orders", **sb))
     emit(dict(what="b_prime_torch_compaction_of_edge_list", **_stats(tbc)))
-    emit(dict(what="c_draw_mask", **_stats(tc)))
+    sc, sct = _stats(tc), _stats(tct)
+    emit(dict(what="c_draw_mask", route="selection kernel (pangnn_mask_k_smallest_i64)", **sc, default=bool(mask_default)))
+    emit(dict(what="c_draw_mask_torch_topk", route="torch.topk + indexed store", **sct, default=not mask_default,
+              topk_over_kernel=sct["ms"] / sc["ms"]))
     emit(dict(what="ratio", b_over_a=sb["ms"] / sa["ms"], a_over_b=sa["ms"] / sb["ms"]))
     del child_ei
+
+    # (e) what a fresh structure costs its first step, part by part, on one derived child: the GCN normalisation of the new
+    # weights, the first layer's node vectors r / s, and the decoder's run-sum plan of each order — the plans by the kernel
+    # (graph.PLAN_KERNEL, pangnn_csr_plan) and by the index-op route, alternated call by call; every cache the part fills is
+    # emptied before the call
+    def first_step_parts():
+        from pangnn_amd import _lib, functional, graph as G
+        child, kept_id, outs = route_a()
+        ct = int(_lib.load().pangnn_decoder_chunk_tiles_for(child.num_edges))
+        w = outs[0]
+
+        def norm_fresh():
+            child._norm.clear()
+            return child.gcn_norm(w)
+
+        def plan_fresh(which, kernel):
+            G.PLAN_KERNEL = kernel
+            child.__dict__["_csr_plans"] = {}
+            if child._runsum is not None and child._runsum is not False:
+                child._runsum.clear()
+            try:
+                return child.runsum_plan(ct) if which == "runsum" else child.csr_plan(which, ct)
+            finally:
+                G.PLAN_KERNEL = plan_default
+
+        plan_default = G.PLAN_KERNEL
+        whichs = ("dst", "src") + (("runsum",) if child.sorted_by_src() else ())
+        t_norm, t_act = [], []
+        t_plan = {(wh, k): [] for wh in whichs for k in (True, False)}
+        same_plans = True
+        for wh in whichs:                    # the same tables?  (before any timing)
+            pa, pb = plan_fresh(wh, True), plan_fresh(wh, False)
+            same_plans &= all(torch.equal(getattr(pa, f), getattr(pb, f)) and getattr(pa, f).dtype == getattr(pb, f).dtype
+                              for f in ("keys", "part_off", "part_rowptr", "_last")) and pa.n_parts == pb.n_parts
+        emit(dict(what="agreement_plans", chunk_tiles=ct, orders=list(whichs), plans_equal=bool(same_plans)))
+        if not same_plans:
+            raise SystemExit("the kernel's plans differ from the index-op route's")
+        del pa, pb
+        for it in range(a.warmup + a.steps):
+            ms_n, norm = _event_ms(norm_fresh)
+            ms_r, out = _event_ms(lambda: functional._node_actions(g.x, child, norm))
+            del out, norm
+            ms_p = {}
+            for key in t_plan:
+                ms_p[key], out = _event_ms(lambda: plan_fresh(*key))
+                del out
+            if it >= a.warmup:
+                t_norm.append(ms_n), t_act.append(ms_r)
+                for key in t_plan:
+                    t_plan[key].append(ms_p[key])
+        emit(dict(what="e_first_step_gcn_norm", **_stats(t_norm)))
+        emit(dict(what="e_first_step_node_actions", **_stats(t_act)))
+        for wh in whichs:
+            sk, st_ = _stats(t_plan[(wh, True)]), _stats(t_plan[(wh, False)])
+            emit(dict(what=f"e_first_step_plan_{wh}", route="pangnn_csr_plan", **sk, default=bool(plan_default)))
+            emit(dict(what=f"e_first_step_plan_{wh}_index_ops", route="_plan_of_sorted_keys", **st_, default=not plan_default,
+                      index_ops_over_kernel=st_["ms"] / sk["ms"]))
+        child._norm.clear()
+        del child, kept_id, outs, w
 
     if not a.no_step:
         torch.manual_seed(0)
@@ -170,6 +244,8 @@ def main():
         emit(dict(what="d_train_step_whole_graph", **_stats(tw)))
         emit(dict(what="d_train_step_fresh_sub_sample", **_stats(ts), edges=kept,
                   max_memory_allocated_GB=torch.cuda.max_memory_allocated() / 1e9))
+    torch.cuda.empty_cache()          # (d)'s cached blocks: (e) starts from a clean allocator, as (a)-(c) did
+    first_step_parts()
     if a.out:
         with open(a.out, "a") as fh:
             fh.write("\n".join(json.dumps(x) for x in lines) + "\n")
