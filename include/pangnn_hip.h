@@ -300,7 +300,9 @@ int pangnn_decoder_mlp_loss_f32(const float* p, int64_t ldp, const float* q, int
  *   what lets two waves share a SIMD without spilling),
  *   rec[E][8] uint32 (required): per edge {4 dwords of relu masks — the h2 mask in the low byte of each half, the h1
  *             mask in the high byte —, dL/dlogit_e replicated into dwords 4 .. 7} for the dgrad pass, whose lane group g
- *             reads mask dword g and dL/dlogit through one address (offsets 0 and 16),
+ *             reads mask dword g and dL/dlogit through one address (offsets 0 and 16).  The value is the one given (or, with
+ *             the fused loss, computed as for a real edge) also where the edge is padding (live_edges): S leaves such an edge
+ *             out of its own sums, its record is not zeroed — T masks by position in its order,
  *   part_buf / part_off (both NULL or both set; edge list sorted by source): sums of dL/dh1 over every
  *   (chunk, source) run, where a chunk is pangnn_decoder_chunk_tiles_for(num_edges) (16 for E >= 1e6, down to 1 for short lists) consecutive 32-edge tiles walked by
  *   one wave with the open run carried from tile to tile: part_off[c] = index of chunk c's first part row, a new
@@ -323,9 +325,11 @@ int pangnn_decoder_mlp_loss_f32(const float* p, int64_t ldp, const float* q, int
  *   pangnn_decoder_dgrad_workspace_bytes().
  * live_edges (both entry points; nullable, DEVICE int64[1]): the list is a fixed-shape batch whose first *live_edges edges
  *   are real and whose tail is padding (a mini-batch collated by pangnn_collate_subgraphs_padded so that one captured
- *   HIP graph serves every batch): in S the padded edges keep their own logit / record slots but get dL/dlogit = 0 and
- *   the fused loss is the mean over *live_edges edges (`denom` is ignored); in T the positions >= *live_edges of the
- *   order are the padding (the pads must sort last: their endpoints are the largest node id).  NULL: every edge is real.
+ *   HIP graph serves every batch): in S the padded edges keep their own logit / record slots but enter every sum with
+ *   dL/dlogit = 0 (the record itself keeps the unmasked value, see `rec`) and the fused loss is the mean over *live_edges
+ *   edges (`denom` is ignored); in T the positions >= *live_edges of the order are the padding and contribute 0 whatever
+ *   their records hold (the pads must sort last: their endpoints are the largest node id).  A value above num_edges counts
+ *   as num_edges.  NULL: every edge is real.
  * Both are reproducible (fixed-order sums, no float atomics).
  * ---------------------------------------------------------------------------------------- */
 int    pangnn_decoder_chunk_tiles(void);
