@@ -29,6 +29,8 @@ extern "C" {
  * by pangnn_amd/_lib.py and by libpangnn_torch.so when it resolves this ABI. */
 /* 3 (round 5, later): PANGNN_DTYPE_F16 accepted by the node-level *_dtype arguments, pangnn_spmm_csr_f16 added; the 128 x 128
  * weight gradient is covered (pangnn_linear_supported(128, 128, 1) = 1). */
+/* 3, extended: pangnn_linear_act_backward_parts_f32 added.  No entry point changed its signature or meaning, so the number
+ * stays; the binding resolves every symbol at load, which refuses an older library of the same number. */
 #define PANGNN_ABI_VERSION 3
 
 #define PANGNN_E_BADARG    (-1)  /* null pointer / negative size / unsupported feature width */
@@ -422,6 +424,21 @@ int    pangnn_linear_act_wgrad_mixed(const void* g, int32_t g_dtype, int64_t ldg
 int    pangnn_linear_dgrad_mixed(const void* g, int32_t g_dtype, int64_t ldg, const float* w, void* gx, int32_t gx_dtype,
                                  int64_t ldgx, int64_t n, int32_t K, int32_t M, const void* gate, int32_t gate_dtype,
                                  int64_t ldgate, pangnn_stream_t stream);
+/* Backward of the decoder's P | Q layer y = act(x) . w^T + b (K = 64, M = 128) straight from the run parts the S and T
+ * kernels leave behind — the [n, 128] gradient dL/dP | dL/dQ is never written:
+ *   G[r][0:64)   = sum of parts_s[rowptr_s[r] .. rowptr_s[r+1]),  G[r][64:128) = the same over parts_t
+ *   gx [n][64] = (G . w) * ELU'(x) (in_act = 1; G . w for 0),  gw [128][64] = G^T . act(x),  gb [128] = column sums of G.
+ * One launch (+ the slab reduction) in place of two pangnn_spmm_csr_f32 part sums, pangnn_linear_dgrad_mixed and
+ * pangnn_linear_act_wgrad_mixed, and equal to that sequence bit for bit: same row sums in part order, same products, same
+ * tile-to-wave assignment and slab order.  parts_* [n_parts_*, 64] contiguous f32, rowptr_* int64 [n + 1] absolute part
+ * positions; x [n, 64] f32 is the layer's input (pre-activation when in_act = 1); workspace as
+ * pangnn_linear_wgrad_workspace_bytes(64, 128), its size passed as int64_t like every other size of this call.  Part positions
+ * outside [0, n_parts) are skipped, not read. */
+int    pangnn_linear_act_backward_parts_f32(const float* parts_s, const int64_t* rowptr_s, int64_t n_parts_s,
+                                            const float* parts_t, const int64_t* rowptr_t, int64_t n_parts_t,
+                                            const float* x, int64_t ldx, const float* w, int64_t n, int32_t K, int32_t M,
+                                            int32_t in_act, float* gx, int64_t ldgx, float* gw, float* gb,
+                                            void* workspace, int64_t workspace_bytes, pangnn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Confusion counts of thresholded link predictions, accumulated on the device:

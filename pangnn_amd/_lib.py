@@ -63,6 +63,9 @@ SIGNATURES = {
     # (g, g_dtype, ldg, x, x_dtype, ldx, n, K, M, in_act, gw, gb, workspace, bytes, stream)
     "pangnn_linear_act_wgrad_mixed": (C.c_int, [_p, _i32, _i64, _p, _i32, _i64, _i64, _i32, _i32, _i32, _p, _p, _p, _sz,
                                                 _p]),
+    # (parts_s, rowptr_s, n_parts_s, parts_t, rowptr_t, n_parts_t, x, ldx, w, n, K, M, in_act, gx, ldgx, gw, gb, workspace, bytes, stream)
+    "pangnn_linear_act_backward_parts_f32": (C.c_int, [_p, _p, _i64, _p, _p, _i64, _p, _i64, _p, _i64, _i32, _i32, _i32, _p, _i64,
+                                                       _p, _p, _p, _i64, _p]),
     "pangnn_confusion_update_f32": (C.c_int, [_p, _p, _i64, C.c_float, C.c_int, _p, _p]),
     "pangnn_weighted_colsum_workspace_bytes": (_sz, [_i32]),
     "pangnn_weighted_colsum_f32": (C.c_int, [_p, _i64, _p, _p, _i64, _i32, _p, _p, _sz, _p]),

@@ -1,5 +1,5 @@
 // The per-step operators that READ A GRAPH, in C++ end to end (round 5):
-//   gcn_propagate, embed_conv_in, embed_conv_in_linear, embed_propagate, decoder_loss, decoder_mlp, edge_score, edge_score_loss,
+//   gcn_propagate, embed_conv_in, embed_conv_in_linear, embed_propagate, decoder_loss, decoder_loss_z, decoder_mlp, edge_score, edge_score_loss,
 //   edge_conv
 //   and their backward ops
 // — schema, HIP ("CUDA" key) implementation and autograd formula (torch::autograd::Function under the Autograd key), like
@@ -638,8 +638,9 @@ void sum_parts(const Plan& plan, const at::Tensor& parts, int64_t n_rows, at::Te
 }
 
 // dL/dh1 summed over the rows of one CSR order from the per-edge records (T kernel + part sum); `g_b2`: also dL/db2
+// `keep_parts`: the part rows are handed out instead of being summed into `out` (pangnn_linear_act_backward_parts_f32 sums them)
 void dgrad_sum(const at::Tensor& rec, const View& v, int by /* 1 dst, 2 src, 0 none */, const DecIn& in, int64_t n_rows,
-               at::Tensor* out, at::Tensor* g_b2, const c10::optional<at::Tensor>& live) {
+               at::Tensor* out, at::Tensor* g_b2, const c10::optional<at::Tensor>& live, at::Tensor* keep_parts = nullptr) {
   const Plan* plan = by == 1 ? &v.plan_dst : by == 2 ? &v.plan_src : nullptr;
   const Csr* csr = by == 1 ? &v.by_dst : by == 2 ? &v.by_src : nullptr;
   at::Tensor parts, ws;
@@ -656,16 +657,36 @@ void dgrad_sum(const at::Tensor& rec, const View& v, int by /* 1 dst, 2 src, 0 n
                                     g_b2 ? g_b2->data_ptr<float>() : nullptr, opt_ptr<int64_t>(live), g_b2 ? ws.data_ptr() : nullptr,
                                     wsb, stream_of(rec)),
            "pangnn_decoder_dgrad_f32");
-  if (plan) sum_parts(*plan, parts, n_rows, *out);
+  if (plan && keep_parts) *keep_parts = parts;
+  else if (plan) sum_parts(*plan, parts, n_rows, *out);
 }
 
-struct DecGrads { at::Tensor loss, logits, g_pq, g_cv, g_w2, g_b2, g_w3, g_b3; };
+struct DecGrads { at::Tensor loss, logits, g_pq, g_cv, g_w2, g_b2, g_w3, g_b3, g_z, g_wpq, g_bpq; };
+
+// the dense layer in front of the decoder, pq = act(z) w_pq^T + b_pq: given to decoder_train, the gradients of z, w_pq and
+// b_pq come back instead of g_pq
+struct PqLayer { at::Tensor z, w; int64_t in_act = 0; };
+
+// backward of that layer from g_pq [n, 128]: pangnn::linear_backward's two calls
+void pq_layer_backward(const PqLayer& L, const at::Tensor& g_pq, DecGrads& r) {
+  const int64_t n = L.z.size(0);
+  check_rc(pangnn_linear_dgrad_mixed(g_pq.data_ptr(), PANGNN_DTYPE_F32, g_pq.stride(0), L.w.data_ptr<float>(), r.g_z.data_ptr(),
+                                     PANGNN_DTYPE_F32, r.g_z.stride(0), n, 64, 128, L.in_act ? L.z.data_ptr() : nullptr,
+                                     PANGNN_DTYPE_F32, L.in_act ? L.z.stride(0) : 0, stream_of(g_pq)),
+           "pangnn_linear_dgrad_mixed");
+  const size_t wsb = pangnn_linear_wgrad_workspace_bytes(64, 128);
+  auto ws = bytes(wsb, L.w);
+  check_rc(pangnn_linear_act_wgrad_mixed(g_pq.data_ptr(), PANGNN_DTYPE_F32, g_pq.stride(0), L.z.data_ptr(), PANGNN_DTYPE_F32,
+                                         L.z.stride(0), n, 64, 128, (int32_t)L.in_act, r.g_wpq.data_ptr<float>(),
+                                         r.g_bpq.data_ptr<float>(), ws.data_ptr(), wsb, stream_of(g_pq)),
+           "pangnn_linear_act_wgrad_mixed");
+}
 
 // the one-pass training decoder on the P | Q table: S (logits, loss or the given dL/dlogits, parameter gradients, by-source
 // run sums, records) then T (by-target sums, dL/db2); no [E, 64] tensor exists
 DecGrads decoder_train(const char* op, const DecIn& in, const at::Tensor& edge_index, const c10::optional<at::Tensor>& y,
                        const c10::optional<at::Tensor>& pos_weight, int64_t denom, const c10::optional<at::Tensor>& g_logits,
-                       const c10::optional<at::Tensor>& live) {
+                       const c10::optional<at::Tensor>& live, const PqLayer* layer = nullptr) {
   const int64_t n = in.pq.size(0), d = in.d;
   View v = lookup(op, edge_index, n, c10::nullopt, c10::nullopt, kByDst | kRunsum | kPlanDst);
   const int64_t e = v.num_edges;
@@ -702,6 +723,31 @@ DecGrads decoder_train(const char* op, const DecIn& in, const at::Tensor& edge_i
                                       defined(in.cv) ? r.g_cv.data_ptr<float>() : nullptr, opt_ptr<int64_t>(live), ws.data_ptr(), wsb,
                                       stream_of(in.pq)),
            "pangnn_decoder_train_mixed");
+  if (layer) {
+    r.g_z = at::empty({n, d}, fo);
+    r.g_wpq = at::empty({2 * d, d}, fo);
+    r.g_bpq = at::empty({2 * d}, fo);
+    if (e == 0) {
+      r.g_z.zero_(); r.g_wpq.zero_(); r.g_bpq.zero_(); r.g_b2.zero_();
+      return r;
+    }
+    if (runs && !defined(live)) {
+      // neither part sum is launched and no [n, 128] gradient exists: one kernel sums the S and T parts of a 32-row tile in
+      // LDS and takes both products of the layer's backward on it
+      at::Tensor parts_t;
+      dgrad_sum(rec, v, 1, in, n, nullptr, &r.g_b2, live, &parts_t);
+      const size_t lwb = pangnn_linear_wgrad_workspace_bytes(64, 128);
+      auto lws = bytes(lwb, in.w2);
+      check_rc(pangnn_linear_act_backward_parts_f32(parts.data_ptr<float>(), v.runsum.part_rowptr.data_ptr<int64_t>(), parts.size(0),
+                                                    parts_t.data_ptr<float>(), v.plan_dst.part_rowptr.data_ptr<int64_t>(),
+                                                    parts_t.size(0), layer->z.data_ptr<float>(), layer->z.stride(0),
+                                                    layer->w.data_ptr<float>(), n, 64, 128, (int32_t)layer->in_act,
+                                                    r.g_z.data_ptr<float>(), r.g_z.stride(0), r.g_wpq.data_ptr<float>(),
+                                                    r.g_bpq.data_ptr<float>(), lws.data_ptr(), (int64_t)lwb, stream_of(in.pq)),
+               "pangnn_linear_act_backward_parts_f32");
+      return r;
+    }
+  }
   r.g_pq = at::empty({n, 2 * d}, fo);
   at::Tensor gp = r.g_pq.narrow(1, 0, d), gq = r.g_pq.narrow(1, d, d);
   if (e == 0) {
@@ -713,6 +759,10 @@ DecGrads decoder_train(const char* op, const DecIn& in, const at::Tensor& edge_i
   if (runs) sum_parts(v.runsum, parts, n, gp);
   else { dgrad_sum(rec, v, 2, in, n, &gp, b2_pending, live); b2_pending = nullptr; }
   dgrad_sum(rec, v, 1, in, n, &gq, b2_pending, live);
+  if (layer) {                                    // an unsorted list: the layer's backward from the summed gradient
+    pq_layer_backward(*layer, r.g_pq, r);
+    r.g_pq = at::Tensor();
+  }
   return r;
 }
 
@@ -729,6 +779,43 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tenso
   const DeviceGuard guard(pq.device());
   DecGrads r = decoder_train("decoder_loss", in, edge_index, y, pos_weight, denom, c10::nullopt, live);
   return {r.loss.view(at::IntArrayRef{}), r.logits, r.g_pq, r.g_cv, r.g_w2.view_as(w2), r.g_b2, r.g_w3.view_as(w3), r.g_b3.view_as(b3)};
+}
+
+// decoder_loss with the P | Q layer in front of it: pq = act(z) w_pq^T + b_pq (pangnn::linear's kernel), S and T as above, and
+// the layer's backward straight from the run parts.  -> (loss, logits, g_z, g_wpq, g_bpq, g_cv, g_w2, g_b2, g_w3, g_b3), all
+// bit-equal to linear -> decoder_loss -> linear_backward.
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor>
+decoder_loss_z(const at::Tensor& z, const at::Tensor& w_pq, const at::Tensor& b_pq, int64_t in_act, const at::Tensor& edge_index,
+               const c10::optional<at::Tensor>& extra, const c10::optional<at::Tensor>& cvec, const at::Tensor& w2,
+               const at::Tensor& b2, const at::Tensor& w3, const at::Tensor& b3, const at::Tensor& y,
+               const c10::optional<at::Tensor>& pos_weight, int64_t denom) {
+  on_gpu(z, "z");
+  TORCH_CHECK(z.dim() == 2 && z.size(1) == 64 && z.scalar_type() == at::kFloat, "pangnn::decoder_loss_z: z must be float32 [N, 64], got ",
+              z.sizes());
+  TORCH_CHECK(w_pq.is_cuda() && w_pq.device() == z.device() && w_pq.dim() == 2 && w_pq.size(0) == 128 && w_pq.size(1) == 64 &&
+                  b_pq.is_cuda() && b_pq.device() == z.device() && b_pq.numel() == 128 && w_pq.is_floating_point() &&
+                  b_pq.is_floating_point(),
+              "pangnn::decoder_loss_z: w_pq must be [128, 64] and b_pq [128] on ", z.device());
+  TORCH_CHECK(in_act == 0 || in_act == 1, "pangnn::decoder_loss_z: in_act is 0 or 1 (ELU)");
+  const DeviceGuard guard(z.device());
+  PqLayer L;
+  L.z = rows_any(z);
+  L.w = w_pq.to(at::kFloat).contiguous();
+  L.in_act = in_act;
+  const at::Tensor bc = b_pq.to(at::kFloat).contiguous();
+  const int64_t n = L.z.size(0);
+  auto pq = at::empty({n, 128}, L.z.options());
+  check_rc(pangnn_linear_act_fwd_mixed(L.z.data_ptr(), PANGNN_DTYPE_F32, L.z.stride(0), L.w.data_ptr<float>(), bc.data_ptr<float>(),
+                                       pq.data_ptr(), PANGNN_DTYPE_F32, pq.stride(0), n, 64, 128, (int32_t)in_act, nullptr, 0, 0,
+                                       stream_of(z)),
+           "pangnn_linear_act_fwd_mixed");
+  const DecIn in = decoder_inputs("decoder_loss_z", pq, extra, cvec, w2, b2, w3, b3);
+  operand_any_float("decoder_loss_z", "y", y, pq);
+  operand_any_float("decoder_loss_z", "pos_weight", pos_weight, pq);
+  TORCH_CHECK(y.dim() == 1 && y.size(0) == edge_index.size(1) && denom > 0, "pangnn::decoder_loss_z: y must be [E], denom > 0");
+  DecGrads r = decoder_train("decoder_loss_z", in, edge_index, y, pos_weight, denom, c10::nullopt, c10::nullopt, &L);
+  return {r.loss.view(at::IntArrayRef{}), r.logits, r.g_z, r.g_wpq.view_as(w_pq), r.g_bpq.view_as(b_pq), r.g_cv, r.g_w2.view_as(w2), r.g_b2,
+          r.g_w3.view_as(w3), r.g_b3.view_as(b3)};
 }
 
 at::Tensor decoder_mlp(const at::Tensor& pq, const at::Tensor& edge_index, const c10::optional<at::Tensor>& extra,
@@ -1132,6 +1219,44 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tenso
   return {o[0], o[1], o[2], o[3], o[4], o[5], o[6], o[7]};
 }
 
+class DecoderLossZFunction : public torch::autograd::Function<DecoderLossZFunction> {
+ public:
+  static variable_list forward(AutogradContext* ctx, const at::Tensor& z, const at::Tensor& w_pq, const at::Tensor& b_pq, int64_t in_act,
+                               const at::Tensor& edge_index, const OptT& extra, const OptT& cvec, const at::Tensor& w2,
+                               const at::Tensor& b2, const at::Tensor& w3, const at::Tensor& b3, const at::Tensor& y,
+                               const OptT& pos_weight, int64_t denom) {
+    at::AutoDispatchBelowADInplaceOrView below;
+    static auto op = typed_op<std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor,
+                                         at::Tensor, at::Tensor>(
+        const at::Tensor&, const at::Tensor&, const at::Tensor&, int64_t, const at::Tensor&, const OptT&, const OptT&, const at::Tensor&,
+        const at::Tensor&, const at::Tensor&, const at::Tensor&, const at::Tensor&, const OptT&, int64_t)>("pangnn::decoder_loss_z");
+    auto [loss, logits, g_z, g_wpq, g_bpq, g_cv, g_w2, g_b2, g_w3, g_b3] =
+        op.call(z, w_pq, b_pq, in_act, edge_index, extra, cvec, w2, b2, w3, b3, y, pos_weight, denom);
+    ctx->save_for_backward({g_z, g_wpq, g_bpq, g_cv, g_w2, g_b2, g_w3, g_b3});
+    ctx->saved_data["has_cv"] = defined(cvec);
+    ctx->mark_non_differentiable({logits, g_z, g_wpq, g_bpq, g_cv, g_w2, g_b2, g_w3, g_b3});
+    return {loss, logits, g_z, g_wpq, g_bpq, g_cv, g_w2, g_b2, g_w3, g_b3};
+  }
+  static variable_list backward(AutogradContext* ctx, variable_list grads) {
+    variable_list out(14);
+    if (!grads[0].defined()) return out;
+    const auto s = ctx->get_saved_variables();
+    const bool has_cv = ctx->saved_data["has_cv"].toBool();
+    auto g = scale_by_loss_grad(ctx, {s[0], s[1], s[2], has_cv ? s[3] : at::Tensor(), s[4], s[5], s[6], s[7]}, grads[0]);
+    out[0] = g[0]; out[1] = g[1]; out[2] = g[2];
+    if (has_cv) out[6] = g[3];
+    out[7] = g[4]; out[8] = g[5]; out[9] = g[6]; out[10] = g[7];
+    return out;
+  }
+};
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor>
+decoder_loss_z_autograd(const at::Tensor& z, const at::Tensor& w_pq, const at::Tensor& b_pq, int64_t in_act, const at::Tensor& edge_index,
+                        const OptT& extra, const OptT& cvec, const at::Tensor& w2, const at::Tensor& b2, const at::Tensor& w3,
+                        const at::Tensor& b3, const at::Tensor& y, const OptT& pos_weight, int64_t denom) {
+  auto o = DecoderLossZFunction::apply(z, w_pq, b_pq, in_act, edge_index, extra, cvec, w2, b2, w3, b3, y, pos_weight, denom);
+  return {o[0], o[1], o[2], o[3], o[4], o[5], o[6], o[7], o[8], o[9]};
+}
+
 class DecoderMlpFunction : public torch::autograd::Function<DecoderMlpFunction> {
  public:
   static at::Tensor forward(AutogradContext* ctx, const at::Tensor& pq, const at::Tensor& edge_index, const OptT& extra,
@@ -1269,6 +1394,9 @@ TORCH_LIBRARY_FRAGMENT(pangnn, m) {
   m.def("embed_propagate_backward(Tensor g, Tensor x, Tensor edge_index, Tensor? edge_weight) -> (Tensor, Tensor)");
   m.def("decoder_loss(Tensor pq, Tensor edge_index, Tensor? extra, Tensor? cvec, Tensor w2, Tensor b2, Tensor w3, Tensor b3, "
         "Tensor y, Tensor? pos_weight, int denom, Tensor? live) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
+  m.def("decoder_loss_z(Tensor z, Tensor w_pq, Tensor b_pq, int in_act, Tensor edge_index, Tensor? extra, Tensor? cvec, Tensor w2, "
+        "Tensor b2, Tensor w3, Tensor b3, Tensor y, Tensor? pos_weight, int denom) -> "
+        "(Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
   m.def("decoder_mlp(Tensor pq, Tensor edge_index, Tensor? extra, Tensor? cvec, Tensor w2, Tensor b2, Tensor w3, Tensor b3) -> Tensor");
   m.def("decoder_mlp_backward(Tensor g, Tensor pq, Tensor edge_index, Tensor? extra, Tensor? cvec, Tensor w2, Tensor b2, Tensor w3, "
         "Tensor b3) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
@@ -1302,6 +1430,7 @@ TORCH_LIBRARY_IMPL(pangnn, CUDA, m) {
   m.impl("embed_propagate", &embed_propagate);
   m.impl("embed_propagate_backward", &embed_propagate_backward);
   m.impl("decoder_loss", &decoder_loss);
+  m.impl("decoder_loss_z", &decoder_loss_z);
   m.impl("decoder_mlp", &decoder_mlp);
   m.impl("decoder_mlp_backward", &decoder_mlp_backward);
   m.impl("edge_score", &edge_score);
@@ -1317,6 +1446,7 @@ TORCH_LIBRARY_IMPL(pangnn, Autograd, m) {
   m.impl("embed_conv_in_linear", &embed_conv_in_linear_autograd);
   m.impl("embed_propagate", &embed_propagate_autograd);
   m.impl("decoder_loss", &decoder_loss_autograd);
+  m.impl("decoder_loss_z", &decoder_loss_z_autograd);
   m.impl("decoder_mlp", &decoder_mlp_autograd);
   m.impl("edge_score", &edge_score_autograd);
   m.impl("edge_score_loss", &edge_score_loss_autograd);

@@ -449,7 +449,9 @@ __global__ __launch_bounds__((FwdGeo<K, M>::WAVES * 64)) void linear_fwd_kernel(
 // of G.  Split-bf16 product: 2 steps of 16 rows on v_mfma_f32_32x32x16_bf16 — both operands are data here, so both are
 // split (three exact bf16 terms each, six partial products, smallest first): per tile 96 column reads, 12 splits, 96 matrix
 // instructions of 8 passes instead of the f32 product's 128 of 16.
-template <int K, int M>
+// ACT = 1: Xt holds the PRE-activation rows and ELU is applied as a value is read (every value is read exactly once, so this
+// is store_rows<K, 1>'s instruction count; pq_backward_parts_kernel keeps the raw rows because they are also its gate).
+template <int K, int M, int ACT = 0>
 __device__ __forceinline__ void wgrad_tile(const float* Xt, const float* Gt, int r, int hh, f32x16 (&acc)[M / 32][K / 32],
                                            float (&gbp)[M / 32]) {
   constexpr int KS = K + 4, MS = M + 4;
@@ -468,7 +470,10 @@ __device__ __forceinline__ void wgrad_tile(const float* Xt, const float* Gt, int
     for (int b = 0; b < K / 32; ++b) {
       float f[8];
 #pragma unroll
-      for (int q = 0; q < 8; ++q) f[q] = Xt[(row0 + q) * KS + r + 32 * b];
+      for (int q = 0; q < 8; ++q) {
+        f[q] = Xt[(row0 + q) * KS + r + 32 * b];
+        if (ACT == 1) f[q] = elu1(f[q]);
+      }
       xb[b] = split8(make_float4(f[0], f[1], f[2], f[3]), make_float4(f[4], f[5], f[6], f[7]));
     }
 #define PG_W3(GT, XT)                                                                                     \
@@ -717,6 +722,231 @@ static int launch_wgrad(const void* g, int g16, int64_t ldg, const void* x, int 
   if (x16) PG_WG(float, H);
   PG_WG(float, float);
 #undef PG_WG
+}
+
+// ==============================================================================================================
+// Backward of the decoder's P | Q layer straight from the run parts of the S and T kernels (64 -> 128 only):
+//     G[r][0:64)   = sum of parts_s[rowptr_s[r] .. rowptr_s[r+1])        dL/dP   (the two spmm_thin_kernel<64> part sums)
+//     G[r][64:128) = sum of parts_t[rowptr_t[r] .. rowptr_t[r+1])        dL/dQ
+//     gx = (G w) * ELU'(x)     linear_fwd_kernel<128, 64, 0, GATE>       gw = G^T act(x), gb = colsum G     linear_wgrad_kernel
+// The [N, 128] matrix G is never written: each 32-row tile of it is formed in LDS and both products run on that tile.
+// Geometry, tile order, accumulators, finish and slab reduction are linear_wgrad_kernel<64, 128>'s, the row sums are
+// spmm_thin_kernel's fmaf(1, part, acc) chains from +0 in part order, the dL/dx product and epilogue are the gated forward
+// kernel's: gx, gw and gb equal the four-launch sequence bit for bit.
+// Sixteen lanes own a (row, half) with one float4 each.  A tile's row pointers are fetched two tiles ahead (one 32-bit
+// value per lane, handed out by shuffles), the first part of every row one tile ahead (16 float4 per lane: a second level
+// of prefetch registers spills); rows with more parts (1.14 per row on average) fetch the rest level by level when the tile
+// is formed.
+// ==============================================================================================================
+struct PartTables {
+  const float* parts[2];        // [n_parts, 64] contiguous
+  const int64_t* rowptr[2];     // int64 [n + 1], absolute part positions
+  uint32_t n_parts[2];
+};
+
+__device__ __forceinline__ float4 ld_part(const float* parts, uint32_t idx, int c4) {
+  typedef float f32x4 __attribute__((ext_vector_type(4)));
+  const f32x4 t = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(parts + (int64_t)idx * 64 + 4 * c4));
+  return make_float4(t[0], t[1], t[2], t[3]);
+}
+
+// rowptr[min(32 t + lane, n)] of both tables as 32-bit positions (lanes 0..32 are used)
+__device__ __forceinline__ void load_part_ptrs(const PartTables& pt, int64_t n, int64_t tile, int lane, uint32_t (&rp)[2]) {
+  int64_t i = tile * 32 + lane;
+  if (i > n) i = n;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) rp[h] = (uint32_t)pt.rowptr[h][i];
+}
+
+// slot i of a lane: half i >> 3 of row 4 (i & 7) + lane / 16
+__device__ __forceinline__ void part_range(const uint32_t (&rp)[2], int i, int lane, uint32_t& beg, int& cnt) {
+  const int row = 4 * (i & 7) + (lane >> 4);
+  beg = __shfl(rp[i >> 3], row);
+  cnt = (int)(__shfl(rp[i >> 3], row + 1) - beg);
+}
+
+__device__ __forceinline__ void issue_parts(const PartTables& pt, const uint32_t (&rp)[2], int lane, float4 (&pa)[16]) {
+  const int c4 = lane & 15;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    uint32_t beg;
+    int cnt;
+    part_range(rp, i, lane, beg, cnt);
+    pa[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (cnt > 0 && beg < pt.n_parts[i >> 3]) pa[i] = ld_part(pt.parts[i >> 3], beg, c4);
+  }
+}
+
+__device__ __forceinline__ void add_part(float4& acc, const float4& p) {
+  acc.x = fmaf(1.f, p.x, acc.x);
+  acc.y = fmaf(1.f, p.y, acc.y);
+  acc.z = fmaf(1.f, p.z, acc.z);
+  acc.w = fmaf(1.f, p.w, acc.w);
+}
+
+// part k (>= 1) of every slot that has one
+__device__ __forceinline__ void load_level(const PartTables& pt, const uint32_t (&rp)[2], int lane, int k, float4 (&t)[16]) {
+  const int c4 = lane & 15;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    uint32_t beg;
+    int cnt;
+    part_range(rp, i, lane, beg, cnt);
+    t[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (k < cnt && beg + (uint32_t)k < pt.n_parts[i >> 3]) t[i] = ld_part(pt.parts[i >> 3], beg + (uint32_t)k, c4);
+  }
+}
+
+// The wave's two LDS tiles from what was prefetched: Xt [32][68] = the raw x rows, Gt [32][132] = the part sums (rows >= n
+// and empty rows: +0).  The second parts are requested first and land behind the x tile's stores and the first adds.
+template <int K>
+__device__ __forceinline__ void form_tiles(const PartTables& pt, const uint32_t (&rp)[2], int lane, const RowRegs<K, float>& rx,
+                                           const float4 (&pa)[16], float* Xt, float* Gt) {
+  constexpr int MS = 128 + 4;
+  const int c4 = lane & 15;
+  float4 acc[16], t[16];
+  int most = 0;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    uint32_t beg;
+    int cnt;
+    part_range(rp, i, lane, beg, cnt);
+    most = cnt > most ? cnt : most;
+  }
+  const bool more = __any(most > 1);                    // wave-uniform
+  if (more) load_level(pt, rp, lane, 1, t);
+  store_rows<K, 0, float>(rx, lane, Xt);                // raw rows: ELU on read (wgrad), ELU' in the dL/dx epilogue
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    acc[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    add_part(acc[i], pa[i]);                            // no part: +0 + +0
+  }
+  if (more) {
+    for (int k = 1;;) {
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        uint32_t beg;
+        int cnt;
+        part_range(rp, i, lane, beg, cnt);
+        if (k < cnt) add_part(acc[i], t[i]);
+      }
+      if (!__any(++k < most)) break;
+      load_level(pt, rp, lane, k, t);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 16; ++i)
+    *reinterpret_cast<float4*>(Gt + (4 * (i & 7) + (lane >> 4)) * MS + 64 * (i >> 3) + 4 * c4) = acc[i];
+}
+
+template <int K, int M, int ACT>
+__global__ __launch_bounds__(256) void pq_backward_parts_kernel(PartTables pt, const float* __restrict__ x, int64_t ldx,
+                                                                const float* __restrict__ w, float* __restrict__ gx,
+                                                                int64_t ldgx, int64_t n, int64_t n_tiles,
+                                                                float* __restrict__ slabs) {
+  static_assert(K == 64 && M == 128, "the decoder's P | Q layer");
+  static_assert(WImg<M, K>::X3, "dL/dx runs tile_product_x3<M, K> on the G tile, whose row stride M + 4 is that product's");
+  constexpr int KS = K + 4, MS = M + 4;
+  constexpr int PER_WAVE = 32 * KS + 32 * MS;
+  constexpr int SLAB = WgradGeo<K, M>::SLAB;
+  constexpr int WF = (WImg<M, K>::FLOATS + 3) & ~3;                 // three bf16 images of w^T, [K][M + 8]
+  constexpr int LDS_F = 4 * PER_WAVE;
+  static_assert(LDS_F >= SLAB, "slab image of the wgrad finish");
+  __shared__ __attribute__((aligned(16))) float lds[WF + LDS_F];
+  float* Wl = lds;
+  float* tiles = lds + WF;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  float* Xt = tiles + wave * PER_WAVE;
+  float* Gt = Xt + 32 * KS;
+  stage_w<M, K>(w, 1, K, Wl, 256);                                  // operand [K][M]: element (k, m) = w[m][k]
+  __syncthreads();
+  const int r = lane & 31, hh = lane >> 5;
+  f32x16 acc[M / 32][K / 32];
+  float gbp[M / 32];
+#pragma unroll
+  for (int a = 0; a < M / 32; ++a) {
+    gbp[a] = 0.f;
+#pragma unroll
+    for (int b = 0; b < K / 32; ++b)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) acc[a][b][i] = 0.f;
+  }
+  const int64_t stride = (int64_t)gridDim.x * 4;
+  int64_t tile = (int64_t)blockIdx.x * 4 + wave;
+  RowRegs<K, float> rx;
+  float4 pa[16];
+  uint32_t rp[2], rp_next[2];
+  load_rows<K, float>(x, ldx, n, tile * 32, lane, rx);
+  load_part_ptrs(pt, n, tile, lane, rp);
+  issue_parts(pt, rp, lane, pa);
+  load_part_ptrs(pt, n, tile + stride, lane, rp_next);
+  for (; tile < n_tiles; tile += stride) {
+    form_tiles<K>(pt, rp, lane, rx, pa, Xt, Gt);
+    load_rows<K, float>(x, ldx, n, (tile + stride) * 32, lane, rx);
+    rp[0] = rp_next[0];
+    rp[1] = rp_next[1];
+    issue_parts(pt, rp, lane, pa);
+    load_part_ptrs(pt, n, tile + 2 * stride, lane, rp_next);
+    wave_sync_lds();
+    wgrad_tile<K, M, ACT>(Xt, Gt, r, hh, acc, gbp);
+    // dL/dx = (G w) * ELU'(x): linear_fwd_kernel<M, K, 0, GATE>'s product and epilogue, gate read from the x tile
+    f32x16 dx[K / 32];
+    tile_product_x3<M, K>(Gt, Wl, r, hh, dx);
+    if (tile * 32 + 32 <= n) {                                      // wave-uniform: full tile, 128-byte row segments
+      uint32_t loff = (4u * hh * (uint32_t)ldgx + r) * (uint32_t)sizeof(float);
+      int64_t sbase = tile * 32;
+      pin(sbase, loff);
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        float* yr = gx + (sbase + (i & 3) + 8 * (i >> 2)) * ldgx;
+#pragma unroll
+        for (int b = 0; b < K / 32; ++b) {
+          float v = dx[b][i] + 0.f;                                 // the forward kernel's "+ bias" with no bias: -0 -> +0
+          if (ACT == 1) v *= elu1_grad(Xt[jrow(i, hh) * KS + r + 32 * b]);
+          st_f32(yr + 32 * b, loff, v);
+        }
+      }
+    } else {
+#pragma unroll
+      for (int b = 0; b < K / 32; ++b)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          const int64_t row = tile * 32 + jrow(i, hh);
+          if (row < n) {
+            float v = dx[b][i] + 0.f;
+            if (ACT == 1) v *= elu1_grad(Xt[jrow(i, hh) * KS + r + 32 * b]);
+            gx[row * ldgx + r + 32 * b] = v;
+          }
+        }
+    }
+    wave_sync_lds();
+  }
+#pragma unroll
+  for (int a = 0; a < M / 32; ++a) gbp[a] += __shfl_xor(gbp[a], 32);
+  wgrad_finish<K, M, LDS_F>(acc, gbp, tiles, slabs + (int64_t)blockIdx.x * SLAB, wave, lane);
+}
+
+static int launch_pq_backward_parts(const PartTables& pt, const float* x, int64_t ldx, const float* w, int64_t n, int in_act,
+                                    float* gx, int64_t ldgx, float* gw, float* gb, float* ws, size_t ws_bytes, hipStream_t s) {
+  constexpr int K = 64, M = 128, SLAB = WgradGeo<K, M>::SLAB;
+  const int64_t n_tiles = (n + 31) / 32;
+  int64_t grid = (n_tiles + 3) / 4;                                 // linear_wgrad_kernel's geometry: same slabs, same order
+  const int64_t cap = (int64_t)num_cus();
+  if (grid > cap) grid = cap;
+  if (grid < 1) grid = 1;
+  PG_CHECK_ARG(ws && ws_bytes >= (size_t)grid * SLAB * sizeof(float), PANGNN_E_WORKSPACE,
+               "pangnn_linear_act_backward_parts_f32: workspace too small");
+  if (in_act)
+    hipLaunchKernelGGL((pq_backward_parts_kernel<K, M, 1>), dim3((unsigned)grid), dim3(256), 0, s, pt, x, ldx, w, gx, ldgx, n,
+                       n_tiles, ws);
+  else
+    hipLaunchKernelGGL((pq_backward_parts_kernel<K, M, 0>), dim3((unsigned)grid), dim3(256), 0, s, pt, x, ldx, w, gx, ldgx, n,
+                       n_tiles, ws);
+  PG_CHECK_LAUNCH("pangnn_linear_act_backward_parts_f32");
+  hipLaunchKernelGGL(slab_reduce_kernel, dim3((SLAB + kWave - 1) / kWave), dim3(kSumThreads), 0, s, ws, (int)grid, SLAB,
+                     M * K, gw, gb);
+  PG_CHECK_LAUNCH("pangnn_linear_act_backward_parts_f32(reduce)");
+  return 0;
 }
 
 
@@ -1242,6 +1472,36 @@ extern "C" int pangnn_linear_wgrad_f32(const float* g, int64_t ldg, const float*
                                        int32_t K, int32_t M, float* gw, float* gb, void* workspace,
                                        size_t workspace_bytes, pangnn_stream_t stream) {
   return pangnn_linear_act_wgrad_f32(g, ldg, x, ldx, n, K, M, 0, gw, gb, workspace, workspace_bytes, stream);
+}
+
+// backward of the decoder's P | Q layer from the run parts (pq_backward_parts_kernel): gx [n, 64], gw [128, 64], gb [128]
+extern "C" int pangnn_linear_act_backward_parts_f32(const float* parts_s, const int64_t* rowptr_s, int64_t n_parts_s,
+                                                    const float* parts_t, const int64_t* rowptr_t, int64_t n_parts_t,
+                                                    const float* x, int64_t ldx, const float* w, int64_t n, int32_t K, int32_t M,
+                                                    int32_t in_act, float* gx, int64_t ldgx, float* gw, float* gb,
+                                                    void* workspace, int64_t workspace_bytes, pangnn_stream_t stream) {
+  const char* who = "pangnn_linear_act_backward_parts_f32";
+  PG_CHECK_ARG(n >= 0 && n_parts_s >= 0 && n_parts_t >= 0, PANGNN_E_BADARG, "%s: negative size", who);
+  PG_CHECK_ARG(K == 64 && M == 128, PANGNN_E_BADARG, "%s: (K, M) must be (64, 128), got (%d, %d)", who, (int)K, (int)M);
+  PG_CHECK_ARG(in_act == 0 || in_act == 1, PANGNN_E_BADARG, "%s: in_act must be 0 or 1", who);
+  PG_CHECK_ARG(n_parts_s <= INT32_MAX && n_parts_t <= INT32_MAX, PANGNN_E_TOOLARGE, "%s: more than 2^31 - 1 part rows", who);
+  PG_CHECK_ARG(gw && gb && w && (n == 0 || (x && gx && rowptr_s && rowptr_t)) && (n_parts_s == 0 || parts_s) &&
+                   (n_parts_t == 0 || parts_t) && ldx >= K && ldgx >= K,
+               PANGNN_E_BADARG, "%s: bad pointer / ld", who);
+  PG_CHECK_ARG(aligned16(x) && aligned16(w) && aligned16(parts_s) && aligned16(parts_t) && ldx % 4 == 0, PANGNN_E_ALIGN,
+               "%s: x rows, w and the part tables must start on 16 bytes, ldx % 4 == 0", who);
+  hipStream_t s = (hipStream_t)stream;
+  if (n == 0) {                       // no rows: the sums are +0
+    hipError_t e = hipMemsetAsync(gw, 0, (size_t)M * K * sizeof(float), s);
+    if (e == hipSuccess) e = hipMemsetAsync(gb, 0, (size_t)M * sizeof(float), s);
+    return (int)e;
+  }
+  PartTables pt;
+  pt.parts[0] = parts_s; pt.parts[1] = parts_t;
+  pt.rowptr[0] = rowptr_s; pt.rowptr[1] = rowptr_t;
+  pt.n_parts[0] = (uint32_t)n_parts_s; pt.n_parts[1] = (uint32_t)n_parts_t;
+  return launch_pq_backward_parts(pt, x, ldx, w, n, in_act, gx, ldgx, gw, gb, static_cast<float*>(workspace),
+                                  workspace_bytes > 0 ? (size_t)workspace_bytes : 0, s);
 }
 
 // ---- first layer by linearity fused into the following dense layer (see gen_linear_*_kernel above) ----

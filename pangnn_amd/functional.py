@@ -481,10 +481,11 @@ def _sum_parts(plan, part_buf: torch.Tensor, n_rows: int, out: torch.Tensor, acc
 
 
 def _dgrad_sum(rec, st: EdgeStructure, by: Optional[str], w2, w3, n_rows: int = 0, out=None, g_b2=None, live=None,
-               accumulate: bool = False):
+               accumulate: bool = False, raw_parts: bool = False):
     """dL/dh1 summed over the rows of CSR order `by` ("src" / "dst") from the per-edge records of the training
     kernel: pangnn_decoder_dgrad_f32 (run parts) + the short contiguous part sum.  `g_b2`: also filled with dL/db2
-    (one call per step asks for it); by = None: the parameter sums alone."""
+    (one call per step asks for it); by = None: the parameter sums alone.  `raw_parts`: no part sum — (plan, parts) come
+    back for pangnn_linear_act_backward_parts_f32."""
     lib = _lib.load()
     dev = rec.device
     plan = st.csr_plan(by, d16_chunk(st.num_edges)) if by else None
@@ -504,6 +505,8 @@ def _dgrad_sum(rec, st: EdgeStructure, by: Optional[str], w2, w3, n_rows: int = 
         _timer_stop("dec.dgrad", ev)
     if plan is None:
         return None
+    if raw_parts:
+        return plan, parts
     if out is None:
         out, accumulate = torch.empty(n_rows, 64, device=dev), False
     return _sum_parts(plan, parts, n_rows, out, accumulate)
@@ -511,7 +514,7 @@ def _dgrad_sum(rec, st: EdgeStructure, by: Optional[str], w2, w3, n_rows: int = 
 
 def _decoder_train16(p, q, st: EdgeStructure, ex, cv, w2, b2, w3, b3, y=None, pw=None, denom=0, g_logits=None,
                      out_p=None, out_q=None, need_p=True, need_q=True, after_p=None, live=None, accumulate_q=False,
-                     p_windows=None, out_logits=None):
+                     p_windows=None, out_logits=None, raw_parts=False):
     """Two-wave-per-SIMD training decoder (csrc/decoder16.hip).  One pass over the edges in the caller's order (S):
     logits, loss (y given) or the given dL/dlogits, every parameter gradient, per-source run sums when the list is
     source-sorted, and a 32-byte record per edge; then dL/dQ (and dL/dP for unsorted lists) from the records in CSR
@@ -523,7 +526,9 @@ def _decoder_train16(p, q, st: EdgeStructure, ex, cv, w2, b2, w3, b3, y=None, pw
     `accumulate_q` (with out_q): dL/dQ is ADDED to out_q (a second edge range of the same targets: the partitioned decoder).
     `p_windows` (source-sorted lists only): [(row_lo, row_hi, out [row_hi - row_lo, 64]), ...] — dL/dP is wanted for these row
     ranges only, each written to its own tensor (an edge range whose sources lie in known row ranges: nothing is written for
-    the rows in between); the returned gp is then the list of those tensors.  `out_logits`: where the fused-loss logits go."""
+    the rows in between); the returned gp is then the list of those tensors.  `out_logits`: where the fused-loss logits go.
+    `raw_parts` (a non-empty source-sorted list, no windows): neither part sum is launched — gp and gq are the (plan, parts)
+    pairs of S and T, which pangnn_linear_act_backward_parts_f32 sums inside the P | Q layer's backward."""
     lib = _lib.load()
     dev = p.device
     e, d = st.num_edges, p.shape[1]
@@ -557,6 +562,8 @@ def _decoder_train16(p, q, st: EdgeStructure, ex, cv, w2, b2, w3, b3, y=None, pw
             gp = [o.zero_() for _, _, o in p_windows]
         elif e == 0:
             gp = (out_p if out_p is not None else torch.empty(p.shape[0], d, device=dev)).zero_()
+        elif raw_parts:
+            gp = (plan, parts)
         elif plan is not None and p_windows is not None:
             gp = [_sum_parts(plan, parts, hi - lo, o, row_lo=lo) for lo, hi, o in p_windows]
         elif plan is not None:
@@ -573,7 +580,8 @@ def _decoder_train16(p, q, st: EdgeStructure, ex, cv, w2, b2, w3, b3, y=None, pw
         if e == 0:
             gq = out_q if acc_q else (out_q if out_q is not None else torch.empty(q.shape[0], d, device=dev)).zero_()
         else:
-            gq = _dgrad_sum(rec, st, "dst", w2, w3, q.shape[0], out_q, g_b2=b2_out, live=live, accumulate=acc_q)
+            gq = _dgrad_sum(rec, st, "dst", w2, w3, q.shape[0], out_q, g_b2=b2_out, live=live, accumulate=acc_q,
+                            raw_parts=raw_parts)
             b2_out = None
     if b2_out is not None:
         if e == 0:
@@ -869,6 +877,86 @@ def decoder_loss_pq(pq, st, extra, cvec, w2, b2, w3, b3, y, pos_weight, denom, l
         from . import torch_ops
         return torch_ops.decoder_loss_pq(pq, st, extra, cvec, w2, b2, w3, b3, y, pos_weight, denom, live)
     return _DecoderLoss.apply(pq, None, st, extra, cvec, w2, b2, w3, b3, y, pos_weight, denom, True, live)
+
+
+# ---- the fused loss with the P | Q layer in front of it: pq = linear(z, w_pq, b_pq, in_act), S and T as decoder_loss_pq runs
+# them, and the layer's backward straight from the run parts of S and T (pangnn_linear_act_backward_parts_f32): neither part sum
+# is launched and the [N, 128] gradient dL/dP | dL/dQ never exists.  Bit-equal to linear -> decoder_loss_pq -> linear's
+# backward.  PANGNN_FUSED_PQ_BWD=0 keeps that route (the A/B baseline); read per call, so a process can run both.
+@torch.compiler.assume_constant_result
+def fused_pq_backward_enabled() -> bool:
+    return os.environ.get("PANGNN_FUSED_PQ_BWD", "1") != "0"
+
+
+def fused_pq_backward_applies(z, w_pq, b_pq, st, live=None) -> bool:
+    """decoder_loss_z can take this call: default decoder precision, f32 rows (no autocast row format), the 64 -> 128 layer, a
+    whole graph whose list is sorted by source (a run-sum plan exists), no padded batch.  Under an eager dispatch mode the
+    step keeps one registered op per layer (linear, decoder_loss, linear_backward): that is what such an observer is there to
+    see, and the values are the same."""
+    if not (DECODER_PRECISION == 1 and live is None and b_pq is not None and fused_pq_backward_enabled()):
+        return False
+    if not torch.compiler.is_compiling() and _dispatch_modes() > 0:
+        return False
+    if not (z.dim() == 2 and z.shape[1] == 64 and z.dtype == torch.float32 and w_pq.dtype == torch.float32
+            and tuple(w_pq.shape) == (128, 64) and autocast_rows_dtype(z) is None):
+        return False
+    if st.num_src != st.num_nodes or st.num_edges == 0:
+        return False
+    return bool(getattr(st, "traced", False)) or st.sorted_by_src()      # traced: the op decides when it runs
+
+
+class _DecoderLossZ(torch.autograd.Function):
+    """decoder_loss_z over ctypes (the route a KERNEL_TIMER with the decoder tags takes): everything is computed in forward(),
+    backward() scales by the upstream gradient of the loss like _DecoderLoss"""
+
+    @staticmethod
+    def forward(ctx, z, w_pq, b_pq, in_act, st: EdgeStructure, extra, cvec, w2, b2, w3, b3, y, pos_weight, denom):
+        lib = _lib.load()
+        _lib.require_device(z, w_pq, b_pq, extra, cvec, w2, b2, w3, b3, y, pos_weight)
+        z, w_pq, b_pq = _rows_f32(z), _f32c(w_pq), _f32c(b_pq)
+        n, dev = z.shape[0], z.device
+        pq = torch.empty(n, 128, dtype=torch.float32, device=dev)
+        with _lib.device_guard(dev):
+            _lib.check(lib.pangnn_linear_act_fwd_mixed(z.data_ptr(), 0, z.stride(0), w_pq.data_ptr(), b_pq.data_ptr(),
+                                                       pq.data_ptr(), 0, pq.stride(0), n, 64, 128, int(in_act), None, 0, 0,
+                                                       _lib.stream_ptr()), "pangnn_linear_act_fwd_mixed")
+        p, q, ex, cv, w2, b2, w3, b3, y, pw = _decoder_operands(pq, None, extra, cvec, w2, b2, w3, b3, y, pos_weight)
+        loss, logits, (plan_s, parts_s), (plan_t, parts_t), g_cv, g_w2, g_b2, g_w3, g_b3 = _decoder_train16(
+            p, q, st, ex, cv, w2, b2, w3, b3, y=y, pw=pw, denom=denom, raw_parts=True)
+        g_z = torch.empty(n, 64, dtype=torch.float32, device=dev)
+        g_wpq, g_bpq = torch.empty_like(w_pq), torch.empty_like(b_pq)
+        with _lib.device_guard(dev):
+            ws_bytes = lib.pangnn_linear_wgrad_workspace_bytes(64, 128)
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            _lib.check(lib.pangnn_linear_act_backward_parts_f32(
+                parts_s.data_ptr(), plan_s.part_rowptr.data_ptr(), parts_s.shape[0], parts_t.data_ptr(),
+                plan_t.part_rowptr.data_ptr(), parts_t.shape[0], z.data_ptr(), z.stride(0), w_pq.data_ptr(), n, 64, 128,
+                int(in_act), g_z.data_ptr(), g_z.stride(0), g_wpq.data_ptr(), g_bpq.data_ptr(), ws.data_ptr(), ws_bytes,
+                _lib.stream_ptr()), "pangnn_linear_act_backward_parts_f32")
+        ctx.has_cv = g_cv is not None
+        ctx.save_for_backward(g_z, g_wpq, g_bpq, g_cv if g_cv is not None else g_z.new_empty(0), g_w2, g_b2, g_w3, g_b3)
+        ctx.mark_non_differentiable(logits)
+        return loss.view(()), logits
+
+    @staticmethod
+    def backward(ctx, go, _go_logits):
+        g = list(ctx.saved_tensors)
+        if not ctx.has_cv:
+            g[3] = None
+        if not is_unit_grad(go):         # `loss.backward(unit_grad(device))` (train.train_step): nothing to scale
+            g = scale_by_loss_grad_(ctx, g, go)
+        g_z, g_wpq, g_bpq, g_cv, g_w2, g_b2, g_w3, g_b3 = g
+        return (g_z, g_wpq, g_bpq, None, None, None, g_cv, g_w2, g_b2, g_w3, g_b3, None, None, None)
+
+
+def decoder_loss_z(z, w_pq, b_pq, in_act, st, extra, cvec, w2, b2, w3, b3, y, pos_weight, denom):
+    """(loss, detached logits) of the fused decoder on pq = linear(z, w_pq, b_pq, in_act); the caller has checked
+    fused_pq_backward_applies"""
+    _lib.require_device(z, w_pq, b_pq, extra, cvec, w2, b2, w3, b3, y, pos_weight)
+    if _via_ops(st, _timed_decoder()):
+        from . import torch_ops
+        return torch_ops.decoder_loss_z(z, w_pq, b_pq, in_act, st, extra, cvec, w2, b2, w3, b3, y, pos_weight, denom)
+    return _DecoderLossZ.apply(z, w_pq, b_pq, int(in_act), st, extra, cvec, w2, b2, w3, b3, y, pos_weight, denom)
 
 
 # ---- weightless link decoders (--decoder cosine / dotproduct, gnn.py:171-180,202-207): csrc/edge_score.hip

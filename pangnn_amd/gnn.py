@@ -227,19 +227,25 @@ class AlternateGCN(nn.Module):
         """the per-edge input of `--skip_connections` (gnn.py:173), else None"""
         return graph.edge_attr[: graph.edge_index.shape[1]] if self.flags.skip_connections else None
 
-    def _decoder_pq(self, z, graph, in_act: int = 0, rows16: bool = True):
+    def _pq_operands(self, z):
+        """(w_pq, b_pq, cvec) of the re-associated first decoder layer"""
+        lin0 = self.mlp[0]
+        return PF.pq_operands(lin0.weight, lin0.bias, z.shape[1], bool(self.flags.skip_connections))
+
+    def _decoder_pq(self, z, graph, in_act: int = 0, rows16: bool = True, operands=None):
         """(P | Q [N, 2D], extra, cvec) of the re-associated first decoder layer: ONE node-level product
         z [W_a ; W_b]^T + [0 ; b1].  bf16 / fp16 mixed precision: mlp[0] is an autocast Linear, its node-level halves are
         stored (and gathered) in that type where the decoder kernel reads them so (`rows16`: the caller's decoder does)"""
-        lin0 = self.mlp[0]
-        w_pq, b_pq, cvec = PF.pq_operands(lin0.weight, lin0.bias, z.shape[1], bool(self.flags.skip_connections))
+        w_pq, b_pq, cvec = self._pq_operands(z) if operands is None else operands
         pq_dtype = PF.autocast_rows_dtype(z) if (rows16 and self._decoder16()) else None
         return self._linear(z, w_pq, b_pq, in_act, pq_dtype), self._skip_feature(graph), cvec
 
     def _fused_decoder_operands(self, graph):
-        """(pq, structure, extra, cvec) of the one-pass training decoder, or None where that kernel does not apply (another
-        decoder, a node_dim it is not built for, no gradient wanted): the encoder (gnn.py:125-166) with its last ELU folded
-        into the node-level half of `mlp[0]` (gnn.py:110,173-175)"""
+        """(pq, structure, extra, cvec, layer) of the one-pass training decoder, or None where that kernel does not apply
+        (another decoder, a node_dim it is not built for, no gradient wanted): the encoder (gnn.py:125-166) with its last ELU
+        folded into the node-level half of `mlp[0]` (gnn.py:110,173-175).  Where PF.decoder_loss_z applies (see
+        PF.fused_pq_backward_applies) the P | Q product is left to that operator: pq is None and layer = (z, w_pq, b_pq,
+        in_act)."""
         z, pending = self._encode_pre(graph)
         fused = "mlp" in self.flags.decoder and self.fused_decoder is True and self._fused_width() and torch.is_grad_enabled()
         if not (fused and pending and self._fold_elu()):
@@ -247,8 +253,13 @@ class AlternateGCN(nn.Module):
         if not fused:
             return None, z
         st = structure_of(graph.edge_index, z.shape[0], holder=graph, name="sim")
-        pq, extra, cvec = self._decoder_pq(z, graph, 1 if pending else 0)
-        return (pq, st, extra, cvec), z
+        in_act = 1 if pending else 0
+        operands = self._pq_operands(z)
+        if type(self)._linear is AlternateGCN._linear and self._decoder16() and PF.fused_pq_backward_applies(
+                z, operands[0], operands[1], st, getattr(graph, "live_edges", None)):
+            return (None, st, self._skip_feature(graph), operands[2], (z, operands[0], operands[1], in_act)), z
+        pq, extra, cvec = self._decoder_pq(z, graph, in_act, operands=operands)
+        return (pq, st, extra, cvec, None), z
 
     def loss_and_logits(self, graph, labels, pos_weight=None):
         """`criterion(model(graph), labels)` (pangnn.py:200-203) as ONE decoder pass when the fused kernel
@@ -258,7 +269,10 @@ class AlternateGCN(nn.Module):
         from .train import criterion
         ops, z = self._fused_decoder_operands(graph)
         if ops is not None:
-            pq, st, extra, cvec = ops
+            pq, st, extra, cvec, layer = ops
+            if layer is not None:
+                return PF.decoder_loss_z(*layer, st, extra, cvec, self.mlp[2].weight, self.mlp[2].bias,
+                                         self.mlp[4].weight.view(-1), self.mlp[4].bias, labels, pos_weight, labels.shape[0])
             # a padded fixed-shape batch (SubGraphDataset.padded_buffers) carries the number of its real edges on the device
             return PF.decoder_loss_pq(pq, st, extra, cvec, self.mlp[2].weight, self.mlp[2].bias,
                                       self.mlp[4].weight.view(-1), self.mlp[4].bias, labels, pos_weight,
@@ -334,7 +348,7 @@ class AlternateGCN(nn.Module):
             return self._decode(z, graph)
         return self._decode(self.encode(graph), graph)
 
-    def _deferred(self, graph, pq, st, extra, cvec):
+    def _deferred(self, graph, pq, st, extra, cvec, layer=None):
         from .deferred import DeferredLogits
         w2, b2, w3, b3 = self.mlp[2].weight, self.mlp[2].bias, self.mlp[4].weight.view(-1), self.mlp[4].bias
         live = getattr(graph, "live_edges", None)
@@ -343,12 +357,16 @@ class AlternateGCN(nn.Module):
             if live is not None:
                 raise NotImplementedError("a padded fixed-shape batch needs the fused training decoder: call "
                                           "BCEWithLogitsLoss(pos_weight)(output, labels) on the model's output first")
-            return PF.decoder_mlp_pq(pq, st, extra, cvec, w2, b2, w3, b3)
+            # (the fused loss forms P | Q itself: a use that needs the inference kernel computes the rows here)
+            rows = pq if layer is None else self._linear(layer[0], layer[1], layer[2], layer[3])
+            return PF.decoder_mlp_pq(rows, st, extra, cvec, w2, b2, w3, b3)
 
         def fused_loss(labels, pos_weight):
+            if layer is not None:
+                return PF.decoder_loss_z(*layer, st, extra, cvec, w2, b2, w3, b3, labels, pos_weight, labels.shape[0])
             return PF.decoder_loss_pq(pq, st, extra, cvec, w2, b2, w3, b3, labels, pos_weight, labels.shape[0], live=live)
 
-        return DeferredLogits(st.num_edges, pq.device, materialize, fused_loss)
+        return DeferredLogits(st.num_edges, (pq if layer is None else layer[0]).device, materialize, fused_loss)
 
     def _pairs(self, z, edge_index, graph=None):
         st = structure_of(edge_index, z.shape[0], holder=graph, name="sim")

@@ -11,7 +11,7 @@ registers, on the same ops,
     stored (half the bytes) with fp32 weights / accumulation / result; float16 rows are promoted to fp32 (the kernels
     have no fp16 row format); everything else runs in fp32.
 The per-step operators of the train step that read a graph (gcn_propagate, embed_conv_in[_linear], embed_propagate,
-decoder_loss, decoder_mlp, edge_score, edge_score_loss, edge_conv and their backward ops) are C++ too since round 5 (csrc/graph_ops.cpp: schema, HIP implementation,
+decoder_loss, decoder_loss_z, decoder_mlp, edge_score, edge_score_loss, edge_conv and their backward ops) are C++ too since round 5 (csrc/graph_ops.cpp: schema, HIP implementation,
 autograd formula, and the structure registry they look a graph up in by the identity of its `edge_index` tensor); the second
 half of this module holds their fake kernels, the registry's build-on-miss hook and the wrappers `functional` calls with this
 package's structure objects.  edge_score, edge_score_loss and edge_conv have no other route, like linear and bce_with_logits;
@@ -226,6 +226,13 @@ def _(pq, edge_index, extra, cvec, w2, b2, w3, b3, y, pos_weight, denom, live):
             f(*b2.shape), f(*w3.shape), f(*b3.shape))
 
 
+@torch.library.register_fake("pangnn::decoder_loss_z")
+def _(z, w_pq, b_pq, in_act, edge_index, extra, cvec, w2, b2, w3, b3, y, pos_weight, denom):
+    f = lambda *s: w2.new_empty(s, dtype=torch.float32)           # noqa: E731
+    return (f(), f(edge_index.shape[1]), f(*z.shape), f(*w_pq.shape), f(*b_pq.shape),
+            f(*(cvec.shape if cvec is not None else (0,))), f(*w2.shape), f(*b2.shape), f(*w3.shape), f(*b3.shape))
+
+
 @torch.library.register_fake("pangnn::decoder_mlp")
 def _(pq, edge_index, extra, cvec, w2, b2, w3, b3):
     return w2.new_empty(edge_index.shape[1], dtype=torch.float32)
@@ -303,6 +310,12 @@ def embed_propagate(x_tab, w, b, st, norm):
 def decoder_loss_pq(pq, st, extra, cvec, w2, b2, w3, b3, y, pos_weight, denom, live=None):
     _ready(st, _G.NEED_BY_DST | _G.NEED_RUNSUM | _G.NEED_PLAN_DST)
     out = ops.decoder_loss(pq, st._key_tensor, extra, cvec, w2, b2, w3, b3, y, pos_weight, int(denom), live)
+    return out[0], out[1]
+
+
+def decoder_loss_z(z, w_pq, b_pq, in_act, st, extra, cvec, w2, b2, w3, b3, y, pos_weight, denom):
+    _ready(st, _G.NEED_BY_DST | _G.NEED_RUNSUM | _G.NEED_PLAN_DST)
+    out = ops.decoder_loss_z(z, w_pq, b_pq, int(in_act), st._key_tensor, extra, cvec, w2, b2, w3, b3, y, pos_weight, int(denom))
     return out[0], out[1]
 
 
