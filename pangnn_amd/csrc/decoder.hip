@@ -73,9 +73,10 @@ __device__ __forceinline__ void stage_weights(const DecParams& a, float* Wl, flo
 
 // ---- gather the tile's 32 h1 rows into the wave's LDS image.  Returns w_e / validity per lane e.
 // FULL: all 32 edges exist (every tile but the last): no bounds predicate on the id loads.
-// max(x, 0), compiler-visible (not inline asm: an asm statement that defines a VGPR is invisible to the MFMA hazard
-// recognizer and may overwrite a source register of an in-flight MFMA — see decoder16.hip)
-__device__ __forceinline__ float relu1(float x) { return __builtin_amdgcn_fmed3f(x, 0.f, __builtin_inff()); }
+// relu as torch computes it: a NaN stays a NaN (fmaxf / fmed3f would return 0 and hide an overflow from a GradScaler).
+// Compiler-visible (not inline asm: an asm statement that defines a VGPR is invisible to the MFMA hazard recognizer and may
+// overwrite a source register of an in-flight MFMA — see decoder16.hip)
+__device__ __forceinline__ float relu1(float x) { return x < 0.f ? 0.f : x; }
 
 // 16-byte row piece at `table + byte_off`: uniform base pointer + 32-bit per-lane byte offset (node tables are
 // < 4 GiB, checked by the host wrapper) — `global_load_dwordx4 v, v_off, s[base]`, no 64-bit vector address
@@ -133,6 +134,9 @@ __device__ __forceinline__ void gather_tile(const DecParams& a, int64_t ebase, i
       h.y = relu1(pv[i].y);
       h.z = relu1(pv[i].z);
       h.w = relu1(pv[i].w);
+      // a row past the end of the list gathered node 0, which no edge may reference: its values (a NaN among them) must
+      // not reach the weight-gradient products, whose zero dL/dlogit would turn them into 0 * NaN
+      if (!FULL && ebase + row >= a.E) h = make_float4(0.f, 0.f, 0.f, 0.f);
       *reinterpret_cast<float4*>(Ht + swz4(row, c4)) = h;
     }
   }
@@ -257,10 +261,10 @@ __global__ __launch_bounds__(FWD_WAVES * 64) void decoder_fwd_kernel(DecParams a
         const int j0 = 32 * b + 8 * qd + 4 * hh;
         const float4 bb = *reinterpret_cast<const float4*>(b2l + j0);
         const float4 ww = *reinterpret_cast<const float4*>(w3l + j0);
-        part = fmaf(fmaxf(acc[b][4 * qd + 0] + bb.x, 0.f), ww.x, part);
-        part = fmaf(fmaxf(acc[b][4 * qd + 1] + bb.y, 0.f), ww.y, part);
-        part = fmaf(fmaxf(acc[b][4 * qd + 2] + bb.z, 0.f), ww.z, part);
-        part = fmaf(fmaxf(acc[b][4 * qd + 3] + bb.w, 0.f), ww.w, part);
+        part = fmaf(relu1(acc[b][4 * qd + 0] + bb.x), ww.x, part);
+        part = fmaf(relu1(acc[b][4 * qd + 1] + bb.y), ww.y, part);
+        part = fmaf(relu1(acc[b][4 * qd + 2] + bb.z), ww.z, part);
+        part = fmaf(relu1(acc[b][4 * qd + 3] + bb.w), ww.w, part);
       }
     part += __shfl_xor(part, 32);
     if (lane < 32 && ebase + lane < a.E) logits[ebase + lane] = part + b3;
@@ -362,10 +366,10 @@ __global__ __launch_bounds__(BWD_WAVES * 64) void decoder_bwd_kernel(
 #pragma unroll
           for (int c = 0; c < 4; ++c) {
             const int i = 4 * qd + c;
-            const float h2 = fmaxf(acc[b][i] + bbv[c], 0.f);
+            const float h2 = relu1(acc[b][i] + bbv[c]);
             part = fmaf(h2, wwv[c], part);
             Gt[(j0 + c) * GS + r] = h2;
-            acc[b][i] = h2 > 0.f ? wwv[c] : 0.f;
+            acc[b][i] = h2 <= 0.f ? 0.f : wwv[c];          // not `h2 > 0 ?`: a NaN h2 keeps its column on
           }
         }
       part += __shfl_xor(part, 32);                 // both halves of the wave now hold edge r's logit
@@ -407,7 +411,7 @@ __global__ __launch_bounds__(BWD_WAVES * 64) void decoder_bwd_kernel(
           for (int c = 0; c < 4; ++c) {
             const int i = 4 * qd + c;
             const float pre = acc[b][i] + bbv[c];
-            const bool on = pre > 0.f;
+            const bool on = !(pre <= 0.f);                // a NaN stays on, as in torch's relu backward
             acc[b][i] = on ? g_e * wwv[c] : 0.f;
             Gt[(j0 + c) * GS + r] = on ? pre : 0.f;
           }
@@ -441,7 +445,7 @@ __global__ __launch_bounds__(BWD_WAVES * 64) void decoder_bwd_kernel(
           const int e = jr(i, hh);
           const int k = r + 32 * bp;
           const float hval = Ht[swz(e, k)];
-          const float v = hval > 0.f ? acc2[bp][i] : 0.f;
+          const float v = hval <= 0.f ? 0.f : acc2[bp][i];
           if (full || ebase + e < a.E) __builtin_nontemporal_store(v, &gout[jr(i, 0) * DD + 32 * bp]);   // 19 GB written once
           acc2[bp][i] = v;
         }
@@ -460,8 +464,8 @@ __global__ __launch_bounds__(BWD_WAVES * 64) void decoder_bwd_kernel(
       const float ge = gl[e];
       const float x0 = Gt[r * GS + e];           // h2[j][e]
       const float x1 = Gt[(r + 32) * GS + e];
-      const float a0 = x0 > 0.f ? ge * w3j[0] : 0.f;
-      const float a1 = x1 > 0.f ? ge * w3j[1] : 0.f;
+      const float a0 = x0 <= 0.f ? 0.f : ge * w3j[0];
+      const float a1 = x1 <= 0.f ? 0.f : ge * w3j[1];
       gw3p[0] = fmaf(ge, x0, gw3p[0]);
       gw3p[1] = fmaf(ge, x1, gw3p[1]);
       gb2p[0] += a0;

@@ -23,6 +23,19 @@
 // fp32-level error (no two-term shortcuts).  No divergent control flow around matrix operands: the last tile is
 // padded by clamping edge ids to E-1 (dead lanes compute a duplicate whose dL/dlogit is forced to 0), so there is
 // ONE tile body, every lane is active in every MFMA / transposing LDS read, and only global stores are predicated.
+//
+// INVARIANT — the relus are held DOUBLED.  relu2x(x) = x + |x| = 2 relu(x) is the one-instruction relu through which a NaN of
+// either sign stays a NaN (see relu2x), so in the S and inference kernels the registers `h` (h1_frags) and `acc` after p1_logit
+// hold 2 h1 and 2 h2.  Every consumer takes the power of two out again, and a NEW consumer of `h` or `acc` must do the same:
+//   stage_weights16   P1's images are W2 / 2                         (2 h1 enters P1 only)
+//   p1_logit          logit = fma(sum_j 2 h2 w3, 0.5, b3)
+//   S kernel          g_half = g_e / 2 multiplies 2 h2 (dL/dw3 partials, gw3a) and 2 h1 (Hg, the dL/dW2 operand, write_hg)
+//   relu masks        m1 / m2 test "top half != 0", the same for x and 2 x (domain below)
+// Where the doubled form equals relu exactly: every scaling above is by a power of two, so results are bit-identical to the
+// relu(x) form as long as nothing leaves the normal range — h1, h2 <= FLT_MAX / 2 (above it 2 relu(x) is inf: an alarm relu
+// would not raise), the split terms of W2 / 2 and g_e / 2 normal (an entry of W2 or a dL/dlogit below 2^-125 loses its last
+// bit), and h2 outside [2^-134, 2^-133) (where the mask of 2 h2 is on and the mask of h2 was off).  And -inf: relu2x(-inf) =
+// -inf + inf = NaN where relu(-inf) = 0 (tests/test_nonfinite.py holds exactly that difference).
 #include "common.h"
 
 // This file is compiled TWICE (csrc/Makefile): as decoder16.o — everything, the 2-byte table format of the PQ16 instances being
@@ -123,12 +136,15 @@ __device__ __forceinline__ Split3 split8(const float (&f)[8]) {
 // source operand (write-after-read on an in-flight matrix instruction) — the later passes of the MFMA then see the
 // new value.  That is what made the round-1 kernel's "AGPR form" build intermittently wrong and what zeroed rows
 // 12-15 of this kernel's second product in its first version (tools/find_asm_mfma_war.py).
-// Written as an integer max of the bit pattern (negative floats are negative integers): one v_max_i32, without the
-// canonicalising v_max_f32(x, x) hipcc puts in front of a float max.
-__device__ __forceinline__ float relu1(float x) {
-  const int i = __builtin_bit_cast(int, x);
-  return __builtin_bit_cast(float, i > 0 ? i : 0);
-}
+// Written as x + |x| = 2 relu(x): ONE v_add_f32 (the |.| is a source modifier) through which a NaN of either sign stays a NaN,
+// as in torch's relu.  The integer max of the bit pattern this replaced (one v_max_i32) turned a NaN with the sign bit set —
+// what the matrix instructions hand on — into 0 and so hid an overflow from a GradScaler; a float max returns the other
+// operand for a quiet NaN; a compare + select is two instructions, 32 more per lane and half tile (+1.2 % of the step,
+// profiles/nonfinite.md).  The factor 2 is a power of two and is taken out again exactly where the value is consumed: P1 runs
+// on images of W2 / 2 (stage_weights16), the logit's w3 sum and the dL/dw3 and dL/dW2 operands take 1/2 with them — the
+// invariant and the exact domain of the identity are at the head of this file.  The stated difference: -inf gives
+// -inf + inf = NaN where relu gives 0 (an alarm torch would not raise).
+__device__ __forceinline__ float relu2x(float x) { return x + __builtin_fabsf(x); }
 
 // x + x[lane ^ 16] and x + x[lane ^ 32] as one swap + one add each (gfx950 v_permlane{16,32}_swap; the
 // clang builtin folds the two results of a swap of a value with itself, so the instruction is written out;
@@ -212,8 +228,10 @@ __device__ __forceinline__ void stage_weights16(const float* w2, const float* b2
     const int j = i >> 6, k = i & 63;
     const float w = w2[i];
     if (which & 1) {
-      const __bf16 h = (__bf16)w;
-      const float r1 = w - (float)h;
+      // P1 multiplies these images with 2 relu(h1) (relu2x): W2 / 2, an exact scaling of all three terms
+      const float wh = 0.5f * w;
+      const __bf16 h = (__bf16)wh;
+      const float r1 = wh - (float)h;
       const __bf16 m = (__bf16)r1;
       const __bf16 l = (__bf16)(r1 - (float)m);
       const int off = LDS_W2 + j * 128 + (((k >> 3) ^ wsw(j)) << 4) + 2 * (k & 7);
@@ -548,13 +566,13 @@ __device__ __forceinline__ float p1_logit(const char* lds, const float (&h)[2][8
     const f32x4 ww = *reinterpret_cast<const f32x4*>(w3l + 16 * jb + 4 * g);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      acc[jb][i] = relu1(acc[jb][i]);
+      acc[jb][i] = relu2x(acc[jb][i]);              // 2 h2: the caller's dL/dw3 takes g_e / 2, the mask bits are the same
       part = fmaf(acc[jb][i], ww[i], part);
     }
   }
-  return xsum32(xsum16(part)) + b3v;
+  return fmaf(xsum32(xsum16(part)), 0.5f, b3v);     // the sum of doubled terms is twice the sum, exactly
 }
-// h1 fragments from the gathered row pieces: h = relu(p + q (+ w_e c))
+// h1 fragments from the gathered row pieces: h = 2 relu(p + q (+ w_e c))  (relu2x)
 __device__ __forceinline__ void sum_rows(const HalfRowsT<false>& rows, float (&h)[2][8]) {
 #pragma unroll
   for (int ks = 0; ks < 2; ++ks)
@@ -599,7 +617,7 @@ __device__ __forceinline__ void h1_frags(const HalfRowsT<PQ16>& rows, bool has_e
 #pragma unroll
   for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-    for (int s = 0; s < 8; ++s) h[ks][s] = relu1(h[ks][s]);
+    for (int s = 0; s < 8; ++s) h[ks][s] = relu2x(h[ks][s]);       // 2 h1 (P1's images are W2 / 2)
 }
 
 template <bool FUSED_LOSS, bool RUNSUM, bool PQ16, bool EXTRA>
@@ -725,6 +743,7 @@ __global__ __launch_bounds__(S_WAVES * 64) void decoder_train16_kernel(
         g_e = live ? g_raw : 0.f;
       }
       gb3p += g_e;
+      const float g_half = 0.5f * g_e;                  // h1 and h2 are held doubled (relu2x)
       const int posc = min(pos, store_lim);
       if (FUSED_LOSS || logits != nullptr)                                // four lane groups, same value
         *reinterpret_cast<float*>(reinterpret_cast<char*>(logit_tile) + 4u * (uint32_t)posc) = xv;
@@ -739,8 +758,8 @@ __global__ __launch_bounds__(S_WAVES * 64) void decoder_train16_kernel(
 #pragma unroll
           for (int pr = 0; pr < 2; ++pr) {
             const float h2a = acc[jb][2 * pr], h2b = acc[jb][2 * pr + 1];
-            gw3a[jb][2 * pr] = fmaf(g_e, h2a, gw3a[jb][2 * pr]);
-            gw3a[jb][2 * pr + 1] = fmaf(g_e, h2b, gw3a[jb][2 * pr + 1]);
+            gw3a[jb][2 * pr] = fmaf(g_half, h2a, gw3a[jb][2 * pr]);            // (g_e / 2) (2 h2)
+            gw3a[jb][2 * pr + 1] = fmaf(g_half, h2b, gw3a[jb][2 * pr + 1]);
             // the pair as two 0/1 halves: top halves packed by one v_perm_b32, [!= 0] by one v_pk_min_u16 (h2 >= 0 after
             // the relu: its top half is non-zero exactly for a positive normal float)
             const uint32_t t2 = nz16x2(__builtin_amdgcn_perm(__builtin_bit_cast(uint32_t, h2b), __builtin_bit_cast(uint32_t, h2a),
@@ -765,7 +784,7 @@ __global__ __launch_bounds__(S_WAVES * 64) void decoder_train16_kernel(
       auto write_hg = [&](int ks) {
         float hg[8];
 #pragma unroll
-        for (int s = 0; s < 8; ++s) hg[s] = g_e * h[ks][s];
+        for (int s = 0; s < 8; ++s) hg[s] = g_half * h[ks][s];             // (g_e / 2) (2 h1)
         const Split3 sb = split8(hg);
         const int off = WV_HG + (ks ? hgw1 : hgw0);
         *reinterpret_cast<bf16x8*>(wv + off) = sb.hi;

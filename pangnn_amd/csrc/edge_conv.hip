@@ -52,7 +52,8 @@ __device__ __forceinline__ void wave_lds_sync() {
 // row of the 32x32 MFMA accumulator held in register r by a lane of half hh
 __device__ __forceinline__ constexpr int acc_row(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }
 
-__device__ __forceinline__ float relu1(float x) { return __builtin_amdgcn_fmed3f(x, 0.f, __builtin_inff()); }
+// relu as torch computes it: a NaN stays a NaN (fmed3f / fmaxf would return 0), so that the max-aggregation sees it
+__device__ __forceinline__ float relu1(float x) { return x < 0.f ? 0.f : x; }
 
 // does candidate (b, ib) replace (a, ia)?  Total order: NaN beats numbers, larger beats smaller, the smaller edge id wins ties.
 __device__ __forceinline__ bool better(float b, int ib, float a, int ia) {

@@ -181,8 +181,11 @@ __global__ __launch_bounds__(kBlock) void bce_kernel(const float* __restrict__ x
     const float t = expf(-ax);
     const float sp = log1pf(t) + fmaxf(-xv, 0.f);            // softplus(-x)
     acc += (1.f - yv) * xv + lw * sp;
-    const float sig_neg = xv >= 0.f ? t / (1.f + t) : 1.f / (1.f + t);   // sigmoid(-x)
-    g[i] = ((1.f - yv) - lw * sig_neg) * inv_denom;
+    // dl/dx through the SMALL sigmoid s = sigmoid(-|x|) on both sides: (1-y) - lw s for x >= 0, lw s - pw y for x < 0 (the same
+    // value, lw - 1 + y = pw y).  Written as (1-y) - lw / (1 + t), the negative side loses s below 2^-24 (x < -16.6, where
+    // 1 + t == 1): a label-0 edge then gets the gradient 0 instead of sigmoid(x).
+    const float sm = t / (1.f + t);
+    g[i] = (xv >= 0.f ? (1.f - yv) - lw * sm : lw * sm - pw * yv) * inv_denom;
   }
   acc = wave_sum(acc);
   if ((threadIdx.x & (kWave - 1)) == 0) red[threadIdx.x >> 6] = acc;
@@ -446,6 +449,8 @@ __global__ __launch_bounds__(kBlock) void softmax_qscore_kernel(const int64_t* _
     if (lane == 0) q[beg] = q_one;
     return;
   }
+  // (fmax drops a NaN score, the sum below does not: one NaN sends its whole segment through the nan_to_num branch, as the
+  // reference's logsumexp and the host leg's scatter_reduce(amax) do — tests/test_nonfinite.py)
   double mx = -INFINITY;
   for (int64_t i = beg + lane; i < end; i += kWave) mx = fmax(mx, score[i] / t);     // divide like the reference (t = 0.8 is not a binary fraction)
 #pragma unroll

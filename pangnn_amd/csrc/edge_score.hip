@@ -49,7 +49,7 @@ __global__ __launch_bounds__(kBlock) void score_norm_kernel(const char* __restri
     const float nrm = sqrtf(s);
     const float inv = 1.f / fmaxf(nrm, kScoreEps);
     norms[2 * node] = inv;
-    norms[2 * node + 1] = nrm > 0.f ? inv / nrm : 0.f;
+    norms[2 * node + 1] = nrm > 0.f ? inv / nrm : 0.f;       // (a NaN norm: the row's dot products and z_n itself carry the NaN on)
   }
 }
 
@@ -98,8 +98,8 @@ __global__ __launch_bounds__(kBlock) void edge_score_kernel(const char* __restri
           const float t = expf(-ax);
           const float sp = log1pf(t) + fmaxf(-x, 0.f);                      // softplus(-x)
           acc += (1.f - yv) * x + lw * sp;
-          const float sig_neg = x >= 0.f ? t / (1.f + t) : 1.f / (1.f + t);   // sigmoid(-x)
-          g_logits[kk] = ((1.f - yv) - lw * sig_neg) * inv_denom;
+          const float sm = t / (1.f + t);                                   // sigmoid(-|x|): bce_kernel's form of dl/dx
+          g_logits[kk] = (x >= 0.f ? (1.f - yv) - lw * sm : lw * sm - pw * yv) * inv_denom;
         }
       }
     }
@@ -232,7 +232,9 @@ __global__ __launch_bounds__(kBlock) void score_grad_kernel(const char* __restri
   score_combine<G>(acc, ds);
   if (sub != 0) return;
   float4 out = acc;
-  if (MODE == PANGNN_SCORE_COSINE) {
+  // a node without edges gets a zero row whatever its own row holds (0 * NaN would raise a false alarm in a GradScaler)
+  if (MODE == PANGNN_SCORE_COSINE &&
+      (src.rowptr[node + 1] > src.rowptr[node] || dst.rowptr[node + 1] > dst.rowptr[node])) {
     const float inv = norms[2 * node], k = norms[2 * node + 1] * ds;
     const float4 zn = score_piece(zb + (uint64_t)node * ldb, XF);
     out = make_float4(inv * acc.x - k * zn.x, inv * acc.y - k * zn.y, inv * acc.z - k * zn.z, inv * acc.w - k * zn.w);
