@@ -289,6 +289,40 @@ int pangnn_decoder_mlp_loss_f32(const float* p, int64_t ldp, const float* q, int
                                 size_t workspace_bytes, pangnn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The same fused link decoder for node_dim D in {32, 128} (csrc/decoder_nd.hip; `--node_dim`, src/setup.py:38): the
+ * strict-fp32 formulation above (every product on v_mfma_f32_32x32x2_f32, per-workgroup slabs summed in index order, no float
+ * atomics) with the width as a parameter.  Arguments, outputs, the part_buf / part_off layout (one 32-edge tile per chunk)
+ * and the order of the return codes are those of pangnn_decoder_mlp_fwd_f32 / _bwd_f32 / _loss_f32 without `precision`;
+ * p, q and g_h1 rows and the part rows are D floats wide, ldp / ldq >= D.  The launch grid follows the edge count alone, so
+ * a result does not depend on the device's size.  pangnn_decoder_nd_supported(D): 1 for 32 and 128, 0 for every other
+ * width, 64 included (that one stays with the entry points above, which keep rejecting D != 64); an unsupported D here:
+ * PANGNN_E_BADARG.  Workspace: pangnn_decoder_nd_bwd_workspace_bytes(D, num_edges) (0 for an unsupported D); its size is
+ * passed as an int64_t, like every other size of these entry points (a negative one: PANGNN_E_WORKSPACE).
+ * ---------------------------------------------------------------------------------------- */
+int pangnn_decoder_nd_supported(int32_t D);
+int pangnn_decoder_nd_fwd_f32(const float* p, int64_t ldp, const float* q, int64_t ldq, int64_t num_nodes,
+                              const int64_t* edge_index, int64_t ld, int64_t num_edges,
+                              const float* extra, const float* cvec, const float* w2, const float* b2,
+                              const float* w3, const float* b3, int32_t D, float* logits,
+                              pangnn_stream_t stream);
+size_t pangnn_decoder_nd_bwd_workspace_bytes(int32_t D, int64_t num_edges);
+int pangnn_decoder_nd_bwd_f32(const float* p, int64_t ldp, const float* q, int64_t ldq, int64_t num_nodes,
+                              const int64_t* edge_index, int64_t ld, int64_t num_edges,
+                              const float* extra, const float* cvec, const float* w2, const float* b2,
+                              const float* w3, const float* b3, int32_t D, const float* g_logits,
+                              float* g_h1, float* g_w2, float* g_b2, float* g_w3, float* g_b3,
+                              float* g_cvec, float* part_buf, const int32_t* part_off,
+                              void* workspace, int64_t workspace_bytes, pangnn_stream_t stream);
+int pangnn_decoder_nd_loss_f32(const float* p, int64_t ldp, const float* q, int64_t ldq, int64_t num_nodes,
+                               const int64_t* edge_index, int64_t ld, int64_t num_edges, const float* extra,
+                               const float* cvec, const float* w2, const float* b2, const float* w3,
+                               const float* b3, int32_t D, const float* y, const float* pos_weight,
+                               int64_t denom, float* logits, float* loss, float* g_h1, float* g_w2,
+                               float* g_b2, float* g_w3, float* g_b3, float* g_cvec, float* part_buf,
+                               const int32_t* part_off, void* workspace, int64_t workspace_bytes,
+                               pangnn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Two-wave-per-SIMD training decoder (csrc/decoder16.hip) — what `precision = 1` training uses.
  * Replaces forward + criterion + backward of src/gnn.py:171-177 / pangnn.py:200-207 with TWO passes and
  * no [E, D] tensor:

@@ -92,6 +92,18 @@ SIGNATURES = {
                                               _p, _p, _i64,                            # y, pos_weight, denom
                                               _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,  # logits .. part_off
                                               _i32, _p, _sz, _p]),
+    # the same decoder for node_dim 32 / 128 (csrc/decoder_nd.hip): the arguments above without `precision`
+    "pangnn_decoder_nd_supported": (C.c_int, [_i32]),
+    "pangnn_decoder_nd_fwd_f32": (C.c_int, [_p, _i64, _p, _i64, _i64, _p, _i64, _i64, _p, _p, _p, _p, _p, _p, _i32,
+                                            _p, _p]),
+    "pangnn_decoder_nd_bwd_workspace_bytes": (_sz, [_i32, _i64]),
+    "pangnn_decoder_nd_bwd_f32": (C.c_int, [_p, _i64, _p, _i64, _i64, _p, _i64, _i64, _p, _p, _p, _p, _p, _p, _i32,
+                                            _p, _p, _p, _p, _p, _p, _p, _p, _p,      # g_logits .. part_off
+                                            _p, _i64, _p]),                          # workspace, bytes (int64), stream
+    "pangnn_decoder_nd_loss_f32": (C.c_int, [_p, _i64, _p, _i64, _i64, _p, _i64, _i64, _p, _p, _p, _p, _p, _p, _i32,
+                                             _p, _p, _i64,                            # y, pos_weight, denom
+                                             _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,  # logits .. part_off
+                                             _p, _i64, _p]),
     "pangnn_softmax_qscore_f64": (C.c_int, [_p, _p, _i64, _i64, C.c_double, C.c_double, C.c_double, _p, _p]),
     # two-wave-per-SIMD training decoder (csrc/decoder16.hip): S kernel (+ by-source run sums, per-edge records)
     "pangnn_decoder_chunk_tiles": (C.c_int, []),

@@ -665,7 +665,7 @@ class DistAlternateGCN(AlternateGCN):
         self.overlap = os.environ.get("PANGNN_DIST_OVERLAP", "1") != "0"
         if self.flags.decoder != "mlp":
             raise NotImplementedError("partitioned mode implements the mlp decoder")
-        if isinstance(self.ops, HipOps) and not self._fused_width():
+        if isinstance(self.ops, HipOps) and self.mlp[2].in_features != 64:
             raise NotImplementedError("partitioned HIP decoder is built for node_dim 64")
 
     # structures / norms are per shard tensor and cached on the shard object

@@ -30,6 +30,9 @@ KERNEL_TIMER = None
 #     against fp64), 0.78x the time of mode 0 because f32 MFMA shares the SIMD's vector lanes;
 # 0 = v_mfma_f32_32x32x2_f32 everywhere (bit-exact fp32 FMA chains).  Environment: PANGNN_DECODER_PRECISION.
 DECODER_PRECISION = int(os.environ.get("PANGNN_DECODER_PRECISION", "1"))
+# node_dim other than 64 with fused per-edge MLP kernels (csrc/decoder_nd.hip): f32 MFMA in both precision modes, float32
+# P | Q rows, the autograd-Function (ctypes) route.  A width taken out of this tuple takes the layer-by-layer route again.
+DECODER_ND_WIDTHS = (32, 128)
 
 
 def _timer_start(tag):
@@ -642,7 +645,8 @@ def _decoder_operands(p, q, extra, cvec, w2, b2, w3, b3, y=None, pos_weight=None
     rows, or in mode 1 bfloat16 / float16 rows as stored (p and q stored differently: both as float32); `q=None`: `p` is
     one joint [N, 2D] table and comes back as its two column windows.  Everything else float32 and contiguous, pos_weight
     flattened."""
-    rows = _rows_any if DECODER_PRECISION == 1 else _rows_f32
+    d = p.shape[1] // 2 if q is None else p.shape[1]
+    rows = _rows_any if (DECODER_PRECISION == 1 and d not in DECODER_ND_WIDTHS) else _rows_f32
     if q is None:
         pq = rows(p)
         d = pq.shape[1] // 2
@@ -703,11 +707,64 @@ def _decoder_f32(p, q, st: EdgeStructure, ex, cv, w2, b2, w3, b3, y=None, pw=Non
     return loss, logits, gp, gq, g_cv, g_w2, g_b2, g_w3, g_b3
 
 
+def _decoder_nd(p, q, st: EdgeStructure, ex, cv, w2, b2, w3, b3, y=None, pw=None, denom=0, g_logits=None,
+                out_p=None, out_q=None, need_p=True, need_q=True, live=None):
+    """_decoder_f32 for the widths of DECODER_ND_WIDTHS (csrc/decoder_nd.hip), same arguments and result: one launch of
+    pangnn_decoder_nd_loss_f32 (y given) or pangnn_decoder_nd_bwd_f32 (the given dL/dlogits), then dL/dP by source (from the
+    per-run partial rows of a source-sorted list) and dL/dQ by target.  A padded batch (`live`) needs node_dim 64."""
+    if live is not None:
+        raise ValueError("live= (a padded fixed-shape batch) needs node_dim 64")
+    lib = _lib.load()
+    dev = p.device
+    e, d = st.num_edges, p.shape[1]
+    fused = y is not None
+    logits = torch.empty(e, dtype=torch.float32, device=dev) if fused else None
+    loss = torch.empty(1, dtype=torch.float32, device=dev) if fused else None
+    g_h1 = torch.empty(e, d, dtype=torch.float32, device=dev)
+    g_w2 = torch.empty_like(w2)
+    g_b2, g_w3, g_b3 = torch.empty_like(b2), torch.empty_like(w3), torch.empty_like(b3)
+    g_cv = None if cv is None else torch.empty_like(cv)
+    plan = st.runsum_plan() if (need_p and e > 0) else None
+    parts = None if plan is None else torch.empty(plan.n_parts, d, dtype=torch.float32, device=dev)
+    with _lib.device_guard(dev):
+        ws_bytes = lib.pangnn_decoder_nd_bwd_workspace_bytes(d, e)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        head = (p.data_ptr(), p.stride(0), q.data_ptr(), q.stride(0), max(p.shape[0], q.shape[0]),
+                st.edge_index.data_ptr(), e, e, _lib.ptr(ex), _lib.ptr(cv), w2.data_ptr(), b2.data_ptr(), w3.data_ptr(),
+                b3.data_ptr(), d)
+        tail = (_lib.ptr(g_h1), g_w2.data_ptr(), g_b2.data_ptr(), g_w3.data_ptr(), g_b3.data_ptr(), _lib.ptr(g_cv),
+                _lib.ptr(parts), None if plan is None else plan.part_off.data_ptr(), ws.data_ptr(), ws_bytes,
+                _lib.stream_ptr())
+        ev = _timer_start("dec.bwd")
+        if fused:
+            _lib.check(lib.pangnn_decoder_nd_loss_f32(*head, _lib.ptr(y), _lib.ptr(pw), int(denom), _lib.ptr(logits),
+                                                      loss.data_ptr(), *tail), "pangnn_decoder_nd_loss_f32")
+        else:
+            _lib.check(lib.pangnn_decoder_nd_bwd_f32(*head, _lib.ptr(g_logits), *tail), "pangnn_decoder_nd_bwd_f32")
+        _timer_stop("dec.bwd", ev)
+    gp = gq = None
+    if need_p:
+        if e == 0:
+            gp = (out_p if out_p is not None else torch.empty(p.shape[0], d, device=dev)).zero_()
+        elif plan is not None:     # per-run partial rows came out of the kernel: short contiguous sum
+            gp = _sum_parts(plan, parts, p.shape[0], out_p if out_p is not None else torch.empty(p.shape[0], d, device=dev))
+        else:
+            gp = segment_sum_rows(st.by_src, g_h1, 0, d, p.shape[0], out=out_p)
+    if need_q:
+        if e == 0:
+            gq = (out_q if out_q is not None else torch.empty(q.shape[0], d, device=dev)).zero_()
+        else:
+            gq = segment_sum_rows(st.by_dst, g_h1, 0, d, q.shape[0], out=out_q)
+    return loss, logits, gp, gq, g_cv, g_w2, g_b2, g_w3, g_b3
+
+
 def _decoder_grads(p, q, st: EdgeStructure, ex, cv, w2, b2, w3, b3, joint: bool, **kw):
-    """the training decoder of the current DECODER_PRECISION (_decoder_train16 / _decoder_f32) on normalised operands;
+    """the training decoder of the current DECODER_PRECISION (_decoder_train16 / _decoder_f32) on normalised operands, or
+    _decoder_nd in either mode at the widths of DECODER_ND_WIDTHS;
     `joint`: p and q are the column windows of one [N, 2D] table and dL/dP | dL/dQ come back as ONE [N, 2D] matrix in
     the gp slot (gq None).  Returns (loss, logits, gp, gq, g_cv, g_w2, g_b2, g_w3, g_b3)."""
-    train = _decoder_train16 if DECODER_PRECISION == 1 else _decoder_f32
+    train = _decoder_nd if p.shape[1] in DECODER_ND_WIDTHS else \
+        _decoder_train16 if DECODER_PRECISION == 1 else _decoder_f32
     if not joint:
         return train(p, q, st, ex, cv, w2, b2, w3, b3, **kw)
     d = p.shape[1]
@@ -732,7 +789,13 @@ class _DecoderMLP(torch.autograd.Function):
         logits = torch.empty(e, dtype=torch.float32, device=p.device)
         with _lib.device_guard(p.device):
             ev = _timer_start("dec.fwd")
-            if p.dtype in ROWS16:
+            if d in DECODER_ND_WIDTHS:
+                _lib.check(lib.pangnn_decoder_nd_fwd_f32(p.data_ptr(), p.stride(0), q.data_ptr(), q.stride(0),
+                                                         max(p.shape[0], q.shape[0]), st.edge_index.data_ptr(), e, e,
+                                                         _lib.ptr(ex), _lib.ptr(cv), w2.data_ptr(), b2.data_ptr(),
+                                                         w3.data_ptr(), b3.data_ptr(), d, _lib.ptr(logits),
+                                                         _lib.stream_ptr()), "pangnn_decoder_nd_fwd_f32")
+            elif p.dtype in ROWS16:
                 _lib.check(lib.pangnn_decoder_mlp_infer_mixed(p.data_ptr(), p.stride(0), q.data_ptr(), q.stride(0), _dt(p),
                                                               max(p.shape[0], q.shape[0]), st.edge_index.data_ptr(), e,
                                                               e, _lib.ptr(ex), _lib.ptr(cv), w2.data_ptr(),
@@ -774,7 +837,7 @@ def decoder_mlp(p, q, st: EdgeStructure, extra, cvec, w2, b2, w3, b3):
 def decoder_mlp_pq(pq, st: EdgeStructure, extra, cvec, w2, b2, w3, b3):
     """p = pq[:, :D], q = pq[:, D:] (one [N, 2D] node-level product)"""
     _lib.require_device(pq, extra, cvec, w2, b2, w3, b3)
-    if _via_ops(st, _timed_decoder()) and DECODER_PRECISION == 1:
+    if _via_ops(st, _timed_decoder()) and DECODER_PRECISION == 1 and pq.shape[1] // 2 not in DECODER_ND_WIDTHS:
         from . import torch_ops
         return torch_ops.decoder_mlp_pq(pq, st, extra, cvec, w2, b2, w3, b3)
     return _DecoderMLP.apply(pq, None, st, extra, cvec, w2, b2, w3, b3, True)
@@ -873,7 +936,7 @@ def decoder_loss_pq(pq, st, extra, cvec, w2, b2, w3, b3, y, pos_weight, denom, l
     """`live` (device int64[1]): a padded fixed-shape batch whose first live[0] edges are real (train.ReplayedFreshStep):
     the loss is their mean and the padding contributes to no gradient"""
     _lib.require_device(pq, extra, cvec, w2, b2, w3, b3, y, pos_weight, live)
-    if _via_ops(st, _timed_decoder()) and DECODER_PRECISION == 1:
+    if _via_ops(st, _timed_decoder()) and DECODER_PRECISION == 1 and pq.shape[1] // 2 not in DECODER_ND_WIDTHS:
         from . import torch_ops
         return torch_ops.decoder_loss_pq(pq, st, extra, cvec, w2, b2, w3, b3, y, pos_weight, denom, live)
     return _DecoderLoss.apply(pq, None, st, extra, cvec, w2, b2, w3, b3, y, pos_weight, denom, True, live)

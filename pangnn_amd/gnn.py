@@ -215,13 +215,16 @@ class AlternateGCN(nn.Module):
         return self.activation_fct(h) if pending else h
 
     def _fused_width(self) -> bool:
-        """node_dim is the one width the fused per-edge MLP kernels are built for (csrc/decoder_mlp.hip)"""
-        return self.mlp[2].in_features == 64
+        """node_dim is a width the fused per-edge MLP kernels are built for: 64 (csrc/decoder.hip, decoder16.hip) or one of
+        PF.DECODER_ND_WIDTHS (csrc/decoder_nd.hip: f32 matrix pipe, float32 P | Q rows, no DeferredLogits)"""
+        d = self.mlp[2].in_features
+        return d == 64 or d in PF.DECODER_ND_WIDTHS
 
     def _decoder16(self) -> bool:
-        """the fused kernels run in their default precision mode: the one-pass training decoder is functional._decoder_train16
-        and P | Q rows are read as stored, so under bf16 / fp16 autocast they may be stored in the autocast type"""
-        return self._fused_width() and PF.DECODER_PRECISION == 1
+        """the fused kernels run in their default precision mode at node_dim 64: the one-pass training decoder is
+        functional._decoder_train16 and P | Q rows are read as stored, so under bf16 / fp16 autocast they may be stored in the
+        autocast type"""
+        return self.mlp[2].in_features == 64 and PF.DECODER_PRECISION == 1
 
     def _skip_feature(self, graph):
         """the per-edge input of `--skip_connections` (gnn.py:173), else None"""
@@ -263,12 +266,13 @@ class AlternateGCN(nn.Module):
 
     def loss_and_logits(self, graph, labels, pos_weight=None):
         """`criterion(model(graph), labels)` (pangnn.py:200-203) as ONE decoder pass when the fused kernel
-        applies (mlp decoder, node_dim 64): returns (loss, detached logits).  Falls back to forward +
+        applies (mlp decoder, node_dim 64, 32 or 128): returns (loss, detached logits).  Falls back to forward +
         criterion otherwise.  `model(graph)` followed by torch's / this package's BCEWithLogitsLoss reaches the same pass
         through the handle `forward` returns in training mode (deferred.DeferredLogits)."""
         from .train import criterion
         ops, z = self._fused_decoder_operands(graph)
-        if ops is not None:
+        padded = getattr(graph, "live_edges", None) is not None
+        if ops is not None and not (padded and self.mlp[2].in_features != 64):
             pq, st, extra, cvec, layer = ops
             if layer is not None:
                 return PF.decoder_loss_z(*layer, st, extra, cvec, self.mlp[2].weight, self.mlp[2].bias,
