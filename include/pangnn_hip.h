@@ -265,6 +265,8 @@ int pangnn_decoder_mlp_infer_f32(const float* p, int64_t ldp, const float* q, in
                                  const float* extra, const float* cvec, const float* w2, const float* b2,
                                  const float* w3, const float* b3, int32_t D, float* logits,
                                  int32_t precision, pangnn_stream_t stream);
+/* one slab per workgroup of the launch over `num_edges` edges; the grid follows the edge count alone (at most 256), as for
+ * the other widths of csrc/decoder.hip's template below */
 size_t pangnn_decoder_mlp_bwd_workspace_bytes(int64_t num_edges);
 int pangnn_decoder_mlp_bwd_f32(const float* p, int64_t ldp, const float* q, int64_t ldq, int64_t num_nodes,
                                const int64_t* edge_index, int64_t ld, int64_t num_edges,
@@ -289,9 +291,10 @@ int pangnn_decoder_mlp_loss_f32(const float* p, int64_t ldp, const float* q, int
                                 size_t workspace_bytes, pangnn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
- * The same fused link decoder for node_dim D in {32, 128} (csrc/decoder_nd.hip; `--node_dim`, src/setup.py:38): the
- * strict-fp32 formulation above (every product on v_mfma_f32_32x32x2_f32, per-workgroup slabs summed in index order, no float
- * atomics) with the width as a parameter.  Arguments, outputs, the part_buf / part_off layout (one 32-edge tile per chunk)
+ * The same fused link decoder for node_dim D in {32, 128} (`--node_dim`, src/setup.py:38): two more instances of the width
+ * template in csrc/decoder.hip that the entry points above run at D = 64 with precision 0, i.e. the strict-fp32 formulation
+ * above (every product on v_mfma_f32_32x32x2_f32, per-workgroup slabs summed in index order, no float atomics) with the
+ * width as a parameter.  Arguments, outputs, the part_buf / part_off layout (one 32-edge tile per chunk)
  * and the order of the return codes are those of pangnn_decoder_mlp_fwd_f32 / _bwd_f32 / _loss_f32 without `precision`;
  * p, q and g_h1 rows and the part rows are D floats wide, ldp / ldq >= D.  The launch grid follows the edge count alone, so
  * a result does not depend on the device's size.  pangnn_decoder_nd_supported(D): 1 for 32 and 128, 0 for every other

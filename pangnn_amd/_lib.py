@@ -92,7 +92,7 @@ SIGNATURES = {
                                               _p, _p, _i64,                            # y, pos_weight, denom
                                               _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,  # logits .. part_off
                                               _i32, _p, _sz, _p]),
-    # the same decoder for node_dim 32 / 128 (csrc/decoder_nd.hip): the arguments above without `precision`
+    # the same decoder for node_dim 32 / 128 (the same template of csrc/decoder.hip): the arguments above without `precision`
     "pangnn_decoder_nd_supported": (C.c_int, [_i32]),
     "pangnn_decoder_nd_fwd_f32": (C.c_int, [_p, _i64, _p, _i64, _i64, _p, _i64, _i64, _p, _p, _p, _p, _p, _p, _i32,
                                             _p, _p]),

@@ -1,23 +1,33 @@
-// Fused link decoder for D = 64 (src/gnn.py:110-116,171-177), fp32, gfx950.
+// Fused link decoder for node_dim D in {32, 64, 128} (src/setup.py:38, src/gnn.py:110-116,171-177), fp32, gfx950.
 //
-//   h1[e]   = relu(P[src_e] + Q[dst_e] (+ w_e * c))         P = z W1a^T, Q = z W1b^T + b1  (node level)
+//   h1[e]   = relu((P[src_e] + Q[dst_e]) (+ w_e * c))        P = z W1a^T, Q = z W1b^T + b1  (node level)
 //   h2[e]   = relu(W2 h1[e] + b2)
 //   logit_e = w3 . h2[e] + b3
 //
-// One wavefront owns a tile of 32 consecutive edges (caller's edge order, so logits are written
-// coalesced and no permutation is needed).  The 32 x 64 h1 tile is gathered with row-contiguous
-// 16-byte loads (16 lanes per 256-B node row, 4 rows per wave-instruction) into a padded LDS
-// image and multiplied with W2 (LDS resident, loaded once per workgroup) on the f32 MFMA
-// (v_mfma_f32_32x32x2_f32: exact fp32 FMA chains, so results match an fp32 reference to rounding).
-// The product is oriented C[j][e] = sum_k W2[j][k] h1[e][k] (A = W2, B = h1^T): the edge index stays
-// on the lane, so bias + relu + the dot with w3 are in-lane and one xor-32 shuffle finishes a logit.
+// One wavefront owns a tile of 32 consecutive edges (caller's edge order, so logits are written coalesced and no
+// permutation is needed).  The 32 x D h1 tile is gathered with row-contiguous 16-byte loads (D / 4 lanes per node row)
+// into a padded LDS image and multiplied with W2 (LDS resident, loaded once per workgroup) on the f32 MFMA
+// (v_mfma_f32_32x32x2_f32: exact, k-ordered fp32 FMA chains, so results match an fp32 reference to rounding).  The product
+// is oriented C[j][e] = sum_k W2[j][k] h1[e][k] (A = W2, B = h1^T): the edge index stays on the lane, so bias + relu + the
+// dot with w3 are in-lane and one xor-32 shuffle finishes a logit.
 //
-// Backward recomputes the forward per tile and chains three more MFMA products without leaving the
-// CU:  G = dL/dh2pre (in the accumulator registers of the first product, used directly as the A
-// operand of the second), gH1 = G^T W2 (written out as dL/dh1pre [E,64]), gW2 += G h1 (operands
-// re-read from LDS).  Parameter gradients are accumulated in registers across all tiles of a wave,
-// reduced over the workgroup's waves in a fixed order and written as one partial slab per workgroup;
-// a second tiny kernel sums the slabs in index order => bitwise reproducible, no float atomics.
+// Backward recomputes the forward per tile and chains two more MFMA products without leaving the CU: gW2 += G h1 with
+// G = dL/dh2pre rebuilt from the h2 rows staged through LDS (the accumulator layout has the edge on the lane, this product
+// wants the output j there), and gH1 = G^T W2 with G in the accumulator registers of the first product, used directly as
+// the A operand (written out as dL/dh1pre [E, D]).  Parameter gradients are accumulated in registers across all tiles of
+// a wave, reduced over the workgroup's waves in a fixed order and written as one partial slab per workgroup; a second
+// tiny kernel sums the slabs in index order => bitwise reproducible, no float atomics.  One forward kernel, one backward
+// kernel <D, FUSED_LOSS, RUNSUM>, one reduce kernel.
+//
+// What the width changes:
+//   D = 32   8 waves per workgroup; everything is one 32 x 32 block.
+//   D = 64   8 waves per workgroup, 2 x 2 blocks; the strict-fp32 mode (precision 0) of the default width, whose
+//            default-mode kernels are decoder16.hip.
+//   D = 128  the padded W2 image alone is 128 x 132 x 4 B = 66 KiB, so a workgroup has 4 waves (one per SIMD), each with a
+//            32 x 132 h1 tile.  dL/dW2 is 16 blocks of 32 x 32: 256 accumulator registers per lane if one wave held it
+//            all, every AGPR there is, so the backward's four waves own four blocks each and exchange the h2 slices (see
+//            the kernel).
+// The launch grid is a function of the edge count alone (never of the device), so a result does not depend on it.
 #include "common.h"
 
 #include <type_traits>
@@ -26,18 +36,32 @@ namespace pangnn {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-constexpr int DD = 64;        // decoder width (node_dim)
-constexpr int TE = 32;        // edges per wave tile
-constexpr int GS = 33;        // row stride of the G tile (floats): conflict-free column reads
-constexpr int SLAB = 64 * 64 + 64 + 64 + 64 + 16;   // gW2 | gb2 | gw3 | gcvec | gb3(+pad)
+constexpr int TE = 32;          // edges per wave tile
+constexpr int GS = 33;          // row stride of the staged h2 slice (floats): conflict-free column reads
+constexpr int kMaxGrid = 256;   // workgroups at most (one per CU of an MI355X); fixed, so slabs and sums do not follow the device
+constexpr int SLAB16 = 64 * 64 + 64 + 64 + 64 + 16;   // slab stride of decoder16.hip's training kernel (same layout, padded)
 
-// LDS images of W2 [64][64] and of the h1 tile [32][64] use a padded row stride of 68 floats
-// (272 B): 16-byte aligned, ds_read_b128 down a column of rows is conflict-free (bank = 4*row + 4*k4
-// mod 64 is distinct over each 16-lane service group), row-wise b32/b128 accesses are contiguous, and
-// every address is `lane base + compile-time offset` (an XOR swizzle costs a VGPR per address).
-constexpr int RS = 68;
-__device__ __forceinline__ constexpr int swz(int row, int k) { return row * RS + k; }
-__device__ __forceinline__ constexpr int swz4(int row, int k4) { return row * RS + 4 * k4; }
+template <int D>
+struct Shape {
+  static_assert(D == 32 || D == 64 || D == 128, "decoder.hip is built for node_dim 32, 64 and 128");
+  static constexpr int NB = D / 32;                 // 32-wide blocks per dimension
+  // padded row stride of the W2 and h1 images (floats): 16-byte aligned rows, and RS mod 64 in {36, 4} = 4 * odd, so a
+  // ds_read_b128 down a column of 16 rows touches 16 distinct groups of four banks; row-wise b32 / b128 accesses are
+  // contiguous, and every address is `lane base + compile-time offset` (an XOR swizzle costs a VGPR per address)
+  static constexpr int RS = D + 4;
+  static constexpr int WAVES = D == 128 ? 4 : 8;
+  static constexpr bool COOP = D == 128;            // the backward's waves share dL/dW2 out among them (see the kernel)
+  static constexpr int WGRAD_UNROLL = D == 32 ? 16 : 4;   // D >= 64: a loop of four rounds, for the registers' sake
+  static constexpr int LPR = D / 4;                 // lanes that cover one node row with 16-byte pieces
+  static constexpr int RPI = 64 / LPR;              // rows per wave-wide load instruction
+  static constexpr int NI = TE / RPI;               // load instructions per table and tile
+  static constexpr int SLAB = D * D + 3 * D + 2;    // gW2 | gb2 | gw3 | gcvec | gb3 | loss
+  static constexpr int FWD_LDS = D * RS + 3 * D + WAVES * TE * RS;
+  static constexpr int PER_WAVE = TE * RS + 32 * GS + 64;   // h1 tile | h2 slice | w_e | g_e
+  static constexpr int BWD_LDS = D * RS + 3 * D + WAVES * PER_WAVE;
+  static_assert(BWD_LDS * 4 <= 160 * 1024 && FWD_LDS * 4 <= 160 * 1024, "LDS budget of one CU");
+  static_assert(SLAB <= WAVES * PER_WAVE, "the slab is reduced in the tile area");
+};
 
 __device__ __forceinline__ void wave_lds_sync() {
   // LDS operations of one wave execute in issue order; this only pins the compiler's ordering.
@@ -57,78 +81,81 @@ struct DecParams {
 };
 
 // ---- stage W2 / b2 / w3 (/ cvec) into LDS, once per workgroup
-__device__ __forceinline__ void stage_weights(const DecParams& a, float* Wl, float* b2l, float* w3l,
-                                              float* cvl, int nthreads) {
-  for (int i = threadIdx.x; i < 64 * 16; i += nthreads) {
-    const int j = i >> 4, k4 = i & 15;
+template <int D>
+__device__ __forceinline__ void stage_weights(const DecParams& a, float* Wl, float* b2l, float* w3l, float* cvl) {
+  using S = Shape<D>;
+  for (int i = threadIdx.x; i < D * (D / 4); i += S::WAVES * 64) {
+    const int j = i / (D / 4), k4 = i % (D / 4);
     const float4 v = reinterpret_cast<const float4*>(a.w2)[i];
-    *reinterpret_cast<float4*>(Wl + swz4(j, k4)) = v;
+    *reinterpret_cast<float4*>(Wl + j * S::RS + 4 * k4) = v;
   }
-  for (int i = threadIdx.x; i < 64; i += nthreads) {
+  for (int i = threadIdx.x; i < D; i += S::WAVES * 64) {
     b2l[i] = a.b2[i];
     w3l[i] = a.w3[i];
     cvl[i] = a.cvec ? a.cvec[i] : 0.f;
   }
 }
 
-// ---- gather the tile's 32 h1 rows into the wave's LDS image.  Returns w_e / validity per lane e.
-// FULL: all 32 edges exist (every tile but the last): no bounds predicate on the id loads.
 // relu as torch computes it: a NaN stays a NaN (fmaxf / fmed3f would return 0 and hide an overflow from a GradScaler).
 // Compiler-visible (not inline asm: an asm statement that defines a VGPR is invisible to the MFMA hazard recognizer and may
 // overwrite a source register of an in-flight MFMA — see decoder16.hip)
 __device__ __forceinline__ float relu1(float x) { return x < 0.f ? 0.f : x; }
 
-// 16-byte row piece at `table + byte_off`: uniform base pointer + 32-bit per-lane byte offset (node tables are
-// < 4 GiB, checked by the host wrapper) — `global_load_dwordx4 v, v_off, s[base]`, no 64-bit vector address
+// 16-byte row piece at `table + byte_off`: uniform base pointer + 32-bit per-lane byte offset (node tables are < 4 GiB,
+// checked by the host wrapper) — `global_load_dwordx4 v, v_off, s[base]`, no 64-bit vector address
 __device__ __forceinline__ float4 ld_row16(const float* table, uint32_t byte_off) {
   return *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(table) + byte_off);
 }
 
-template <bool FULL = false>
-__device__ __forceinline__ void gather_tile(const DecParams& a, int64_t ebase, int lane, float* Ht,
-                                            const float* cvl, float& w_e, int& id) {
+// ---- gather the tile's 32 h1 rows into the wave's LDS image.  Returns w_e / the node id per lane (lanes 0-31: source of
+// edge `lane`, 32-63: target of edge `lane - 32`).  FULL: all 32 edges exist, no bounds predicate on the id loads.
+template <int D, bool FULL>
+__device__ __forceinline__ void gather_tile(const DecParams& a, int64_t ebase, int lane, float* Ht, const float* cvl,
+                                            float& w_e, int& id) {
+  using S = Shape<D>;
   const int64_t e = ebase + (lane & 31);
   id = 0;
   w_e = 0.f;
   if (FULL || e < a.E) {
-    id = (int)a.ei[(int64_t)(lane >> 5) * a.ld + e];     // lanes 0-31: source, 32-63: target
+    id = (int)a.ei[(int64_t)(lane >> 5) * a.ld + e];
     if (a.extra && lane < 32) w_e = a.extra[e];
   }
-  const int c4 = lane & 15, r4 = lane >> 4;
-  // byte offset of this lane's node row in its table (P for the source half, Q for the target half): one
-  // multiply per lane and tile; the 16 row gathers below shuffle the finished offset instead of the id
+  const int c4 = lane % S::LPR, r4 = lane / S::LPR;
+  // byte offset of this lane's node row in its table (P for the source half, Q for the target half): one multiply per
+  // lane and tile; the row gathers below shuffle the finished offset instead of the id
   const uint32_t row_off = (uint32_t)id * ((lane >> 5) ? a.ldq4 : a.ldp4) * 16u;
   const uint32_t col_off = 16u * c4;
   const bool has_extra = a.extra != nullptr;             // uniform: the w_e * c term only exists with skip connections
   float4 cv = make_float4(0.f, 0.f, 0.f, 0.f);
   if (has_extra) cv = reinterpret_cast<const float4*>(cvl)[c4];
-#pragma unroll
-  for (int half = 0; half < 2; ++half) {
+  // a real loop at D = 128 (four rounds of eight loads): unrolled, the scheduler issues all 32 loads first and the kernel
+  // runs out of registers
+#pragma unroll 1
+  for (int g = 0; g < S::NI / 4; ++g) {
     float4 pv[4], qv[4];
-    float wv[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const int row = 4 * (4 * half + i) + r4;
+      const int row = S::RPI * (4 * g + i) + r4;
       pv[i] = ld_row16(a.p, (uint32_t)__shfl((int)row_off, row) + col_off);
       qv[i] = ld_row16(a.q, (uint32_t)__shfl((int)row_off, 32 + row) + col_off);
     }
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {                         // same association as the forward kernel: (p + q) + w c
+    for (int i = 0; i < 4; ++i) {                         // (p + q) + w c, in that association
       pv[i].x += qv[i].x; pv[i].y += qv[i].y; pv[i].z += qv[i].z; pv[i].w += qv[i].w;
     }
     if (has_extra) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        wv[i] = __shfl(w_e, 4 * (4 * half + i) + r4);
-        pv[i].x = fmaf(wv[i], cv.x, pv[i].x);
-        pv[i].y = fmaf(wv[i], cv.y, pv[i].y);
-        pv[i].z = fmaf(wv[i], cv.z, pv[i].z);
-        pv[i].w = fmaf(wv[i], cv.w, pv[i].w);
+        const float wv = __shfl(w_e, S::RPI * (4 * g + i) + r4);
+        pv[i].x = fmaf(wv, cv.x, pv[i].x);
+        pv[i].y = fmaf(wv, cv.y, pv[i].y);
+        pv[i].z = fmaf(wv, cv.z, pv[i].z);
+        pv[i].w = fmaf(wv, cv.w, pv[i].w);
       }
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const int row = 4 * (4 * half + i) + r4;
+      const int row = S::RPI * (4 * g + i) + r4;
       float4 h;
       h.x = relu1(pv[i].x);
       h.y = relu1(pv[i].y);
@@ -137,42 +164,67 @@ __device__ __forceinline__ void gather_tile(const DecParams& a, int64_t ebase, i
       // a row past the end of the list gathered node 0, which no edge may reference: its values (a NaN among them) must
       // not reach the weight-gradient products, whose zero dL/dlogit would turn them into 0 * NaN
       if (!FULL && ebase + row >= a.E) h = make_float4(0.f, 0.f, 0.f, 0.f);
-      *reinterpret_cast<float4*>(Ht + swz4(row, c4)) = h;
+      *reinterpret_cast<float4*>(Ht + row * S::RS + 4 * c4) = h;
     }
   }
 }
 
-// ---- C[j][e] = sum_k W2[j][k] h1[e][k]; lane (e = lane&31, hh = lane>>5) gets rows jr(r,hh)+32b
-__device__ __forceinline__ void gemm1(const float* Wl, const float* Ht, int lane, f32x16 (&acc)[2]) {
+// ---- C[j][e] = sum_k W2[j][k] h1[e][k]; lane (e = lane&31, hh = lane>>5) gets rows jr(i,hh) + 32b in acc[b][i].
+// Half hh of the wave feeds k = (D/2) hh + 0 .. D/2 - 1, one k of each half per instruction.
+template <int D>
+__device__ __forceinline__ void gemm1(const float* Wl, const float* Ht, int lane, f32x16 (&acc)[Shape<D>::NB]) {
+  using S = Shape<D>;
   const int r = lane & 31, h = lane >> 5;
 #pragma unroll
-  for (int b = 0; b < 2; ++b)
+  for (int b = 0; b < S::NB; ++b)
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[b][i] = 0.f;
+#pragma unroll 4
+  for (int i = 0; i < D / 8; ++i) {                        // D = 128: four rounds of four steps, for the registers' sake
+    const int k4 = (D / 8) * h + i;
+    const float4 bf = *reinterpret_cast<const float4*>(Ht + r * S::RS + 4 * k4);
+    float4 af[S::NB];
 #pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int k4 = 8 * h + i;
-    const float4 bf = *reinterpret_cast<const float4*>(Ht + swz4(r, k4));
-    const float4 a0 = *reinterpret_cast<const float4*>(Wl + swz4(r, k4));
-    const float4 a1 = *reinterpret_cast<const float4*>(Wl + swz4(r + 32, k4));
-    acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.x, bf.x, acc[0], 0, 0, 0);
-    acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.x, bf.x, acc[1], 0, 0, 0);
-    acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.y, bf.y, acc[0], 0, 0, 0);
-    acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.y, bf.y, acc[1], 0, 0, 0);
-    acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.z, bf.z, acc[0], 0, 0, 0);
-    acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.z, bf.z, acc[1], 0, 0, 0);
-    acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.w, bf.w, acc[0], 0, 0, 0);
-    acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.w, bf.w, acc[1], 0, 0, 0);
+    for (int b = 0; b < S::NB; ++b) af[b] = *reinterpret_cast<const float4*>(Wl + (r + 32 * b) * S::RS + 4 * k4);
+#pragma unroll
+    for (int b = 0; b < S::NB; ++b) acc[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[b].x, bf.x, acc[b], 0, 0, 0);
+#pragma unroll
+    for (int b = 0; b < S::NB; ++b) acc[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[b].y, bf.y, acc[b], 0, 0, 0);
+#pragma unroll
+    for (int b = 0; b < S::NB; ++b) acc[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[b].z, bf.z, acc[b], 0, 0, 0);
+#pragma unroll
+    for (int b = 0; b < S::NB; ++b) acc[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[b].w, bf.w, acc[b], 0, 0, 0);
   }
 }
 
-constexpr int FWD_WAVES = 8;    // 512 threads, 1 workgroup / CU, 2 waves / SIMD (prefetch registers)
-constexpr int BWD_WAVES = 8;    // 512 threads, 1 workgroup / CU, 2 waves / SIMD
+// ---- h2 = relu(C + b2) in place in the accumulators; returns this half's part of w3 . h2 (same order of additions in the
+// forward and in the training kernel, so their logits are the same bits)
+template <int D>
+__device__ __forceinline__ float layer2_epilogue(const float* b2l, const float* w3l, int hh, f32x16 (&acc)[Shape<D>::NB]) {
+  float part = 0.f;
+#pragma unroll
+  for (int b = 0; b < Shape<D>::NB; ++b)
+#pragma unroll
+    for (int qd = 0; qd < 4; ++qd) {
+      const int j0 = 32 * b + 8 * qd + 4 * hh;
+      const float4 bb = *reinterpret_cast<const float4*>(b2l + j0);
+      const float4 ww = *reinterpret_cast<const float4*>(w3l + j0);
+      const float bbv[4] = {bb.x, bb.y, bb.z, bb.w};
+      const float wwv[4] = {ww.x, ww.y, ww.z, ww.w};
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const float h2 = relu1(acc[b][4 * qd + c] + bbv[c]);
+        part = fmaf(h2, wwv[c], part);
+        acc[b][4 * qd + c] = h2;
+      }
+    }
+  return part;
+}
 
-// ---- software-pipelined gather: edge ids two tiles ahead, node rows one tile ahead, so a wave never
-// waits on HBM between two MFMA phases (the rows of tile t+1 land while tile t is in the matrix pipe).
+// ---- software-pipelined gather of the forward kernel: edge ids two tiles ahead, node rows one tile ahead, so a wave never
+// waits on HBM between two MFMA phases (the rows of tile t+1 land while tile t is in the matrix pipe)
 struct TileIds { int id; float w_e; uint32_t row_off; };     // row_off: byte offset of the lane's node row in P / Q
-struct TileRows { float4 pv[8]; float4 qv[8]; float wv[8]; };
+template <int D> struct TileRows { float4 pv[Shape<D>::NI]; float4 qv[Shape<D>::NI]; float wv[Shape<D>::NI]; };
 
 __device__ __forceinline__ TileIds load_ids(const DecParams& a, int64_t tile, int64_t n_tiles, int lane) {
   TileIds t;
@@ -187,28 +239,32 @@ __device__ __forceinline__ TileIds load_ids(const DecParams& a, int64_t tile, in
   return t;
 }
 
-__device__ __forceinline__ void issue_rows(const DecParams& a, const TileIds& t, int lane, TileRows& rw) {
-  const int r4 = lane >> 4;
-  const uint32_t col_off = 16u * (lane & 15);
+template <int D>
+__device__ __forceinline__ void issue_rows(const DecParams& a, const TileIds& t, int lane, TileRows<D>& rw) {
+  using S = Shape<D>;
+  const int r4 = lane / S::LPR;
+  const uint32_t col_off = 16u * (lane % S::LPR);
   const bool has_extra = a.extra != nullptr;
 #pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int row = 4 * i + r4;
+  for (int i = 0; i < S::NI; ++i) {
+    const int row = S::RPI * i + r4;
     rw.wv[i] = has_extra ? __shfl(t.w_e, row) : 0.f;
     rw.pv[i] = ld_row16(a.p, (uint32_t)__shfl((int)t.row_off, row) + col_off);
     rw.qv[i] = ld_row16(a.q, (uint32_t)__shfl((int)t.row_off, 32 + row) + col_off);
   }
 }
 
-__device__ __forceinline__ void commit_rows(const DecParams& a, const TileRows& rw, int lane, const float* cvl,
+template <int D>
+__device__ __forceinline__ void commit_rows(const DecParams& a, const TileRows<D>& rw, int lane, const float* cvl,
                                             float* Ht) {
-  const int c4 = lane & 15, r4 = lane >> 4;
+  using S = Shape<D>;
+  const int c4 = lane % S::LPR, r4 = lane / S::LPR;
   const bool has_extra = a.extra != nullptr;
   float4 cv = make_float4(0.f, 0.f, 0.f, 0.f);
   if (has_extra) cv = reinterpret_cast<const float4*>(cvl)[c4];
 #pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int row = 4 * i + r4;
+  for (int i = 0; i < S::NI; ++i) {
+    const int row = S::RPI * i + r4;
     float4 h;
     h.x = rw.pv[i].x + rw.qv[i].x;
     h.y = rw.pv[i].y + rw.qv[i].y;
@@ -221,119 +277,145 @@ __device__ __forceinline__ void commit_rows(const DecParams& a, const TileRows& 
       h.w = fmaf(rw.wv[i], cv.w, h.w);
     }
     h.x = relu1(h.x); h.y = relu1(h.y); h.z = relu1(h.z); h.w = relu1(h.w);
-    *reinterpret_cast<float4*>(Ht + swz4(row, c4)) = h;
+    *reinterpret_cast<float4*>(Ht + row * S::RS + 4 * c4) = h;
   }
 }
 
-__global__ __launch_bounds__(FWD_WAVES * 64) void decoder_fwd_kernel(DecParams a, float* __restrict__ logits,
-                                                                    int64_t n_tiles) {
-  __shared__ __attribute__((aligned(16))) float lds[64 * RS + 3 * 64 + FWD_WAVES * TE * RS];
+template <int D>
+__global__ __launch_bounds__(Shape<D>::WAVES * 64) void decoder_fwd_kernel(DecParams a, float* __restrict__ logits,
+                                                                          int64_t n_tiles) {
+  using S = Shape<D>;
+  __shared__ __attribute__((aligned(16))) float lds[S::FWD_LDS];
   float* Wl = lds;
-  float* b2l = lds + 64 * RS;
-  float* w3l = b2l + 64;
-  float* cvl = w3l + 64;
+  float* b2l = lds + D * S::RS;
+  float* w3l = b2l + D;
+  float* cvl = w3l + D;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;   // SGPR: tile index and its addresses stay scalar
-  float* Ht = cvl + 64 + wave * (TE * RS);
-  stage_weights(a, Wl, b2l, w3l, cvl, FWD_WAVES * 64);
+  float* Ht = cvl + D + wave * (TE * S::RS);
+  stage_weights<D>(a, Wl, b2l, w3l, cvl);
   __syncthreads();
   const float b3 = a.b3[0];
   const int hh = lane >> 5;
-  const int64_t stride = (int64_t)gridDim.x * FWD_WAVES;
-  int64_t tile = (int64_t)blockIdx.x * FWD_WAVES + wave;
+  const int64_t stride = (int64_t)gridDim.x * S::WAVES;
+  int64_t tile = (int64_t)blockIdx.x * S::WAVES + wave;
   TileIds cur = load_ids(a, tile, n_tiles, lane);
   TileIds nxt = load_ids(a, tile + stride, n_tiles, lane);
-  TileRows rw;
-  issue_rows(a, cur, lane, rw);
+  TileRows<D> rw;
+  issue_rows<D>(a, cur, lane, rw);
   for (; tile < n_tiles; tile += stride) {
     const int64_t ebase = tile * TE;
-    commit_rows(a, rw, lane, cvl, Ht);                       // waits for this tile's rows only
+    commit_rows<D>(a, rw, lane, cvl, Ht);                    // waits for this tile's rows only
     const TileIds nn = load_ids(a, tile + 2 * stride, n_tiles, lane);
-    issue_rows(a, nxt, lane, rw);                            // next tile's rows fly during the MFMAs
+    issue_rows<D>(a, nxt, lane, rw);                         // next tile's rows fly during the MFMAs
     nxt = nn;
     wave_lds_sync();
-    f32x16 acc[2];
-    gemm1(Wl, Ht, lane, acc);
-    float part = 0.f;
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int qd = 0; qd < 4; ++qd) {
-        const int j0 = 32 * b + 8 * qd + 4 * hh;
-        const float4 bb = *reinterpret_cast<const float4*>(b2l + j0);
-        const float4 ww = *reinterpret_cast<const float4*>(w3l + j0);
-        part = fmaf(relu1(acc[b][4 * qd + 0] + bb.x), ww.x, part);
-        part = fmaf(relu1(acc[b][4 * qd + 1] + bb.y), ww.y, part);
-        part = fmaf(relu1(acc[b][4 * qd + 2] + bb.z), ww.z, part);
-        part = fmaf(relu1(acc[b][4 * qd + 3] + bb.w), ww.w, part);
-      }
+    f32x16 acc[S::NB];
+    gemm1<D>(Wl, Ht, lane, acc);
+    float part = layer2_epilogue<D>(b2l, w3l, hh, acc);
     part += __shfl_xor(part, 32);
     if (lane < 32 && ebase + lane < a.E) logits[ebase + lane] = part + b3;
     wave_lds_sync();   // the next commit overwrites Ht
   }
 }
 
-// FUSED_LOSS: the upstream gradient is not read but produced in place — the tile's logits come out of the
-// first product anyway, so BCEWithLogits(pos_weight) and its derivative are evaluated right there
-// (pangnn.py:200-207 in one pass): a training step then runs this kernel only, not forward + loss +
-// backward, and the forward's 64 MFMAs per tile are not spent twice.
+// FUSED_LOSS: the upstream gradient is not read but produced in place — the tile's logits come out of the first product
+// anyway, so BCEWithLogits(pos_weight) and its derivative are evaluated right there (pangnn.py:200-207 in one pass): a
+// training step then runs this kernel only, not forward + loss + backward.
 struct LossParams {
-  const float* y; const float* pos_weight; float inv_denom; float* logits; 
+  const float* y; const float* pos_weight; float inv_denom; float* logits;
 };
 
-// RUNSUM: when the caller's edge order is sorted by source (every edge list pangnn_amd/construct.py emits
-// is), the rows of dL/dh1 that belong to one source are consecutive, so their sum — dL/dP[source] — is
-// taken right here per (tile, source) run and written as one 256-byte "part" row; a short contiguous
-// segment sum over the parts replaces a 19 GB pass over dL/dh1.  part_off[tile] = index of the tile's first
-// part (precomputed with the structure); the number of parts a tile writes is fixed by the edge list, so
-// the layout is deterministic.
+// RUNSUM: when the caller's edge order is sorted by source (every edge list pangnn_amd/construct.py emits is), the rows of
+// dL/dh1 that belong to one source are consecutive, so their sum — dL/dP[source] — is taken right here per (tile, source)
+// run and written as one "part" row of D floats; a short contiguous segment sum over the parts replaces a pass over
+// dL/dh1.  part_off[tile] = index of the tile's first part (EdgeStructure._plan_of_sorted_keys with chunk_tiles = 1); the
+// number of parts a tile writes is fixed by the edge list, so the layout is deterministic.
 struct RunSumParams {
   float* part; const int32_t* part_off;
 };
 
-template <bool FUSED_LOSS, bool RUNSUM>
-__global__ __launch_bounds__(BWD_WAVES * 64) void decoder_bwd_kernel(
+template <int D, bool FUSED_LOSS, bool RUNSUM>
+__global__ __launch_bounds__(Shape<D>::WAVES * 64) void decoder_bwd_kernel(
     DecParams a, const float* __restrict__ g_logits, LossParams lp, RunSumParams rs, float* __restrict__ g_h1,
     float* __restrict__ slabs, int64_t n_tiles) {
-  constexpr int PER_WAVE = TE * RS + 64 * GS + 64;   // Ht | H2t | w_e | g_e
-  __shared__ __attribute__((aligned(16))) float lds[64 * RS + 3 * 64 + BWD_WAVES * PER_WAVE];
+  using S = Shape<D>;
+  constexpr int NB = S::NB, RS = S::RS, WAVES = S::WAVES;
+  // D = 128: dL/dW2 is shared out over the workgroup's four waves, wave w owning the 32 rows j of block w (4 blocks of
+  // 32 x 32 = 64 accumulator registers; all 16 blocks per wave would take every accumulator register there is and leave
+  // none for the two other products).  The waves then walk their tiles in step, one round of WAVES tiles at a time.
+  constexpr bool COOP = S::COOP;
+  constexpr int NJ = COOP ? 1 : NB;      // blocks of 32 rows of dL/dW2 a wave accumulates
+  constexpr int WGRAD_UNROLL = S::WGRAD_UNROLL;
+  __shared__ __attribute__((aligned(16))) float lds[S::BWD_LDS];
   float* Wl = lds;
-  float* b2l = lds + 64 * RS;
-  float* w3l = b2l + 64;
-  float* cvl = w3l + 64;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;   // SGPR: tile index and its addresses stay scalar
-  float* Ht = cvl + 64 + wave * PER_WAVE;
-  float* Gt = Ht + TE * RS;
-  float* wl = Gt + 64 * GS;
+  float* b2l = lds + D * RS;
+  float* w3l = b2l + D;
+  float* cvl = w3l + D;
+  float* tiles = cvl + D;         // WAVES x (h1 tile | h2 slice | w_e | g_e)
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  float* Ht = tiles + wave * S::PER_WAVE;
+  float* Gt = Ht + TE * RS;       // h2[j][e] of one block of 32 outputs j
+  float* wl = Gt + 32 * GS;
   float* gl = wl + 32;
-  stage_weights(a, Wl, b2l, w3l, cvl, BWD_WAVES * 64);
+  stage_weights<D>(a, Wl, b2l, w3l, cvl);
   __syncthreads();
   const int hh = lane >> 5, r = lane & 31;
 
-  f32x16 acc3[2][2];   // gW2[j = jr(i,hh)+32bj][k = r+32bk]
+  f32x16 acc3[NJ][NB];   // gW2[j = jr(i,hh) + 32 (COOP ? wave : bj)][k = r + 32bk]
 #pragma unroll
-  for (int x = 0; x < 2; ++x) {
+  for (int bj = 0; bj < NJ; ++bj)
 #pragma unroll
-    for (int i = 0; i < 16; ++i) { acc3[x][0][i] = 0.f; acc3[x][1][i] = 0.f; }
+    for (int bk = 0; bk < NB; ++bk)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) acc3[bj][bk][i] = 0.f;
+  float w3j[NJ], gw3p[NJ], gb2p[NJ], gcv[NB];
+#pragma unroll
+  for (int b = 0; b < NJ; ++b) {
+    w3j[b] = w3l[r + 32 * (COOP ? wave : b)];
+    gw3p[b] = 0.f;   // lane (j = r + 32b, hh): partial of gw3[j] over the edges e = hh mod 2
+    gb2p[b] = 0.f;   // same lanes: partial of gb2[j]
   }
-  const float w3j[2] = {w3l[r], w3l[r + 32]};
-  float gw3p[2] = {0.f, 0.f};   // lane (j = r+32bj, h): partial of gw3[j] over edges e = h mod 2
-  float gb2p[2] = {0.f, 0.f};   // same lanes: partial of gb2[j]
-  float gcv[2] = {0.f, 0.f};    // lane (k = r+32bp, hh): partial of gcvec[k]
+#pragma unroll
+  for (int b = 0; b < NB; ++b) gcv[b] = 0.f;    // lane (k = r + 32b, hh): partial of gcvec[k]
   float gb3p = 0.f;
-  float lossp = 0.f;            // FUSED_LOSS: lanes < 32, partial of the (already 1/denom-scaled) loss
+  float lossp = 0.f;            // FUSED_LOSS: partial of the (already 1/denom-scaled) loss
   const float b3v = a.b3[0];
   const float pw = (FUSED_LOSS && lp.pos_weight) ? lp.pos_weight[0] : 1.f;
 
-  // One tile.  FULL (every tile but the last of the edge list): all 32 edges exist, so the bounds predicates on
-  // loads / stores and the `live` selects fold away; the instruction count of this body is what the kernel's
-  // time follows (f32 MFMA and vector instructions share the SIMD's lanes), so the common case carries none.
-  auto body = [&](const int64_t tile, auto full_c) __attribute__((always_inline)) {
+  // what a tile carries from its front half (forward recomputation) to its back half (dL/dh1)
+  f32x16 acc[NB];      // h2[j][e], lane (e = r, hh), rows jr(i,hh) + 32b
+  float g_e = 0.f;
+  int id = 0;
+
+  // gW2[j][k] += sum_e G[j][e] h1[e][k] for the 32 rows j of one block, G rebuilt from the block's h2 rows in `Gs` and the
+  // tile's dL/dlogit in `gls`; h1 from the tile image `Hs`
+  auto wgrad_block = [&](const float* Hs, const float* Gs, const float* gls, int bj) __attribute__((always_inline)) {
+#pragma unroll WGRAD_UNROLL
+    for (int s = 0; s < 16; ++s) {
+      const int e = 2 * s + hh;
+      const float ge = gls[e];
+      const float x = Gs[r * GS + e];                      // h2[j = r + 32 block][e]
+      const float av = x <= 0.f ? 0.f : ge * w3j[bj];      // not `x > 0 ?`: a NaN h2 keeps its column on
+      gw3p[bj] = fmaf(ge, x, gw3p[bj]);
+      gb2p[bj] += av;
+#pragma unroll
+      for (int bk = 0; bk < NB; ++bk) {
+        const float hv = Hs[e * RS + r + 32 * bk];
+        acc3[bj][bk] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, hv, acc3[bj][bk], 0, 0, 0);
+      }
+    }
+  };
+
+  // Front half of a tile: gather, first product, logits / loss / dL/dlogit.  FULL (every tile but the last of the edge
+  // list): all 32 edges exist, so the bounds predicates on loads / stores and the `live` selects fold away; the
+  // instruction count of a tile is what the kernel's time follows (f32 MFMA and vector instructions share the SIMD's
+  // lanes), so the common case carries none.
+  auto front = [&](const int64_t tile, auto full_c) __attribute__((always_inline)) {
     constexpr bool FULL = decltype(full_c)::value;
     const int64_t ebase = tile * TE;
     float w_e;
-    int id;
-    gather_tile<FULL>(a, ebase, lane, Ht, cvl, w_e, id);
-    float g_e = 0.f;
+    gather_tile<D, FULL>(a, ebase, lane, Ht, cvl, w_e, id);
+    g_e = 0.f;
     float y_e = 0.f;
     const bool live = FULL || ebase + r < a.E;
     if (FUSED_LOSS) {
@@ -345,33 +427,10 @@ __global__ __launch_bounds__(BWD_WAVES * 64) void decoder_bwd_kernel(
     }
     wave_lds_sync();
 
-    f32x16 acc[2];
-    gemm1(Wl, Ht, lane, acc);
+    gemm1<D>(Wl, Ht, lane, acc);
+    float part = layer2_epilogue<D>(b2l, w3l, hh, acc);     // acc = h2[j][e]
 
     if (FUSED_LOSS) {
-      // h2 = relu(C + b2) -> LDS (the weight-gradient product reads it); the tile's logits; the accumulator is
-      // overwritten with the masked w3 ([h2 > 0] w3[j]) while w3 is in registers anyway, so that once the
-      // edge's dL/dlogit is known G = g_e * (masked w3) is one multiply per element — no second pass over w3,
-      // no compare / select after the reduction
-      float part = 0.f;
-#pragma unroll
-      for (int b = 0; b < 2; ++b)
-#pragma unroll
-        for (int qd = 0; qd < 4; ++qd) {
-          const int j0 = 32 * b + 8 * qd + 4 * hh;
-          const float4 bb = *reinterpret_cast<const float4*>(b2l + j0);
-          const float4 ww = *reinterpret_cast<const float4*>(w3l + j0);
-          const float bbv[4] = {bb.x, bb.y, bb.z, bb.w};
-          const float wwv[4] = {ww.x, ww.y, ww.z, ww.w};
-#pragma unroll
-          for (int c = 0; c < 4; ++c) {
-            const int i = 4 * qd + c;
-            const float h2 = relu1(acc[b][i] + bbv[c]);
-            part = fmaf(h2, wwv[c], part);
-            Gt[(j0 + c) * GS + r] = h2;
-            acc[b][i] = h2 <= 0.f ? 0.f : wwv[c];          // not `h2 > 0 ?`: a NaN h2 keeps its column on
-          }
-        }
       part += __shfl_xor(part, 32);                 // both halves of the wave now hold edge r's logit
       const float xv = part + b3v;
       const float lw = 1.f + (pw - 1.f) * y_e;
@@ -391,168 +450,190 @@ __global__ __launch_bounds__(BWD_WAVES * 64) void decoder_bwd_kernel(
       gb3p += g_e;                                   // per-half partials; lane 0's half is the one read out
       lossp += live ? ((1.f - y_e) * xv + lw * (l1p + fmaxf(-xv, 0.f))) * lp.inv_denom : 0.f;   // select, not a branch
       if (hh == 0 && live) lp.logits[ebase + r] = xv;
-#pragma unroll
-      for (int b = 0; b < 2; ++b)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[b][i] *= g_e;   // G[j][e]: A operand of the next product
-    } else {
-      // G[j][e] = g_e * w3[j] * [h2pre > 0]  (in place in acc; A operand of the next product);
-      // h2[j][e] goes to LDS: the weight-gradient product rebuilds G and g_e * h2 from it
-#pragma unroll
-      for (int b = 0; b < 2; ++b)
-#pragma unroll
-        for (int qd = 0; qd < 4; ++qd) {
-          const int j0 = 32 * b + 8 * qd + 4 * hh;
-          const float4 bb = *reinterpret_cast<const float4*>(b2l + j0);
-          const float4 ww = *reinterpret_cast<const float4*>(w3l + j0);
-          const float bbv[4] = {bb.x, bb.y, bb.z, bb.w};
-          const float wwv[4] = {ww.x, ww.y, ww.z, ww.w};
-#pragma unroll
-          for (int c = 0; c < 4; ++c) {
-            const int i = 4 * qd + c;
-            const float pre = acc[b][i] + bbv[c];
-            const bool on = !(pre <= 0.f);                // a NaN stays on, as in torch's relu backward
-            acc[b][i] = on ? g_e * wwv[c] : 0.f;
-            Gt[(j0 + c) * GS + r] = on ? pre : 0.f;
-          }
-        }
     }
-    wave_lds_sync();
+  };
 
-    // gH1[e][k] = sum_j G[j][e] W2[j][k]  : A = G from the accumulator registers, B = W2 rows
-    f32x16 acc2[2];
+  // Back half: the accumulators become G[j][e] = g_e * w3[j] * [h2 > 0], the A operand of gH1[e][k] = sum_j G[j][e] W2[j][k]
+  // (B = W2 rows); mask by h1 > 0, write dL/dh1pre, accumulate gcvec, run sums.
+  auto back = [&](const int64_t tile, auto full_c) __attribute__((always_inline)) {
+    constexpr bool FULL = decltype(full_c)::value;
+    const int64_t ebase = tile * TE;
 #pragma unroll
-    for (int i = 0; i < 16; ++i) { acc2[0][i] = 0.f; acc2[1][i] = 0.f; }
+    for (int b = 0; b < NB; ++b)
 #pragma unroll
-    for (int b = 0; b < 2; ++b)
+      for (int qd = 0; qd < 4; ++qd) {
+        const float4 ww = *reinterpret_cast<const float4*>(w3l + 32 * b + 8 * qd + 4 * hh);
+        const float wwv[4] = {ww.x, ww.y, ww.z, ww.w};
 #pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int j = 32 * b + jr(i, hh);
-        const float w0 = Wl[swz(j, r)];
-        const float w1 = Wl[swz(j, r + 32)];
-        acc2[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(acc[b][i], w0, acc2[0], 0, 0, 0);
-        acc2[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(acc[b][i], w1, acc2[1], 0, 0, 0);
+        for (int c = 0; c < 4; ++c) acc[b][4 * qd + c] = acc[b][4 * qd + c] <= 0.f ? 0.f : g_e * wwv[c];
       }
-    // mask by h1 > 0, write dL/dh1pre (kept in acc2 for the run sums), accumulate gcvec.  Full tiles store
-    // through one lane base pointer + compile-time offsets: no per-element bounds test or address arithmetic.
-    {
-      float* gout = g_h1 + (ebase + 4 * hh) * DD + r;
-      const bool full = FULL || ebase + TE <= a.E;
-#pragma unroll
-      for (int bp = 0; bp < 2; ++bp)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const int e = jr(i, hh);
-          const int k = r + 32 * bp;
-          const float hval = Ht[swz(e, k)];
-          const float v = hval <= 0.f ? 0.f : acc2[bp][i];
-          if (full || ebase + e < a.E) __builtin_nontemporal_store(v, &gout[jr(i, 0) * DD + 32 * bp]);   // 19 GB written once
-          acc2[bp][i] = v;
-        }
-      if (a.extra) {                                 // uniform; only with skip connections
-#pragma unroll
-        for (int bp = 0; bp < 2; ++bp)
-#pragma unroll
-          for (int i = 0; i < 16; ++i) gcv[bp] = fmaf(wl[jr(i, hh)], acc2[bp][i], gcv[bp]);
-      }
-    }
-
-    // gW2[j][k] += sum_e G[j][e] h1[e][k]  : both operands from LDS, reduction over the tile's edges
-#pragma unroll
-    for (int s = 0; s < 16; ++s) {
-      const int e = 2 * s + hh;
-      const float ge = gl[e];
-      const float x0 = Gt[r * GS + e];           // h2[j][e]
-      const float x1 = Gt[(r + 32) * GS + e];
-      const float a0 = x0 <= 0.f ? 0.f : ge * w3j[0];
-      const float a1 = x1 <= 0.f ? 0.f : ge * w3j[1];
-      gw3p[0] = fmaf(ge, x0, gw3p[0]);
-      gw3p[1] = fmaf(ge, x1, gw3p[1]);
-      gb2p[0] += a0;
-      gb2p[1] += a1;
-      const float h0 = Ht[swz(e, r)];
-      const float h1v = Ht[swz(e, r + 32)];
-      acc3[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, h0, acc3[0][0], 0, 0, 0);
-      acc3[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, h1v, acc3[0][1], 0, 0, 0);
-      acc3[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, h0, acc3[1][0], 0, 0, 0);
-      acc3[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, h1v, acc3[1][1], 0, 0, 0);
-    }
+    // run sums: a part closes at the last edge of every source run of the tile
+    unsigned m = 0u;
+    int64_t pidx = 0;
     if (RUNSUM) {
-      // close a part at the last edge of every source run of the tile
       const int id_nxt = __shfl(id, (lane + 1) & 63);
       const bool ok = lane < 32 && (FULL || ebase + lane < a.E);
       const bool ok_nxt = lane < 31 && (FULL || ebase + lane + 1 < a.E);
       const unsigned long long mask = __ballot(ok && (!ok_nxt || id != id_nxt));
-      const unsigned m = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(mask & 0xffffffffull));
-      int64_t pidx = rs.part_off[tile];
-      if ((m & (m - 1u)) == 0u) {
-        // one run covers the tile (the common case at degree >> 32): column sums straight from registers
-        float s0 = 0.f, s1 = 0.f;
+      m = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(mask & 0xffffffffull));
+      pidx = rs.part_off[tile];
+    }
+    const bool one_run = (m & (m - 1u)) == 0u, two_runs = __builtin_popcount(m) == 2;   // uniform
+    const int bnd = __builtin_ctz(m | 0x80000000u);        // two runs: last edge of the first
+    float* gout = g_h1 + (ebase + 4 * hh) * D + r;
+    const bool full = FULL || ebase + TE <= a.E;
+    const bool has_extra = a.extra != nullptr;             // uniform; only with skip connections
+    // one block of 32 columns k at a time (16 accumulator registers, not 16 NB)
 #pragma unroll
-        for (int i = 0; i < 16; ++i) { s0 += acc2[0][i]; s1 += acc2[1][i]; }
-        s0 += __shfl_xor(s0, 32);
-        s1 += __shfl_xor(s1, 32);
-        if (hh == 0) {
-          rs.part[pidx * DD + r] = s0;
-          rs.part[pidx * DD + 32 + r] = s1;
+    for (int bp = 0; bp < NB; ++bp) {
+      f32x16 acc2;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) acc2[i] = 0.f;
+#pragma unroll
+      for (int b = 0; b < NB; ++b)
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+          acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(acc[b][i], Wl[(32 * b + jr(i, hh)) * RS + r + 32 * bp], acc2, 0, 0, 0);
+      // mask by h1 > 0, write dL/dh1pre (full tiles store through one lane base pointer + compile-time offsets: no
+      // per-element bounds test or address arithmetic), accumulate gcvec
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const int e = jr(i, hh);
+        const float hval = Ht[e * RS + r + 32 * bp];
+        const float v = hval <= 0.f ? 0.f : acc2[i];
+        if (full || ebase + e < a.E) __builtin_nontemporal_store(v, &gout[jr(i, 0) * D + 32 * bp]);   // written once
+        acc2[i] = v;
+      }
+      if (has_extra) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) gcv[bp] = fmaf(wl[jr(i, hh)], acc2[i], gcv[bp]);
+      }
+      if (RUNSUM) {
+        if (one_run) {
+          // one run covers the tile (the common case at degree >> 32): column sums straight from registers
+          float s0 = 0.f;
+#pragma unroll
+          for (int i = 0; i < 16; ++i) s0 += acc2[i];
+          s0 += __shfl_xor(s0, 32);
+          if (hh == 0) rs.part[pidx * D + 32 * bp + r] = s0;
+        } else if (two_runs) {
+          // both column sums from the registers, rows selected by their position relative to the boundary
+          float s0 = 0.f, s1 = 0.f;
+#pragma unroll
+          for (int i = 0; i < 16; ++i) {
+            const bool first = jr(i, hh) <= bnd;
+            s0 += first ? acc2[i] : 0.f;
+            s1 += first ? 0.f : acc2[i];
+          }
+          s0 += __shfl_xor(s0, 32);
+          s1 += __shfl_xor(s1, 32);
+          if (hh == 0) {
+            rs.part[pidx * D + 32 * bp + r] = s0;
+            rs.part[(pidx + 1) * D + 32 * bp + r] = s1;
+          }
+        } else {
+          // three or more runs: the block's dL/dh1 values replace the h1 values they were masked with (same lane, same
+          // address; the other blocks' columns stay)
+#pragma unroll
+          for (int i = 0; i < 16; ++i) Ht[jr(i, hh) * RS + r + 32 * bp] = acc2[i];
         }
-      } else if (__builtin_popcount(m) == 2) {
-        // two runs: both column sums from the registers, rows selected by their position relative to the boundary
-        const int bnd = __builtin_ctz(m);            // last edge of the first run
-        float a0 = 0.f, a1 = 0.f, b0 = 0.f, b1 = 0.f;
+      }
+      if (D == 128) __builtin_amdgcn_sched_barrier(0);     // one block's loads in flight at a time: registers
+    }
+    if (RUNSUM && !one_run && !two_runs) {
+      // a lane owns the columns lane, lane + 64 (D = 32: lanes 0-31 one column each) and walks the 32 rows
+      constexpr int CPL = (D + 63) / 64;
+      wave_lds_sync();
+      if (D >= 64 || lane < D) {
+        float sum[CPL];
 #pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const bool first = jr(i, hh) <= bnd;
-          a0 += first ? acc2[0][i] : 0.f;
-          b0 += first ? 0.f : acc2[0][i];
-          a1 += first ? acc2[1][i] : 0.f;
-          b1 += first ? 0.f : acc2[1][i];
-        }
-        a0 += __shfl_xor(a0, 32);
-        a1 += __shfl_xor(a1, 32);
-        b0 += __shfl_xor(b0, 32);
-        b1 += __shfl_xor(b1, 32);
-        if (hh == 0) {
-          rs.part[pidx * DD + r] = a0;
-          rs.part[pidx * DD + 32 + r] = a1;
-          rs.part[(pidx + 1) * DD + r] = b0;
-          rs.part[(pidx + 1) * DD + 32 + r] = b1;
-        }
-      } else {
-        // three or more runs: dL/dh1 tile -> LDS (the h1 image is no longer needed); every lane owns one of the
-        // 64 columns and walks the 32 rows
-        wave_lds_sync();
-#pragma unroll
-        for (int bp = 0; bp < 2; ++bp)
-#pragma unroll
-          for (int i = 0; i < 16; ++i) Ht[swz(jr(i, hh), r + 32 * bp)] = acc2[bp][i];
-        wave_lds_sync();
-        float sum = 0.f;
+        for (int x = 0; x < CPL; ++x) sum[x] = 0.f;
 #pragma unroll
         for (int e = 0; e < TE; ++e) {
-          sum += Ht[swz(e, lane)];
+#pragma unroll
+          for (int x = 0; x < CPL; ++x) sum[x] += Ht[e * RS + lane + 64 * x];
           if ((m >> e) & 1u) {
-            rs.part[pidx * DD + lane] = sum;
-            sum = 0.f;
+#pragma unroll
+            for (int x = 0; x < CPL; ++x) {
+              rs.part[pidx * D + lane + 64 * x] = sum[x];
+              sum[x] = 0.f;
+            }
             ++pidx;
           }
         }
       }
     }
-    wave_lds_sync();   // next tile overwrites Ht / Gt / wl
+    wave_lds_sync();   // next tile overwrites Ht / Gt / wl / gl
   };
-  const int64_t n_full = a.E / TE, stride = (int64_t)gridDim.x * BWD_WAVES;
-  int64_t tile = (int64_t)blockIdx.x * BWD_WAVES + wave;
-  for (; tile < n_full; tile += stride) body(tile, std::true_type{});
-  if (tile < n_tiles) body(tile, std::false_type{});     // tile == n_full: the partial tile, one wave's turn
+
+  const int64_t n_full = a.E / TE, stride = (int64_t)gridDim.x * WAVES;
+  if constexpr (!COOP) {
+    // a wave finishes a tile on its own: one block of 32 outputs j at a time, the block's h2 rows go through LDS (the
+    // accumulator layout has the edge on the lane, the weight-gradient product wants j there)
+    auto body = [&](const int64_t tile, auto full_c) __attribute__((always_inline)) {
+      front(tile, full_c);
+#pragma unroll
+      for (int b = 0; b < NB; ++b) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) Gt[jr(i, hh) * GS + r] = acc[b][i];
+        wave_lds_sync();
+        wgrad_block(Ht, Gt, gl, b);
+        wave_lds_sync();   // the next block overwrites Gt
+      }
+      back(tile, full_c);
+    };
+    int64_t tile = (int64_t)blockIdx.x * WAVES + wave;
+    for (; tile < n_full; tile += stride) body(tile, std::true_type{});
+    if (tile < n_tiles) body(tile, std::false_type{});     // tile == n_full: the partial tile, one wave's turn
+  } else {
+    // Rounds of WAVES consecutive tiles, wave w taking tile base + w.  In step t of a round wave w stages the h2 rows of
+    // block (w + t) mod WAVES of its tile, and the owner of that block, wave (w + t) mod WAVES, multiplies them with w's h1
+    // tile.  Every wave of the workgroup passes every barrier, with or without a tile of its own; the barriers stand
+    // outside the FULL / partial instances of the two halves.
+    static_assert(!COOP || (NB == WAVES && (WAVES & (WAVES - 1)) == 0), "one block of dL/dW2 rows per wave");
+    for (int64_t base = (int64_t)blockIdx.x * WAVES; base < n_tiles; base += stride) {
+      const int64_t tile = base + wave;
+      const bool have = tile < n_tiles;                     // tiles base .. base + n_have - 1 exist
+      const int n_have = (int)(n_tiles - base < WAVES ? n_tiles - base : WAVES);
+      if (have) {
+        if (tile < n_full) front(tile, std::true_type{});
+        else front(tile, std::false_type{});
+      }
+#pragma unroll 1
+      for (int t = 0; t < WAVES; ++t) {
+        if (have) {
+          const int pb = (wave + t) & (WAVES - 1);          // uniform; selects, not a register index
+#pragma unroll
+          for (int i = 0; i < 16; ++i) {
+            float v = acc[0][i];
+#pragma unroll
+            for (int b = 1; b < NB; ++b) v = pb == b ? acc[b][i] : v;
+            Gt[jr(i, hh) * GS + r] = v;
+          }
+        }
+        __syncthreads();
+        const int src = (wave - t) & (WAVES - 1);           // the wave whose tile this wave's block is staged from
+        if (src < n_have) {
+          const float* Hs = tiles + src * S::PER_WAVE;
+          wgrad_block(Hs, Hs + TE * RS, Hs + TE * RS + 32 * GS + 32, 0);
+        }
+        __syncthreads();   // the next step overwrites the slices; after the last step the tiles are their waves' again
+      }
+      if (have) {
+        if (tile < n_full) back(tile, std::true_type{});
+        else back(tile, std::false_type{});
+      }
+    }
+  }
 
   // ---- fold the per-lane partials, then reduce the workgroup's waves in wave order
-  gw3p[0] += __shfl_xor(gw3p[0], 32);
-  gw3p[1] += __shfl_xor(gw3p[1], 32);
-  gb2p[0] += __shfl_xor(gb2p[0], 32);
-  gb2p[1] += __shfl_xor(gb2p[1], 32);
-  gcv[0] += __shfl_xor(gcv[0], 32);
-  gcv[1] += __shfl_xor(gcv[1], 32);
+#pragma unroll
+  for (int b = 0; b < NJ; ++b) {
+    gw3p[b] += __shfl_xor(gw3p[b], 32);
+    gb2p[b] += __shfl_xor(gb2p[b], 32);
+  }
+#pragma unroll
+  for (int b = 0; b < NB; ++b) gcv[b] += __shfl_xor(gcv[b], 32);
 #pragma unroll
   for (int off = 16; off >= 1; off >>= 1) {
     gb3p += __shfl_xor(gb3p, off);
@@ -560,55 +641,86 @@ __global__ __launch_bounds__(BWD_WAVES * 64) void decoder_bwd_kernel(
   }
 
   __syncthreads();
-  float* red = cvl + 64;   // reuse the tile area: SLAB floats
-  for (int w = 0; w < BWD_WAVES; ++w) {
+  float* red = tiles;   // reuse the tile area: SLAB floats
+  if constexpr (COOP) {   // the rows of gW2 / gb2 / gw3 of block `wave` are this wave's alone
+#pragma unroll
+    for (int bk = 0; bk < NB; ++bk)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) red[(32 * wave + jr(i, hh)) * D + r + 32 * bk] = acc3[0][bk][i];
+    if (hh == 0) {
+      red[D * D + 32 * wave + r] = gb2p[0];
+      red[D * D + D + 32 * wave + r] = gw3p[0];
+    }
+  }
+  for (int w = 0; w < WAVES; ++w) {
     if (wave == w) {
       const bool first = (w == 0);
+      if constexpr (!COOP) {
 #pragma unroll
-      for (int bj = 0; bj < 2; ++bj)
+        for (int bj = 0; bj < NB; ++bj)
 #pragma unroll
-        for (int bk = 0; bk < 2; ++bk)
+          for (int bk = 0; bk < NB; ++bk)
 #pragma unroll
-          for (int i = 0; i < 16; ++i) {
-            const int idx = (32 * bj + jr(i, hh)) * 64 + r + 32 * bk;
-            red[idx] = (first ? 0.f : red[idx]) + acc3[bj][bk][i];
-          }
+            for (int i = 0; i < 16; ++i) {
+              const int idx = (32 * bj + jr(i, hh)) * D + r + 32 * bk;
+              red[idx] = (first ? 0.f : red[idx]) + acc3[bj][bk][i];
+            }
+      }
       if (hh == 0) {
 #pragma unroll
-        for (int x = 0; x < 2; ++x) {
-          red[4096 + r + 32 * x] = (first ? 0.f : red[4096 + r + 32 * x]) + gb2p[x];
-          red[4096 + 64 + r + 32 * x] = (first ? 0.f : red[4096 + 64 + r + 32 * x]) + gw3p[x];
-          red[4096 + 128 + r + 32 * x] = (first ? 0.f : red[4096 + 128 + r + 32 * x]) + gcv[x];
+        for (int x = 0; x < NB; ++x) {
+          const int o = D * D + r + 32 * x;
+          if constexpr (!COOP) {
+            red[o] = (first ? 0.f : red[o]) + gb2p[x];
+            red[o + D] = (first ? 0.f : red[o + D]) + gw3p[x];
+          }
+          red[o + 2 * D] = (first ? 0.f : red[o + 2 * D]) + gcv[x];
         }
       }
       if (lane == 0) {
-        red[4096 + 192] = (first ? 0.f : red[4096 + 192]) + gb3p;
-        red[4096 + 193] = (first ? 0.f : red[4096 + 193]) + lossp;
+        const int o = D * D + 3 * D;
+        red[o] = (first ? 0.f : red[o]) + gb3p;
+        red[o + 1] = (first ? 0.f : red[o + 1]) + lossp;
       }
     }
     __syncthreads();
   }
-  float* slab = slabs + (int64_t)blockIdx.x * SLAB;
-  for (int i = threadIdx.x; i < 4096 + 194; i += BWD_WAVES * 64) slab[i] = red[i];
+  float* slab = slabs + (int64_t)blockIdx.x * S::SLAB;
+  for (int i = threadIdx.x; i < S::SLAB; i += WAVES * 64) slab[i] = red[i];
 }
 
-// out[i] = sum over workgroup slabs in index order (fixed => reproducible)
+// out[i] = sum over the workgroup slabs (`stride` floats apart, layout of Shape<d>::SLAB) in index order (fixed =>
+// reproducible)
 __global__ __launch_bounds__(kSumThreads) void decoder_reduce_kernel(const float* __restrict__ slabs, int n_slabs,
-                                                                float* __restrict__ g_w2,
-                                                                float* __restrict__ g_b2,
-                                                                float* __restrict__ g_w3,
-                                                                float* __restrict__ g_cvec,
-                                                                float* __restrict__ g_b3,
-                                                                float* __restrict__ loss) {
+                                                                     int stride, int d, float* __restrict__ g_w2,
+                                                                     float* __restrict__ g_b2, float* __restrict__ g_w3,
+                                                                     float* __restrict__ g_cvec, float* __restrict__ g_b3,
+                                                                     float* __restrict__ loss) {
+  const int dd = d * d, len = dd + 3 * d + 2;
   const int i = blockIdx.x * kWave + (threadIdx.x & (kWave - 1));
-  const float s = ordered_parts_sum(slabs, n_slabs, SLAB, i, 4096 + 194);
-  if (threadIdx.x >= kWave || i >= 4096 + 194) return;
-  if (i < 4096) g_w2[i] = s;
-  else if (i < 4096 + 64) { if (g_b2) g_b2[i - 4096] = s; }
-  else if (i < 4096 + 128) g_w3[i - 4096 - 64] = s;
-  else if (i < 4096 + 192) { if (g_cvec) g_cvec[i - 4096 - 128] = s; }
-  else if (i == 4096 + 192) g_b3[0] = s;
+  const float s = ordered_parts_sum(slabs, n_slabs, stride, i, len);
+  if (threadIdx.x >= kWave || i >= len) return;
+  if (i < dd) g_w2[i] = s;
+  else if (i < dd + d) { if (g_b2) g_b2[i - dd] = s; }
+  else if (i < dd + 2 * d) g_w3[i - dd - d] = s;
+  else if (i < dd + 3 * d) { if (g_cvec) g_cvec[i - dd - 2 * d] = s; }
+  else if (i == dd + 3 * d) g_b3[0] = s;
   else if (loss) loss[0] = s;
+}
+
+static int launch_reduce(const char* who, const float* slabs, int n_slabs, int stride, int d, float* g_w2, float* g_b2,
+                         float* g_w3, float* g_cvec, float* g_b3, float* loss, hipStream_t s) {
+  const int len = d * d + 3 * d + 2;
+  hipLaunchKernelGGL(decoder_reduce_kernel, dim3((len + kWave - 1) / kWave), dim3(kSumThreads), 0, s, slabs, n_slabs,
+                     stride, d, g_w2, g_b2, g_w3, g_cvec, g_b3, loss);
+  PG_CHECK_LAUNCH(who);
+  return 0;
+}
+
+// for decoder16.hip: the same finishing reduction over its slabs (same layout at d = 64, its own stride)
+int launch_decoder_reduce(const float* slabs, int n_slabs, float* g_w2, float* g_b2, float* g_w3, float* g_cvec,
+                          float* g_b3, float* loss, hipStream_t s) {
+  return launch_reduce("decoder_reduce", slabs, n_slabs, SLAB16, 64, g_w2, g_b2, g_w3, g_cvec, g_b3, loss, s);
 }
 
 // decoder16.hip: inference form of the bf16 matrix-pipe mode
@@ -616,159 +728,224 @@ int launch_decoder_infer16(const float* p, int64_t ldp, const float* q, int64_t 
                            int64_t num_edges, const float* extra, const float* cvec, const float* w2, const float* b2,
                            const float* w3, const float* b3, float* logits, hipStream_t s);
 
-// for decoder16.hip: the same finishing reduction over its slabs (same layout)
-int launch_decoder_reduce(const float* slabs, int n_slabs, float* g_w2, float* g_b2, float* g_w3, float* g_cvec,
-                          float* g_b3, float* loss, hipStream_t s) {
-  hipLaunchKernelGGL(decoder_reduce_kernel, dim3((4096 + 194 + kWave - 1) / kWave), dim3(kSumThreads), 0, s, slabs,
-                     n_slabs, g_w2, g_b2, g_w3, g_cvec, g_b3, loss);
-  PG_CHECK_LAUNCH("decoder_reduce");
-  return 0;
-}
-
-static int grid_cus() {
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) {
-    int v = 0;
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
+// ---- host side.  Two families of entry points share it: pangnn_decoder_mlp_* (node_dim 64, with a `precision` argument)
+// and pangnn_decoder_nd_* (node_dim 32 and 128); `nd` says which one is asking.
+struct DecArgs {   // the argument head every entry point takes
+  const float* p; int64_t ldp; const float* q; int64_t ldq; int64_t num_nodes; const int64_t* ei; int64_t ld; int64_t E;
+  const float* extra; const float* cvec; const float* w2; const float* b2; const float* w3; const float* b3; int32_t D;
+  DecParams params() const {
+    return DecParams{p, q, (uint32_t)(ldp / 4), (uint32_t)(ldq / 4), ei, ld, E, extra, cvec, w2, b2, w3, b3};
   }
-  return cus;
+};
+
+static bool nd_supported(int32_t D) { return D == 32 || D == 128; }
+
+// f(std::integral_constant<int, D>) for the runtime width D (checked by check_common)
+template <typename F>
+static void with_width(int32_t D, F&& f) {
+  if (D == 32) f(std::integral_constant<int, 32>{});
+  else if (D == 64) f(std::integral_constant<int, 64>{});
+  else f(std::integral_constant<int, 128>{});
 }
 
-static int check_common(const char* who, const float* p, const float* q, int64_t ldp, int64_t ldq,
-                        int64_t num_nodes,
-                        const int64_t* ei, int64_t ld, int64_t E, const float* extra,
-                        const float* cvec, const float* w2, const float* b2, const float* w3,
-                        const float* b3, int32_t D) {
-  PG_CHECK_ARG(D == DD, PANGNN_E_BADARG, "%s: fused decoder is built for node_dim 64, got %d", who, (int)D);
-  PG_CHECK_ARG(E >= 0 && ld >= E && num_nodes >= 0, PANGNN_E_BADARG, "%s: bad size", who);
-  PG_CHECK_ARG(ldp >= DD && ldq >= DD && ldp % 4 == 0 && ldq % 4 == 0, PANGNN_E_BADARG,
-               "%s: ldp / ldq must be multiples of 4 and >= 64", who);
-  PG_CHECK_ARG((double)num_nodes * (double)(ldp > ldq ? ldp : ldq) * 4.0 < 4294967296.0, PANGNN_E_TOOLARGE,
+// workgroups of a launch over `num_edges` edges: a function of the list's length alone
+static int64_t grid_of(int32_t D, int64_t num_edges) {
+  const int waves = D == 128 ? Shape<128>::WAVES : Shape<64>::WAVES;
+  static_assert(Shape<32>::WAVES == Shape<64>::WAVES, "grid_of");
+  const int64_t n_tiles = (num_edges + TE - 1) / TE;
+  int64_t grid = (n_tiles + waves - 1) / waves;
+  if (grid > kMaxGrid) grid = kMaxGrid;
+  if (grid < 1) grid = 1;
+  return grid;
+}
+
+static size_t workspace_of(int32_t D, int64_t num_edges) {
+  return (size_t)grid_of(D, num_edges < 0 ? 0 : num_edges) * (size_t)(D * D + 3 * D + 2) * sizeof(float);
+}
+
+static int check_common(const char* who, bool nd, const DecArgs& c) {
+  const int32_t D = c.D;
+  if (nd) PG_CHECK_ARG(nd_supported(D), PANGNN_E_BADARG, "%s: built for node_dim 32 and 128, got %d", who, (int)D);
+  else PG_CHECK_ARG(D == 64, PANGNN_E_BADARG, "%s: fused decoder is built for node_dim 64, got %d", who, (int)D);
+  PG_CHECK_ARG(c.E >= 0 && c.ld >= c.E && c.num_nodes >= 0, PANGNN_E_BADARG, "%s: bad size", who);
+  PG_CHECK_ARG(c.ldp >= D && c.ldq >= D && c.ldp % 4 == 0 && c.ldq % 4 == 0, PANGNN_E_BADARG,
+               "%s: ldp / ldq must be multiples of 4 and >= %d", who, (int)D);
+  PG_CHECK_ARG((double)c.num_nodes * (double)(c.ldp > c.ldq ? c.ldp : c.ldq) * 4.0 < 4294967296.0, PANGNN_E_TOOLARGE,
                "%s: node tables must stay under 4 GiB (32-bit gather offsets)", who);
-  if (E == 0) return 0;
-  PG_CHECK_ARG(p && q && ei && w2 && b2 && w3 && b3 && (!extra || cvec), PANGNN_E_BADARG,
+  if (c.E == 0) return 0;
+  PG_CHECK_ARG(c.p && c.q && c.ei && c.w2 && c.b2 && c.w3 && c.b3 && (!c.extra || c.cvec), PANGNN_E_BADARG,
                "%s: null pointer", who);
-  PG_CHECK_ARG(aligned16(p) && aligned16(q) && aligned16(w2), PANGNN_E_ALIGN,
+  PG_CHECK_ARG(aligned16(c.p) && aligned16(c.q) && aligned16(c.w2), PANGNN_E_ALIGN,
                "%s: p / q / w2 must be 16-byte aligned", who);
   return 0;
 }
+
+// precision: 0, or 1 from pangnn_decoder_mlp_infer_f32 = the bf16 matrix pipe with split operands of decoder16.hip (the
+// first product of its training kernel)
+static int decoder_fwd(const char* who, bool nd, const DecArgs& c, float* logits, int32_t precision, hipStream_t s) {
+  int rc = check_common(who, nd, c);
+  if (rc) return rc;
+  PG_CHECK_ARG(precision == 0 || precision == 1, PANGNN_E_BADARG, "pangnn_decoder_mlp_infer_f32: precision must be 0 or 1");
+  if (c.E == 0) return 0;
+  PG_CHECK_ARG(logits, PANGNN_E_BADARG, "%s: null logits", who);
+  if (precision)
+    return launch_decoder_infer16(c.p, c.ldp, c.q, c.ldq, c.ei, c.ld, c.E, c.extra, c.cvec, c.w2, c.b2, c.w3, c.b3, logits, s);
+  const int64_t n_tiles = (c.E + TE - 1) / TE;
+  const dim3 g((unsigned)grid_of(c.D, c.E));
+  const DecParams a = c.params();
+  with_width(c.D, [&](auto d) {
+    constexpr int D = decltype(d)::value;
+    hipLaunchKernelGGL((decoder_fwd_kernel<D>), g, dim3(Shape<D>::WAVES * 64), 0, s, a, logits, n_tiles);
+  });
+  PG_CHECK_LAUNCH(who);
+  return 0;
+}
+
+struct GradOut {   // the outputs and the workspace of the two training operations
+  float* g_h1; float* g_w2; float* g_b2; float* g_w3; float* g_b3; float* g_cvec; float* part_buf; const int32_t* part_off;
+  void* workspace; size_t workspace_bytes;
+};
+
+// the backward kernel (lp: with the fused loss) and the reduction over its slabs
+static int launch_bwd(const char* who, const DecArgs& c, const float* g_logits, const LossParams* lp, float* loss,
+                      int32_t precision, const GradOut& o, hipStream_t s) {
+  PG_CHECK_ARG(o.g_w2 && o.g_b2 && o.g_w3 && o.g_b3, PANGNN_E_BADARG, "%s: null gradient output", who);
+  PG_CHECK_ARG(precision == 0, PANGNN_E_BADARG,
+               "%s: only precision 0 (f32 MFMA) here; the bf16 matrix-pipe mode is pangnn_decoder_train_f32 + "
+               "pangnn_decoder_dgrad_f32", who);
+  const int64_t n_tiles = (c.E + TE - 1) / TE;
+  const int64_t grid = grid_of(c.D, c.E);
+  const size_t need = workspace_of(c.D, c.E);
+  PG_CHECK_ARG(o.workspace && o.workspace_bytes >= need, PANGNN_E_WORKSPACE, "%s: workspace too small", who);
+  PG_CHECK_ARG(c.E == 0 || o.g_h1, PANGNN_E_BADARG, "%s: null g_h1", who);
+  float* ws = static_cast<float*>(o.workspace);
+  if (c.E == 0) {
+    hipError_t e = hipMemsetAsync(ws, 0, need, s);
+    PG_CHECK_ARG(e == hipSuccess, (int)e, "%s: memset failed", who);
+  } else {
+    PG_CHECK_ARG((o.part_buf == nullptr) == (o.part_off == nullptr), PANGNN_E_BADARG,
+                 "%s: part_buf and part_off go together", who);
+    const DecParams a = c.params();
+    const LossParams l = lp ? *lp : LossParams{nullptr, nullptr, 0.f, nullptr};
+    const RunSumParams rs{o.part_buf, o.part_off};
+    const dim3 g((unsigned)grid);
+    with_width(c.D, [&](auto d) {
+      constexpr int D = decltype(d)::value;
+      const dim3 b(Shape<D>::WAVES * 64);
+      if (lp && rs.part) hipLaunchKernelGGL((decoder_bwd_kernel<D, true, true>), g, b, 0, s, a, g_logits, l, rs, o.g_h1, ws, n_tiles);
+      else if (lp) hipLaunchKernelGGL((decoder_bwd_kernel<D, true, false>), g, b, 0, s, a, g_logits, l, rs, o.g_h1, ws, n_tiles);
+      else if (rs.part) hipLaunchKernelGGL((decoder_bwd_kernel<D, false, true>), g, b, 0, s, a, g_logits, l, rs, o.g_h1, ws, n_tiles);
+      else hipLaunchKernelGGL((decoder_bwd_kernel<D, false, false>), g, b, 0, s, a, g_logits, l, rs, o.g_h1, ws, n_tiles);
+    });
+    PG_CHECK_LAUNCH(who);
+  }
+  return launch_reduce(who, ws, (int)grid, c.D * c.D + 3 * c.D + 2, c.D, o.g_w2, o.g_b2, o.g_w3, o.g_cvec, o.g_b3, loss, s);
+}
+
+static int decoder_bwd(const char* who, bool nd, const DecArgs& c, const float* g_logits, int32_t precision,
+                       const GradOut& o, hipStream_t s) {
+  int rc = check_common(who, nd, c);
+  if (rc) return rc;
+  PG_CHECK_ARG(c.E == 0 || g_logits, PANGNN_E_BADARG, "%s: null g_logits", who);
+  return launch_bwd(who, c, g_logits, nullptr, nullptr, precision, o, s);
+}
+
+static int decoder_loss(const char* who, bool nd, const DecArgs& c, const float* y, const float* pos_weight, int64_t denom,
+                        float* logits, float* loss, int32_t precision, const GradOut& o, hipStream_t s) {
+  int rc = check_common(who, nd, c);
+  if (rc) return rc;
+  PG_CHECK_ARG(denom > 0 && loss && (c.E == 0 || (y && logits)), PANGNN_E_BADARG, "%s: bad denom / null pointer", who);
+  const LossParams lp{y, pos_weight, 1.0f / (float)denom, logits};
+  return launch_bwd(who, c, nullptr, &lp, loss, precision, o, s);
+}
+
+// the nd family passes its workspace size as an int64_t: a negative one is too small
+static size_t ws_size(int64_t bytes) { return bytes > 0 ? (size_t)bytes : 0; }
 
 }  // namespace pangnn
 
 using namespace pangnn;
 
-extern "C" int pangnn_decoder_mlp_infer_f32(const float* p, int64_t ldp, const float* q, int64_t ldq,
-                                            int64_t num_nodes, const int64_t* edge_index, int64_t ld,
-                                            int64_t num_edges, const float* extra, const float* cvec,
-                                            const float* w2, const float* b2, const float* w3, const float* b3,
-                                            int32_t D, float* logits, int32_t precision, pangnn_stream_t stream) {
-  int rc = check_common("pangnn_decoder_mlp_fwd_f32", p, q, ldp, ldq, num_nodes, edge_index, ld, num_edges, extra,
-                        cvec, w2, b2, w3, b3, D);
-  if (rc) return rc;
-  PG_CHECK_ARG(precision == 0 || precision == 1, PANGNN_E_BADARG, "pangnn_decoder_mlp_infer_f32: precision must be 0 or 1");
-  if (num_edges == 0) return 0;
-  PG_CHECK_ARG(logits, PANGNN_E_BADARG, "pangnn_decoder_mlp_fwd_f32: null logits");
-  if (precision)   // bf16 matrix pipe, split operands: decoder16.hip (the first product of the training kernel)
-    return launch_decoder_infer16(p, ldp, q, ldq, edge_index, ld, num_edges, extra, cvec, w2, b2, w3, b3, logits,
-                                  (hipStream_t)stream);
-  const int64_t n_tiles = (num_edges + TE - 1) / TE;
-  int64_t grid = (n_tiles + FWD_WAVES - 1) / FWD_WAVES;
-  const int cus = grid_cus();
-  if (grid > cus) grid = cus;
-  DecParams a{p, q, (uint32_t)(ldp / 4), (uint32_t)(ldq / 4), edge_index, ld, num_edges, extra, cvec, w2, b2, w3, b3};
-  hipLaunchKernelGGL(decoder_fwd_kernel, dim3((unsigned)grid), dim3(FWD_WAVES * 64), 0, (hipStream_t)stream, a, logits,
-                     n_tiles);
-  PG_CHECK_LAUNCH("pangnn_decoder_mlp_fwd_f32");
-  return 0;
+extern "C" int pangnn_decoder_mlp_infer_f32(const float* p, int64_t ldp, const float* q, int64_t ldq, int64_t num_nodes,
+                                            const int64_t* edge_index, int64_t ld, int64_t num_edges, const float* extra,
+                                            const float* cvec, const float* w2, const float* b2, const float* w3,
+                                            const float* b3, int32_t D, float* logits, int32_t precision,
+                                            pangnn_stream_t stream) {
+  const DecArgs c{p, ldp, q, ldq, num_nodes, edge_index, ld, num_edges, extra, cvec, w2, b2, w3, b3, D};
+  return decoder_fwd("pangnn_decoder_mlp_fwd_f32", false, c, logits, precision, (hipStream_t)stream);
 }
 
-extern "C" int pangnn_decoder_mlp_fwd_f32(const float* p, int64_t ldp, const float* q, int64_t ldq,
-                                          int64_t num_nodes, const int64_t* edge_index, int64_t ld, int64_t num_edges,
-                                          const float* extra, const float* cvec, const float* w2,
-                                          const float* b2, const float* w3, const float* b3,
-                                          int32_t D, float* logits, pangnn_stream_t stream) {
-  return pangnn_decoder_mlp_infer_f32(p, ldp, q, ldq, num_nodes, edge_index, ld, num_edges, extra, cvec, w2, b2, w3, b3,
-                                      D, logits, 0, stream);
+extern "C" int pangnn_decoder_mlp_fwd_f32(const float* p, int64_t ldp, const float* q, int64_t ldq, int64_t num_nodes,
+                                          const int64_t* edge_index, int64_t ld, int64_t num_edges, const float* extra,
+                                          const float* cvec, const float* w2, const float* b2, const float* w3,
+                                          const float* b3, int32_t D, float* logits, pangnn_stream_t stream) {
+  const DecArgs c{p, ldp, q, ldq, num_nodes, edge_index, ld, num_edges, extra, cvec, w2, b2, w3, b3, D};
+  return decoder_fwd("pangnn_decoder_mlp_fwd_f32", false, c, logits, 0, (hipStream_t)stream);
 }
 
-extern "C" size_t pangnn_decoder_mlp_bwd_workspace_bytes(int64_t num_edges) {
-  (void)num_edges;
-  return (size_t)grid_cus() * SLAB * sizeof(float);
-}
+extern "C" size_t pangnn_decoder_mlp_bwd_workspace_bytes(int64_t num_edges) { return workspace_of(64, num_edges); }
 
-static int launch_bwd(const char* who, const DecParams& a, int64_t num_nodes, int32_t D, const float* g_logits,
-                      const LossParams* lp, int precision, float* part_buf, const int32_t* part_off, float* g_h1, float* g_w2, float* g_b2, float* g_w3, float* g_b3,
-                      float* g_cvec, float* loss, void* workspace, size_t workspace_bytes, hipStream_t s) {
-  PG_CHECK_ARG(g_w2 && g_b2 && g_w3 && g_b3, PANGNN_E_BADARG, "%s: null gradient output", who);
-  const int64_t num_edges = a.E;
-  PG_CHECK_ARG(precision == 0, PANGNN_E_BADARG,
-               "%s: only precision 0 (f32 MFMA) here; the bf16 matrix-pipe mode is pangnn_decoder_train_f32 + "
-               "pangnn_decoder_dgrad_f32", who);
-  const int waves = BWD_WAVES;
-  const int64_t n_tiles = (num_edges + TE - 1) / TE;
-  int64_t grid = (n_tiles + waves - 1) / waves;
-  const int cus = grid_cus();
-  if (grid > cus) grid = cus;
-  if (grid < 1) grid = 1;
-  PG_CHECK_ARG(workspace && workspace_bytes >= (size_t)grid * SLAB * sizeof(float), PANGNN_E_WORKSPACE,
-               "%s: workspace too small", who);
-  PG_CHECK_ARG(num_edges == 0 || g_h1, PANGNN_E_BADARG, "%s: null g_h1", who);
-  if (num_edges == 0) {
-    hipError_t e = hipMemsetAsync(workspace, 0, (size_t)grid * SLAB * sizeof(float), s);
-    PG_CHECK_ARG(e == hipSuccess, (int)e, "%s: memset failed", who);
-  } else {
-    PG_CHECK_ARG((part_buf == nullptr) == (part_off == nullptr), PANGNN_E_BADARG,
-                 "%s: part_buf and part_off go together", who);
-    const LossParams none{nullptr, nullptr, 0.f, nullptr};
-    const LossParams l = lp ? *lp : none;
-    const RunSumParams rs{part_buf, part_off};
-    const dim3 g((unsigned)grid), b(waves * 64);
-    float* ws = static_cast<float*>(workspace);
-    if (lp && part_buf) hipLaunchKernelGGL((decoder_bwd_kernel<true, true>), g, b, 0, s, a, g_logits, l, rs, g_h1, ws, n_tiles);
-    else if (lp) hipLaunchKernelGGL((decoder_bwd_kernel<true, false>), g, b, 0, s, a, g_logits, l, rs, g_h1, ws, n_tiles);
-    else if (part_buf) hipLaunchKernelGGL((decoder_bwd_kernel<false, true>), g, b, 0, s, a, g_logits, l, rs, g_h1, ws, n_tiles);
-    else hipLaunchKernelGGL((decoder_bwd_kernel<false, false>), g, b, 0, s, a, g_logits, l, rs, g_h1, ws, n_tiles);
-    PG_CHECK_LAUNCH(who);
-  }
-  hipLaunchKernelGGL(decoder_reduce_kernel, dim3((4096 + 194 + kWave - 1) / kWave), dim3(kSumThreads), 0, s,
-                     static_cast<const float*>(workspace), (int)grid, g_w2, g_b2, g_w3, g_cvec, g_b3, loss);
-  PG_CHECK_LAUNCH(who);
-  return 0;
-}
-
-extern "C" int pangnn_decoder_mlp_bwd_f32(const float* p, int64_t ldp, const float* q, int64_t ldq,
-                                          int64_t num_nodes, const int64_t* edge_index, int64_t ld, int64_t num_edges,
-                                          const float* extra, const float* cvec, const float* w2,
-                                          const float* b2, const float* w3, const float* b3, int32_t D,
-                                          const float* g_logits, float* g_h1, float* g_w2, float* g_b2,
-                                          float* g_w3, float* g_b3, float* g_cvec, float* part_buf,
+extern "C" int pangnn_decoder_mlp_bwd_f32(const float* p, int64_t ldp, const float* q, int64_t ldq, int64_t num_nodes,
+                                          const int64_t* edge_index, int64_t ld, int64_t num_edges, const float* extra,
+                                          const float* cvec, const float* w2, const float* b2, const float* w3,
+                                          const float* b3, int32_t D, const float* g_logits, float* g_h1, float* g_w2,
+                                          float* g_b2, float* g_w3, float* g_b3, float* g_cvec, float* part_buf,
                                           const int32_t* part_off, int32_t precision, void* workspace,
                                           size_t workspace_bytes, pangnn_stream_t stream) {
-  int rc = check_common("pangnn_decoder_mlp_bwd_f32", p, q, ldp, ldq, num_nodes, edge_index, ld, num_edges, extra,
-                        cvec, w2, b2, w3, b3, D);
-  if (rc) return rc;
-  PG_CHECK_ARG(num_edges == 0 || g_logits, PANGNN_E_BADARG, "pangnn_decoder_mlp_bwd_f32: null g_logits");
-  DecParams a{p, q, (uint32_t)(ldp / 4), (uint32_t)(ldq / 4), edge_index, ld, num_edges, extra, cvec, w2, b2, w3, b3};
-  return launch_bwd("pangnn_decoder_mlp_bwd_f32", a, num_nodes, D, g_logits, nullptr, precision, part_buf, part_off, g_h1, g_w2, g_b2, g_w3, g_b3,
-                    g_cvec, nullptr, workspace, workspace_bytes, (hipStream_t)stream);
+  const DecArgs c{p, ldp, q, ldq, num_nodes, edge_index, ld, num_edges, extra, cvec, w2, b2, w3, b3, D};
+  const GradOut o{g_h1, g_w2, g_b2, g_w3, g_b3, g_cvec, part_buf, part_off, workspace, workspace_bytes};
+  return decoder_bwd("pangnn_decoder_mlp_bwd_f32", false, c, g_logits, precision, o, (hipStream_t)stream);
 }
 
-extern "C" int pangnn_decoder_mlp_loss_f32(const float* p, int64_t ldp, const float* q, int64_t ldq,
-                                           int64_t num_nodes, const int64_t* edge_index, int64_t ld,
-                                           int64_t num_edges, const float* extra, const float* cvec,
-                                           const float* w2, const float* b2, const float* w3, const float* b3,
-                                           int32_t D, const float* y, const float* pos_weight, int64_t denom,
-                                           float* logits, float* loss, float* g_h1, float* g_w2, float* g_b2,
-                                           float* g_w3, float* g_b3, float* g_cvec, float* part_buf,
+extern "C" int pangnn_decoder_mlp_loss_f32(const float* p, int64_t ldp, const float* q, int64_t ldq, int64_t num_nodes,
+                                           const int64_t* edge_index, int64_t ld, int64_t num_edges, const float* extra,
+                                           const float* cvec, const float* w2, const float* b2, const float* w3,
+                                           const float* b3, int32_t D, const float* y, const float* pos_weight,
+                                           int64_t denom, float* logits, float* loss, float* g_h1, float* g_w2,
+                                           float* g_b2, float* g_w3, float* g_b3, float* g_cvec, float* part_buf,
                                            const int32_t* part_off, int32_t precision, void* workspace,
                                            size_t workspace_bytes, pangnn_stream_t stream) {
-  int rc = check_common("pangnn_decoder_mlp_loss_f32", p, q, ldp, ldq, num_nodes, edge_index, ld, num_edges, extra,
-                        cvec, w2, b2, w3, b3, D);
-  if (rc) return rc;
-  PG_CHECK_ARG(denom > 0 && loss && (num_edges == 0 || (y && logits)), PANGNN_E_BADARG,
-               "pangnn_decoder_mlp_loss_f32: bad denom / null pointer");
-  DecParams a{p, q, (uint32_t)(ldp / 4), (uint32_t)(ldq / 4), edge_index, ld, num_edges, extra, cvec, w2, b2, w3, b3};
-  LossParams lp{y, pos_weight, 1.0f / (float)denom, logits};
-  return launch_bwd("pangnn_decoder_mlp_loss_f32", a, num_nodes, D, nullptr, &lp, precision, part_buf, part_off, g_h1, g_w2, g_b2, g_w3, g_b3,
-                    g_cvec, loss, workspace, workspace_bytes, (hipStream_t)stream);
+  const DecArgs c{p, ldp, q, ldq, num_nodes, edge_index, ld, num_edges, extra, cvec, w2, b2, w3, b3, D};
+  const GradOut o{g_h1, g_w2, g_b2, g_w3, g_b3, g_cvec, part_buf, part_off, workspace, workspace_bytes};
+  return decoder_loss("pangnn_decoder_mlp_loss_f32", false, c, y, pos_weight, denom, logits, loss, precision, o,
+                      (hipStream_t)stream);
+}
+
+extern "C" int pangnn_decoder_nd_supported(int32_t D) { return nd_supported(D) ? 1 : 0; }
+
+extern "C" int pangnn_decoder_nd_fwd_f32(const float* p, int64_t ldp, const float* q, int64_t ldq, int64_t num_nodes,
+                                         const int64_t* edge_index, int64_t ld, int64_t num_edges, const float* extra,
+                                         const float* cvec, const float* w2, const float* b2, const float* w3,
+                                         const float* b3, int32_t D, float* logits, pangnn_stream_t stream) {
+  const DecArgs c{p, ldp, q, ldq, num_nodes, edge_index, ld, num_edges, extra, cvec, w2, b2, w3, b3, D};
+  return decoder_fwd("pangnn_decoder_nd_fwd_f32", true, c, logits, 0, (hipStream_t)stream);
+}
+
+extern "C" size_t pangnn_decoder_nd_bwd_workspace_bytes(int32_t D, int64_t num_edges) {
+  return nd_supported(D) ? workspace_of(D, num_edges) : 0;
+}
+
+extern "C" int pangnn_decoder_nd_bwd_f32(const float* p, int64_t ldp, const float* q, int64_t ldq, int64_t num_nodes,
+                                         const int64_t* edge_index, int64_t ld, int64_t num_edges, const float* extra,
+                                         const float* cvec, const float* w2, const float* b2, const float* w3,
+                                         const float* b3, int32_t D, const float* g_logits, float* g_h1, float* g_w2,
+                                         float* g_b2, float* g_w3, float* g_b3, float* g_cvec, float* part_buf,
+                                         const int32_t* part_off, void* workspace, int64_t workspace_bytes,
+                                         pangnn_stream_t stream) {
+  const DecArgs c{p, ldp, q, ldq, num_nodes, edge_index, ld, num_edges, extra, cvec, w2, b2, w3, b3, D};
+  const GradOut o{g_h1, g_w2, g_b2, g_w3, g_b3, g_cvec, part_buf, part_off, workspace, ws_size(workspace_bytes)};
+  return decoder_bwd("pangnn_decoder_nd_bwd_f32", true, c, g_logits, 0, o, (hipStream_t)stream);
+}
+
+extern "C" int pangnn_decoder_nd_loss_f32(const float* p, int64_t ldp, const float* q, int64_t ldq, int64_t num_nodes,
+                                          const int64_t* edge_index, int64_t ld, int64_t num_edges, const float* extra,
+                                          const float* cvec, const float* w2, const float* b2, const float* w3,
+                                          const float* b3, int32_t D, const float* y, const float* pos_weight,
+                                          int64_t denom, float* logits, float* loss, float* g_h1, float* g_w2,
+                                          float* g_b2, float* g_w3, float* g_b3, float* g_cvec, float* part_buf,
+                                          const int32_t* part_off, void* workspace, int64_t workspace_bytes,
+                                          pangnn_stream_t stream) {
+  const DecArgs c{p, ldp, q, ldq, num_nodes, edge_index, ld, num_edges, extra, cvec, w2, b2, w3, b3, D};
+  const GradOut o{g_h1, g_w2, g_b2, g_w3, g_b3, g_cvec, part_buf, part_off, workspace, ws_size(workspace_bytes)};
+  return decoder_loss("pangnn_decoder_nd_loss_f32", true, c, y, pos_weight, denom, logits, loss, 0, o, (hipStream_t)stream);
 }

@@ -30,8 +30,9 @@ KERNEL_TIMER = None
 #     against fp64), 0.78x the time of mode 0 because f32 MFMA shares the SIMD's vector lanes;
 # 0 = v_mfma_f32_32x32x2_f32 everywhere (bit-exact fp32 FMA chains).  Environment: PANGNN_DECODER_PRECISION.
 DECODER_PRECISION = int(os.environ.get("PANGNN_DECODER_PRECISION", "1"))
-# node_dim other than 64 with fused per-edge MLP kernels (csrc/decoder_nd.hip): f32 MFMA in both precision modes, float32
-# P | Q rows, the autograd-Function (ctypes) route.  A width taken out of this tuple takes the layer-by-layer route again.
+# node_dim other than 64 with fused per-edge MLP kernels (the width template of csrc/decoder.hip): f32 MFMA in both precision
+# modes, float32 P | Q rows, the autograd-Function (ctypes) route.  A width taken out of this tuple takes the layer-by-layer
+# route again.
 DECODER_ND_WIDTHS = (32, 128)
 
 
@@ -660,63 +661,28 @@ def _decoder_operands(p, q, extra, cvec, w2, b2, w3, b3, y=None, pos_weight=None
     return p, q, ex, cv, w2, b2, w3, b3, y, (None if pw is None else pw.reshape(-1))
 
 
+def _decoder_head(p, q, st: EdgeStructure, ex, cv, w2, b2, w3, b3):
+    """(p, ldp, q, ldq, num_nodes, edge_index, ld, num_edges, extra, cvec, w2, b2, w3, b3, D): what the ctypes decoder entry
+    points begin with"""
+    e = st.num_edges
+    return (p.data_ptr(), p.stride(0), q.data_ptr(), q.stride(0), max(p.shape[0], q.shape[0]), st.edge_index.data_ptr(),
+            e, e, _lib.ptr(ex), _lib.ptr(cv), w2.data_ptr(), b2.data_ptr(), w3.data_ptr(), b3.data_ptr(), p.shape[1])
+
+
 def _decoder_f32(p, q, st: EdgeStructure, ex, cv, w2, b2, w3, b3, y=None, pw=None, denom=0, g_logits=None,
                  out_p=None, out_q=None, need_p=True, need_q=True, live=None):
-    """_decoder_train16's strict-fp32 counterpart (DECODER_PRECISION 0), same arguments and result: one launch of
-    pangnn_decoder_mlp_loss_f32 (y given: logits, loss and every gradient) or pangnn_decoder_mlp_bwd_f32 (the given
+    """_decoder_train16's strict-fp32 counterpart (csrc/decoder.hip), same arguments and result: node_dim 64 under
+    DECODER_PRECISION 0 (pangnn_decoder_mlp_*, which take `precision`) and the widths of DECODER_ND_WIDTHS in either mode
+    (pangnn_decoder_nd_*).  One launch of *_loss_f32 (y given: logits, loss and every gradient) or *_bwd_f32 (the given
     dL/dlogits), which writes dL/dh1 [E, D] and, for a source-sorted list, per-run partial rows; then dL/dP by source and
-    dL/dQ by target, into `out_p` / `out_q` when given (e.g. the column windows of one [N, 2D] gradient).  A padded batch
-    (`live`) needs mode 1."""
-    assert live is None
-    lib = _lib.load()
-    dev = p.device
-    e, d = st.num_edges, p.shape[1]
-    fused = y is not None
-    logits = torch.empty(e, dtype=torch.float32, device=dev) if fused else None
-    loss = torch.empty(1, dtype=torch.float32, device=dev) if fused else None
-    g_h1 = torch.empty(e, d, dtype=torch.float32, device=dev)
-    g_w2 = torch.empty_like(w2)
-    g_b2, g_w3, g_b3 = torch.empty_like(b2), torch.empty_like(w3), torch.empty_like(b3)
-    g_cv = None if cv is None else torch.empty_like(cv)
-    plan = st.runsum_plan()
-    parts = None if plan is None else torch.empty(plan.n_parts, d, dtype=torch.float32, device=dev)
-    with _lib.device_guard(dev):
-        ws_bytes = lib.pangnn_decoder_mlp_bwd_workspace_bytes(e)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        head = (p.data_ptr(), p.stride(0), q.data_ptr(), q.stride(0), max(p.shape[0], q.shape[0]),
-                st.edge_index.data_ptr(), e, e, _lib.ptr(ex), _lib.ptr(cv), w2.data_ptr(), b2.data_ptr(), w3.data_ptr(),
-                b3.data_ptr(), d)
-        tail = (_lib.ptr(g_h1), g_w2.data_ptr(), g_b2.data_ptr(), g_w3.data_ptr(), g_b3.data_ptr(), _lib.ptr(g_cv),
-                _lib.ptr(parts), None if plan is None else plan.part_off.data_ptr(), DECODER_PRECISION, ws.data_ptr(),
-                ws_bytes, _lib.stream_ptr())
-        ev = _timer_start("dec.bwd")
-        if fused:
-            _lib.check(lib.pangnn_decoder_mlp_loss_f32(*head, _lib.ptr(y), _lib.ptr(pw), int(denom), _lib.ptr(logits),
-                                                       loss.data_ptr(), *tail), "pangnn_decoder_mlp_loss_f32")
-        else:
-            _lib.check(lib.pangnn_decoder_mlp_bwd_f32(*head, _lib.ptr(g_logits), *tail), "pangnn_decoder_mlp_bwd_f32")
-        _timer_stop("dec.bwd", ev)
-    gp = gq = None
-    if need_p:
-        if plan is not None:       # per-run partial rows came out of the kernel: short contiguous sum
-            gp = _sum_parts(plan, parts, p.shape[0], out_p if out_p is not None else torch.empty(p.shape[0], d, device=dev))
-        else:
-            gp = segment_sum_rows(st.by_src, g_h1, 0, d, p.shape[0], out=out_p)
-    if need_q:
-        gq = segment_sum_rows(st.by_dst, g_h1, 0, d, q.shape[0], out=out_q)
-    return loss, logits, gp, gq, g_cv, g_w2, g_b2, g_w3, g_b3
-
-
-def _decoder_nd(p, q, st: EdgeStructure, ex, cv, w2, b2, w3, b3, y=None, pw=None, denom=0, g_logits=None,
-                out_p=None, out_q=None, need_p=True, need_q=True, live=None):
-    """_decoder_f32 for the widths of DECODER_ND_WIDTHS (csrc/decoder_nd.hip), same arguments and result: one launch of
-    pangnn_decoder_nd_loss_f32 (y given) or pangnn_decoder_nd_bwd_f32 (the given dL/dlogits), then dL/dP by source (from the
-    per-run partial rows of a source-sorted list) and dL/dQ by target.  A padded batch (`live`) needs node_dim 64."""
+    dL/dQ by target, into `out_p` / `out_q` when given (e.g. the column windows of one [N, 2D] gradient)."""
     if live is not None:
-        raise ValueError("live= (a padded fixed-shape batch) needs node_dim 64")
+        raise ValueError("live= (a padded fixed-shape batch) needs node_dim 64 in the default precision mode")
     lib = _lib.load()
     dev = p.device
     e, d = st.num_edges, p.shape[1]
+    nd = d in DECODER_ND_WIDTHS
+    name = "pangnn_decoder_nd_" if nd else "pangnn_decoder_mlp_"
     fused = y is not None
     logits = torch.empty(e, dtype=torch.float32, device=dev) if fused else None
     loss = torch.empty(1, dtype=torch.float32, device=dev) if fused else None
@@ -727,20 +693,18 @@ def _decoder_nd(p, q, st: EdgeStructure, ex, cv, w2, b2, w3, b3, y=None, pw=None
     plan = st.runsum_plan() if (need_p and e > 0) else None
     parts = None if plan is None else torch.empty(plan.n_parts, d, dtype=torch.float32, device=dev)
     with _lib.device_guard(dev):
-        ws_bytes = lib.pangnn_decoder_nd_bwd_workspace_bytes(d, e)
+        ws_bytes = lib.pangnn_decoder_nd_bwd_workspace_bytes(d, e) if nd else lib.pangnn_decoder_mlp_bwd_workspace_bytes(e)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        head = (p.data_ptr(), p.stride(0), q.data_ptr(), q.stride(0), max(p.shape[0], q.shape[0]),
-                st.edge_index.data_ptr(), e, e, _lib.ptr(ex), _lib.ptr(cv), w2.data_ptr(), b2.data_ptr(), w3.data_ptr(),
-                b3.data_ptr(), d)
+        head = _decoder_head(p, q, st, ex, cv, w2, b2, w3, b3)
         tail = (_lib.ptr(g_h1), g_w2.data_ptr(), g_b2.data_ptr(), g_w3.data_ptr(), g_b3.data_ptr(), _lib.ptr(g_cv),
-                _lib.ptr(parts), None if plan is None else plan.part_off.data_ptr(), ws.data_ptr(), ws_bytes,
-                _lib.stream_ptr())
+                _lib.ptr(parts), None if plan is None else plan.part_off.data_ptr()) + (() if nd else (DECODER_PRECISION,)) + \
+               (ws.data_ptr(), ws_bytes, _lib.stream_ptr())
         ev = _timer_start("dec.bwd")
         if fused:
-            _lib.check(lib.pangnn_decoder_nd_loss_f32(*head, _lib.ptr(y), _lib.ptr(pw), int(denom), _lib.ptr(logits),
-                                                      loss.data_ptr(), *tail), "pangnn_decoder_nd_loss_f32")
+            _lib.check(getattr(lib, name + "loss_f32")(*head, _lib.ptr(y), _lib.ptr(pw), int(denom), _lib.ptr(logits),
+                                                       loss.data_ptr(), *tail), name + "loss_f32")
         else:
-            _lib.check(lib.pangnn_decoder_nd_bwd_f32(*head, _lib.ptr(g_logits), *tail), "pangnn_decoder_nd_bwd_f32")
+            _lib.check(getattr(lib, name + "bwd_f32")(*head, _lib.ptr(g_logits), *tail), name + "bwd_f32")
         _timer_stop("dec.bwd", ev)
     gp = gq = None
     if need_p:
@@ -759,12 +723,11 @@ def _decoder_nd(p, q, st: EdgeStructure, ex, cv, w2, b2, w3, b3, y=None, pw=None
 
 
 def _decoder_grads(p, q, st: EdgeStructure, ex, cv, w2, b2, w3, b3, joint: bool, **kw):
-    """the training decoder of the current DECODER_PRECISION (_decoder_train16 / _decoder_f32) on normalised operands, or
-    _decoder_nd in either mode at the widths of DECODER_ND_WIDTHS;
+    """the training decoder on normalised operands: _decoder_train16 at node_dim 64 under DECODER_PRECISION 1, else
+    _decoder_f32;
     `joint`: p and q are the column windows of one [N, 2D] table and dL/dP | dL/dQ come back as ONE [N, 2D] matrix in
     the gp slot (gq None).  Returns (loss, logits, gp, gq, g_cv, g_w2, g_b2, g_w3, g_b3)."""
-    train = _decoder_nd if p.shape[1] in DECODER_ND_WIDTHS else \
-        _decoder_train16 if DECODER_PRECISION == 1 else _decoder_f32
+    train = _decoder_train16 if (DECODER_PRECISION == 1 and p.shape[1] not in DECODER_ND_WIDTHS) else _decoder_f32
     if not joint:
         return train(p, q, st, ex, cv, w2, b2, w3, b3, **kw)
     d = p.shape[1]
@@ -789,25 +752,15 @@ class _DecoderMLP(torch.autograd.Function):
         logits = torch.empty(e, dtype=torch.float32, device=p.device)
         with _lib.device_guard(p.device):
             ev = _timer_start("dec.fwd")
+            head = _decoder_head(p, q, st, ex, cv, w2, b2, w3, b3)
             if d in DECODER_ND_WIDTHS:
-                _lib.check(lib.pangnn_decoder_nd_fwd_f32(p.data_ptr(), p.stride(0), q.data_ptr(), q.stride(0),
-                                                         max(p.shape[0], q.shape[0]), st.edge_index.data_ptr(), e, e,
-                                                         _lib.ptr(ex), _lib.ptr(cv), w2.data_ptr(), b2.data_ptr(),
-                                                         w3.data_ptr(), b3.data_ptr(), d, _lib.ptr(logits),
-                                                         _lib.stream_ptr()), "pangnn_decoder_nd_fwd_f32")
-            elif p.dtype in ROWS16:
-                _lib.check(lib.pangnn_decoder_mlp_infer_mixed(p.data_ptr(), p.stride(0), q.data_ptr(), q.stride(0), _dt(p),
-                                                              max(p.shape[0], q.shape[0]), st.edge_index.data_ptr(), e,
-                                                              e, _lib.ptr(ex), _lib.ptr(cv), w2.data_ptr(),
-                                                              b2.data_ptr(), w3.data_ptr(), b3.data_ptr(), d,
-                                                              _lib.ptr(logits), _lib.stream_ptr()),
-                           "pangnn_decoder_mlp_infer_mixed")
+                _lib.check(lib.pangnn_decoder_nd_fwd_f32(*head, _lib.ptr(logits), _lib.stream_ptr()),
+                           "pangnn_decoder_nd_fwd_f32")
+            elif p.dtype in ROWS16:         # the tables' storage type goes in after the four table arguments
+                _lib.check(lib.pangnn_decoder_mlp_infer_mixed(*head[:4], _dt(p), *head[4:], _lib.ptr(logits),
+                                                              _lib.stream_ptr()), "pangnn_decoder_mlp_infer_mixed")
             else:
-                _lib.check(lib.pangnn_decoder_mlp_infer_f32(p.data_ptr(), p.stride(0), q.data_ptr(), q.stride(0),
-                                                            max(p.shape[0], q.shape[0]), st.edge_index.data_ptr(), e, e,
-                                                            _lib.ptr(ex), _lib.ptr(cv), w2.data_ptr(), b2.data_ptr(),
-                                                            w3.data_ptr(), b3.data_ptr(), d, _lib.ptr(logits),
-                                                            DECODER_PRECISION, _lib.stream_ptr()),
+                _lib.check(lib.pangnn_decoder_mlp_infer_f32(*head, _lib.ptr(logits), DECODER_PRECISION, _lib.stream_ptr()),
                            "pangnn_decoder_mlp_infer_f32")
             _timer_stop("dec.fwd", ev)
         ctx.st, ctx.joint = st, pq_joint

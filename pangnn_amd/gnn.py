@@ -216,7 +216,8 @@ class AlternateGCN(nn.Module):
 
     def _fused_width(self) -> bool:
         """node_dim is a width the fused per-edge MLP kernels are built for: 64 (csrc/decoder.hip, decoder16.hip) or one of
-        PF.DECODER_ND_WIDTHS (csrc/decoder_nd.hip: f32 matrix pipe, float32 P | Q rows, no DeferredLogits)"""
+        PF.DECODER_ND_WIDTHS (the width template of csrc/decoder.hip in both precision modes: f32 matrix pipe, float32 P | Q rows,
+        no DeferredLogits)"""
         d = self.mlp[2].in_features
         return d == 64 or d in PF.DECODER_ND_WIDTHS
 

@@ -1,7 +1,9 @@
-"""The fused MLP link decoder for node_dim 32 and 128 on the GPU (csrc/decoder_nd.hip through pangnn_amd.functional and
+"""The width template of the strict-fp32 MLP link decoder on the GPU (csrc/decoder.hip through pangnn_amd.functional and
 AlternateGCN): bit for bit against a float64 evaluation on the exact grid of tests/test_decoder_run_sums.py (whose exactness at
-these widths tests/test_decoder_widths_host.py proves on the CPU), the fused loss on the same grids, the whole model against the
-oracle, the route a model takes, non-finite values, and bf16 autocast."""
+these widths tests/test_decoder_widths_host.py proves on the CPU) and the fused loss on the same grids at node_dim 32, 64
+(the strict-fp32 mode) and 128; at 32 and 128 the whole model against the oracle, the route a model takes, non-finite values,
+and bf16 autocast."""
+import contextlib
 import functools
 
 import pytest
@@ -9,7 +11,7 @@ import torch
 import torch.nn.functional as F
 
 from test_decoder_run_sums import SUMS, decoder_reference
-from test_decoder_widths_host import EXACT_SETS, WIDTHS, exact_inputs, set_id
+from test_decoder_widths_host import EXACT_SETS, EXACT_WIDTHS, WIDTHS, exact_inputs, set_id
 from test_hip_parity import _check_logits_loss_grads_against_oracle, _pair, close
 
 pytestmark = pytest.mark.gpu
@@ -18,6 +20,17 @@ NAN = float("nan")
 
 def dev():
     return torch.device("cuda:0")
+
+
+@contextlib.contextmanager
+def _strict_fp32():
+    """PF.DECODER_PRECISION = 0 for the duration: node_dim 64 then runs the template's instance (32 and 128 do in any mode)"""
+    from pangnn_amd import functional as PF
+    old, PF.DECODER_PRECISION = PF.DECODER_PRECISION, 0
+    try:
+        yield
+    finally:
+        PF.DECODER_PRECISION = old
 
 
 def _f32(x):
@@ -61,6 +74,7 @@ def _decoder_mlp(td, st, extra, g):
 # 1. bit for bit on the exact grid
 # ------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("s", EXACT_SETS, ids=set_id)
+@_strict_fp32()
 def test_logits_and_gradients_bit_for_bit_on_the_exact_grid(s):
     """PF.decoder_mlp and its backward under a given dL/dlogit: torch.equal against the float64 reference, no tolerance.  The
     list sorted by source (run-sum parts inside the kernel) and as drawn (segment sums by source and by target); "one-source"
@@ -85,7 +99,8 @@ def test_logits_and_gradients_bit_for_bit_on_the_exact_grid(s):
         assert torch.equal(out, out2) and all(torch.equal(got[k], got2[k]) for k in got), name
 
 
-@pytest.mark.parametrize("d", WIDTHS)
+@pytest.mark.parametrize("d", EXACT_WIDTHS)
+@_strict_fp32()
 def test_empty_list(d):
     """num_edges == 0: no logits, every gradient zero (the reduction runs over a zeroed workspace)"""
     from pangnn_amd.graph import EdgeStructure
@@ -102,6 +117,7 @@ def test_empty_list(d):
 # 2. the fused loss on the same grids
 # ------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("s", EXACT_SETS, ids=set_id)
+@_strict_fp32()
 def test_fused_loss_on_the_exact_grid(s):
     """PF.decoder_loss with w3 / 64 (still exact; |logit| stays where the sigmoid is not saturated), y ~ Bernoulli(0.3),
     pos_weight 2.5, denom = E.  Logits: the float64 reference's and the forward kernel's, bit for bit.  Loss: 1e-6 + 1e-5 |ref|.

@@ -1,6 +1,7 @@
-"""The fused MLP link decoder for node_dim 32 and 128 (csrc/decoder_nd.hip), the part that needs no GPU: which widths the
-entry points take, their argument checks (fake pointers, nothing launched), which models pick the kernels, and the proof that
-every input set the bit-for-bit GPU cases of tests/test_decoder_widths.py use is exact in float32 in any order of summation.
+"""The width template of the strict-fp32 MLP link decoder (csrc/decoder.hip), the part that needs no GPU: which widths the
+pangnn_decoder_nd_* entry points (node_dim 32 and 128) take, their argument checks (fake pointers, nothing launched), which
+models pick the kernels, and the proof that every input set the bit-for-bit GPU cases of tests/test_decoder_widths.py use, the
+node_dim 64 instance's included, is exact in float32 in any order of summation.
 
 The input sets are defined here (`exact_inputs`) and imported by the GPU file."""
 import functools
@@ -13,12 +14,13 @@ import torch
 from pangnn_amd import _lib
 from test_decoder_run_sums import _assert_exact_in_any_order, decoder_reference, g_grid, grid_edges, grid_tables
 
-WIDTHS = (32, 128)
+WIDTHS = (32, 128)                          # the widths of the pangnn_decoder_nd_* entry points and of the model gating
+EXACT_WIDTHS = (32, 64, 128)                # the template's instances; 64 is what pangnn_decoder_mlp_* run at precision 0
 N = 97
 EXACT_E = (1, 31, 32, 33, 1000, 70001)     # around one tile; 70 001: a last tile of 17 edges, more tiles than 256 workgroups x
-#                                            waves hold at both widths, so waves walk several tiles and every workgroup has a slab
-EXACT_SETS = [(d, skip, "list", e) for d in WIDTHS for skip in (False, True) for e in EXACT_E] + \
-             [(d, skip, kind, 1000) for d in WIDTHS for skip in (False, True) for kind in ("one-source", "own-source")]
+#                                            waves hold at every width, so waves walk several tiles and every workgroup has a slab
+EXACT_SETS = [(d, skip, "list", e) for d in EXACT_WIDTHS for skip in (False, True) for e in EXACT_E] + \
+             [(d, skip, kind, 1000) for d in EXACT_WIDTHS for skip in (False, True) for kind in ("one-source", "own-source")]
 
 
 def set_id(s):
@@ -168,7 +170,7 @@ def test_model_gating():
 
 
 # ------------------------------------------------------------------------------------------------------------------
-# the exact grid at widths 32 and 128
+# the exact grid at widths 32, 64 and 128
 # ------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("s", EXACT_SETS, ids=set_id)
 def test_grid_is_exact_in_float32_at_both_widths(s):

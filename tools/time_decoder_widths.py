@@ -1,5 +1,5 @@
 """AlternateGCN(dims=[D, 128]) at node_dim D = 32 and 128: `loss_and_logits` + backward (the training step without the
-optimizer) and the eval-mode forward, with the fused per-edge MLP decoder (csrc/decoder_nd.hip) against the layer-by-layer
+optimizer) and the eval-mode forward, with the fused per-edge MLP decoder (the width template of csrc/decoder.hip) against the layer-by-layer
 route (`fused_decoder=False`: gather-concat, torch Linear / relu_ / Linear), on two simulated similarity graphs:
 
   * small: config 2's size, `simulate_graph(1000, 5, 0.3, 10, 2)` (N = 5 000, E ~ 4.5e4);
