@@ -4,7 +4,7 @@
 // These are HBM-bound (0.25 flop/B at K = 64): a library GEMM tuned for square problems leaves an
 // order of magnitude on the table (hipBLASLt: 1.7 - 3.3 ms for 0.77 GB at N = 1e6).  Here one wave
 // owns 32 consecutive rows: row-contiguous 16-byte loads into a padded LDS tile, w resident in LDS,
-// f32 MFMA 32x32x2 (exact fp32 FMA chains), output rows stored as 128-byte segments.
+// products on the bf16 matrix pipe over exact three-term operand splits (see Split3), output rows stored as 128-byte segments.
 // The weight gradient keeps its [M,K] accumulator in registers across all of a wave's tiles and is
 // reduced over waves and workgroups in a fixed order (slabs), so it is bitwise reproducible.
 #include "common.h"
@@ -36,7 +36,7 @@ __device__ __forceinline__ void st_f32(float* ubase, uint32_t byte_off, float v)
   *reinterpret_cast<float*>(reinterpret_cast<char*>(ubase) + byte_off) = v;
 }
 
-// ---- storage types.  Arithmetic is fp32 everywhere (f32 MFMA); a matrix may be STORED as bfloat16 (config 5's
+// ---- storage types.  Arithmetic is fp32 everywhere (fp32 operands, fp32 accumulators); a matrix may be STORED as bfloat16 (config 5's
 // autocast: the reference's Linear outputs are bf16 tensors, gnn.py:93,111,173 under accelerate's mixed precision):
 // half the HBM bytes of the row streams these kernels are bound by.  bf16 -> f32 is a shift, f32 -> bf16 rounds to
 // nearest even.  Elem<T>: 4 consecutive elements as raw registers (converted only when they go to LDS, so the
@@ -162,64 +162,25 @@ __device__ __forceinline__ void store_rows(const RowRegs<C, T>& rg, int lane, fl
   }
 }
 
-// Waves per workgroup of the forward kernel.  Measured at N = 1e6: 4 waves per CU
-// (one per SIMD) is the fastest arrangement — an f32 MFMA occupies its SIMD's vector lanes, so a second wave
-// on the SIMD cannot hide the first one's epilogue, it only adds LDS / issue contention (8 waves +5..10 %,
-// 12 waves +30 %).
+// Waves per workgroup of the forward kernel.  Measured at N = 1e6 while the product still ran on v_mfma_f32_32x32x2_f32
+// (until late round 3): 4 waves per CU (one per SIMD) is the fastest arrangement — that instruction occupies its SIMD's
+// vector lanes, so a second wave on the SIMD could not hide the first one's epilogue, it only added LDS / issue
+// contention (8 waves +5..10 %, 12 waves +30 %).
 template <int K, int M>
 struct FwdGeo {
   static constexpr int KS = K + 4;
   // (8 waves for K = 64 measured: no gain — these kernels are at their HBM time.)  128 x 128: the three split images of the
-  // weight take 102 KB, which leaves room for THREE 16.5 KB row tiles — three waves on the split-bf16 product beat four on
-  // v_mfma_f32_32x32x2_f32 (round 5, N = 1e6: forward 0.23-0.25 ms vs 0.30, dL/dx + dL/dW 0.65 vs 0.71)
+  // weight take 102 KB, which leaves room for THREE 16.5 KB row tiles — three waves on the split-bf16 product beat the four
+  // that v_mfma_f32_32x32x2_f32 on an unsplit 66 KB weight had room for (round 5, N = 1e6: forward 0.23-0.25 ms vs 0.30,
+  // dL/dx + dL/dW 0.65 vs 0.71)
   static constexpr int WAVES = (K == 128 && M == 128) ? 3 : 4;
 };
 
-// one 32-row tile out of LDS: acc[b] = x_tile . w[32b .. 32b+32)^T.  Operand fragments of k-step i+1 are read
-// from LDS before the 4*M/32 MFMAs of step i are issued (sched_barrier keeps that order).
-template <int K, int M>
-__device__ __forceinline__ void tile_product(const float* Xt, const float* Wl, int r, int hh, f32x16 (&acc)[M / 32]) {
-  constexpr int KS = K + 4;
-#pragma unroll
-  for (int b = 0; b < M / 32; ++b)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[b][i] = 0.f;
-  const float* xa = Xt + r * KS + 4 * (K / 8) * hh;
-  const float* wb = Wl + r * KS + 4 * (K / 8) * hh;
-  float4 a = *reinterpret_cast<const float4*>(xa);
-  float4 bw[M / 32];
-#pragma unroll
-  for (int b = 0; b < M / 32; ++b) bw[b] = *reinterpret_cast<const float4*>(wb + 32 * b * KS);
-#pragma unroll
-  for (int i = 0; i < K / 8; ++i) {
-    float4 an = a, bn[M / 32];
-#pragma unroll
-    for (int b = 0; b < M / 32; ++b) bn[b] = bw[b];
-    if (i + 1 < K / 8) {
-      an = *reinterpret_cast<const float4*>(xa + 4 * (i + 1));
-#pragma unroll
-      for (int b = 0; b < M / 32; ++b) bn[b] = *reinterpret_cast<const float4*>(wb + 32 * b * KS + 4 * (i + 1));
-    }
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int b = 0; b < M / 32; ++b) {
-      acc[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, bw[b].x, acc[b], 0, 0, 0);
-      acc[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, bw[b].y, acc[b], 0, 0, 0);
-      acc[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, bw[b].z, acc[b], 0, 0, 0);
-      acc[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, bw[b].w, acc[b], 0, 0, 0);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    a = an;
-#pragma unroll
-    for (int b = 0; b < M / 32; ++b) bw[b] = bn[b];
-  }
-}
-
-// ---- the same product on the bf16 matrix pipe with fp32-exact operand handling (wherever its weight images fit in
-// LDS, WImg::X3; the f32-MFMA product above otherwise).  v_mfma_f32_32x32x2_f32 runs at 1/16 of the bf16 rate and holds
-// its SIMD for 16 passes: at N = 1e6 a 128 x 64 layer is 1.6e10 flop = 0.10 ms of matrix time at peak, 0.20 ms measured
-// — above the layers' HBM time once their row streams are short (the generated first layer reads 8 bytes per row).
-// Here both operands are split into three bf16 terms by truncation (x = hi + mid + lo EXACTLY: 8 + 8 + 8 significand
+// ---- every product of this file: the bf16 matrix pipe with fp32-exact operand handling.  (Until round 5 shapes whose
+// weight images did not fit in LDS ran on v_mfma_f32_32x32x2_f32 instead.  That instruction runs at 1/16 of the bf16 rate
+// and holds its SIMD for 16 passes: at N = 1e6 a 128 x 64 layer is 1.6e10 flop = 0.10 ms of matrix time at peak, 0.20 ms
+// measured — above the layers' HBM time once their row streams are short; the generated first layer reads 8 bytes per row.)
+// Both operands are split into three bf16 terms by truncation (x = hi + mid + lo EXACTLY: 8 + 8 + 8 significand
 // bits) and the six partial products of order <= 2^-16 are accumulated in fp32 by v_mfma_f32_32x32x16_bf16, smallest
 // first; the three dropped terms (mid.lo, lo.mid, lo.lo) are <= 2^-23 |x||w| — below fp32's own rounding of the
 // product.  Weights are split once per workgroup into three LDS images [M][K+8] bf16; a tile's x values are split as
@@ -249,54 +210,64 @@ __device__ __forceinline__ Split3 split8(const float4& f0, const float4& f1) {
   return r;
 }
 
-// floats of LDS the weight image of a [M][K] layer takes
+// floats of LDS the three split images of a [M][K] weight take
 template <int K, int M>
 struct WImg {
   static constexpr int WS = K + 8;                                     // bf16 row stride of a split image
-  // 128 x 128: three 34 KB images + three 16.5 KB row tiles (FwdGeo: three waves) = 152 KB of the 160 KB; with four tiles it
-  // does not fit and the f32 product is used
-  static constexpr bool X3 = (3 * M * WS * 2 + FwdGeo<K, M>::WAVES * 32 * (K + 4) * 4 <= 156 * 1024);
-  static constexpr int FLOATS = X3 ? (3 * M * WS + 1) / 2 : M * (K + 4);
+  static constexpr int FLOATS = (3 * M * WS + 1) / 2;
+  // 128 x 128: three 34 KB images + three 16.5 KB row tiles (FwdGeo: three waves) = 152 KB of the 160 KB; a fourth tile
+  // would not fit.  There is no other product to fall back on: a shape that does not fit does not compile
+  static_assert(3 * M * WS * 2 + FwdGeo<K, M>::WAVES * 32 * (K + 4) * 4 <= 156 * 1024,
+                "the three weight images and FwdGeo::WAVES row tiles must fit in LDS");
 };
 
 // stage w into LDS: element (m, k) of the [M][K] operand is w[m * sm + k * sk] (sk = 1: row-major [M][K]; sm = 1: the
 // transpose of a row-major [K][M])
 template <int K, int M>
 __device__ __forceinline__ void stage_w(const float* __restrict__ w, int sm, int sk, float* Wl, int n_threads) {
-  if constexpr (WImg<K, M>::X3) {
-    constexpr int WS = WImg<K, M>::WS, IMG = M * WS;
-    unsigned short* W3 = reinterpret_cast<unsigned short*>(Wl);
-    // eight weight loads in flight per thread: on a mini-batch (a few workgroups, every one of them staging w before its
-    // first tile) the loop of dependent load -> split -> store rounds was most of the kernel (13-16 us for 900 rows)
+  constexpr int WS = WImg<K, M>::WS, IMG = M * WS;
+  unsigned short* W3 = reinterpret_cast<unsigned short*>(Wl);
+  // eight weight loads in flight per thread: on a mini-batch (a few workgroups, every one of them staging w before its
+  // first tile) the loop of dependent load -> split -> store rounds was most of the kernel (13-16 us for 900 rows)
 #pragma unroll 8
-    for (int i = threadIdx.x; i < M * K; i += n_threads) {
-      const int m = sk == 1 ? i / K : i % M, k = sk == 1 ? i % K : i / M;       // consecutive threads: consecutive addresses
-      const float v = w[m * sm + k * sk];
-      const uint32_t a = __builtin_bit_cast(uint32_t, v);
-      const float r1 = v - __builtin_bit_cast(float, a & 0xffff0000u);
-      const uint32_t b = __builtin_bit_cast(uint32_t, r1);
-      const float r2 = r1 - __builtin_bit_cast(float, b & 0xffff0000u);
-      W3[m * WS + k] = (unsigned short)(a >> 16);
-      W3[IMG + m * WS + k] = (unsigned short)(b >> 16);
-      W3[2 * IMG + m * WS + k] = (unsigned short)(__builtin_bit_cast(uint32_t, r2) >> 16);
-    }
-  } else {
-    constexpr int KS = K + 4;
-#pragma unroll 8
-    for (int i = threadIdx.x; i < M * K; i += n_threads) {
-      const int m = sk == 1 ? i / K : i % M, k = sk == 1 ? i % K : i / M;
-      Wl[m * KS + k] = w[m * sm + k * sk];
-    }
+  for (int i = threadIdx.x; i < M * K; i += n_threads) {
+    const int m = sk == 1 ? i / K : i % M, k = sk == 1 ? i % K : i / M;       // consecutive threads: consecutive addresses
+    const float v = w[m * sm + k * sk];
+    const uint32_t a = __builtin_bit_cast(uint32_t, v);
+    const float r1 = v - __builtin_bit_cast(float, a & 0xffff0000u);
+    const uint32_t b = __builtin_bit_cast(uint32_t, r1);
+    const float r2 = r1 - __builtin_bit_cast(float, b & 0xffff0000u);
+    W3[m * WS + k] = (unsigned short)(a >> 16);
+    W3[IMG + m * WS + k] = (unsigned short)(b >> 16);
+    W3[2 * IMG + m * WS + k] = (unsigned short)(__builtin_bit_cast(uint32_t, r2) >> 16);
   }
 }
 
-template <int K, int M>
-__device__ __forceinline__ void tile_product_x3(const float* Xt, const float* Wl, int r, int hh, f32x16 (&acc)[M / 32]) {
-  constexpr int KS = K + 4, WS = WImg<K, M>::WS, IMG = M * WS;
+template <int NB>
+__device__ __forceinline__ void zero_acc(f32x16 (&acc)[NB]) {
 #pragma unroll
-  for (int b = 0; b < M / 32; ++b)
+  for (int b = 0; b < NB; ++b)
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[b][i] = 0.f;
+}
+
+// acc[b] += x . w[b] for one k-step of 16: the six partial products, smallest first (this order fixes the rounding); the
+// output blocks interleaved so that consecutive matrix instructions never wait for each other's accumulator.
+// wf[b] = the (hi, mid, lo) fragments of output block b's weights
+template <int NB>
+__device__ __forceinline__ void mfma6_fwd(const Split3& x, const bf16x8 (&wf)[NB][3], f32x16 (&acc)[NB]) {
+  auto term = [&](const bf16x8& xt, int wt) __attribute__((always_inline)) {
+#pragma unroll
+    for (int b = 0; b < NB; ++b) acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xt, wf[b][wt], acc[b], 0, 0, 0);
+  };
+  term(x.lo, 0); term(x.hi, 2); term(x.mid, 1); term(x.mid, 0); term(x.hi, 1); term(x.hi, 0);
+}
+
+// one 32-row tile out of LDS: acc[b] = x_tile . w[32b .. 32b+32)^T
+template <int K, int M>
+__device__ __forceinline__ void tile_product(const float* Xt, const float* Wl, int r, int hh, f32x16 (&acc)[M / 32]) {
+  constexpr int KS = K + 4, WS = WImg<K, M>::WS, IMG = M * WS;
+  zero_acc(acc);
   const float* xa = Xt + r * KS + 8 * hh;
   const unsigned short* wb = reinterpret_cast<const unsigned short*>(Wl) + r * WS + 8 * hh;
   float4 x0 = *reinterpret_cast<const float4*>(xa), x1 = *reinterpret_cast<const float4*>(xa + 4);
@@ -330,20 +301,8 @@ __device__ __forceinline__ void tile_product_x3(const float* Xt, const float* Wl
             wf[(i + 1) & 1][b][t] = *reinterpret_cast<const bf16x8*>(wb + 32 * b * WS + 16 * (i + 1) + t * IMG);
       }
     }
-    // the six partial products, smallest first; the output blocks interleaved so that consecutive matrix instructions
-    // never wait for each other's accumulator
-#define PG_X3(AT, WT)                                                                                     \
-    _Pragma("unroll") for (int b = 0; b < M / 32; ++b)                                                    \
-      acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.AT, wf[DB ? (i & 1) : 0][b][WT], acc[b], 0, 0, 0);
-    PG_X3(lo, 0) PG_X3(hi, 2) PG_X3(mid, 1) PG_X3(mid, 0) PG_X3(hi, 1) PG_X3(hi, 0)
-#undef PG_X3
+    mfma6_fwd(a, wf[DB ? (i & 1) : 0], acc);
   }
-}
-
-template <int K, int M>
-__device__ __forceinline__ void tile_mult(const float* Xt, const float* Wl, int r, int hh, f32x16 (&acc)[M / 32]) {
-  if constexpr (WImg<K, M>::X3) tile_product_x3<K, M>(Xt, Wl, r, hh, acc);
-  else tile_product<K, M>(Xt, Wl, r, hh, acc);
 }
 
 // Pipeline per wave over the FULL tiles (rows [32t, 32t+32) all inside the matrix):
@@ -403,7 +362,7 @@ __global__ __launch_bounds__((FwdGeo<K, M>::WAVES * 64)) void linear_fwd_kernel(
           for (int b = 0; b < M / 32; ++b) gv[b][i] = Elem<TG>::ld1(gr + 32 * b, goff);
         }
       }
-      tile_mult<K, M>(Xt, Wl, r, hh, acc);
+      tile_product<K, M>(Xt, Wl, r, hh, acc);
       // C[row = jrow(i,hh)][m = r + 32b]: 128-byte row segments
       uint32_t loff = (4u * hh * (uint32_t)ldy + r) * (uint32_t)sizeof(TY);
       int64_t sbase = tile * 32;
@@ -430,7 +389,7 @@ __global__ __launch_bounds__((FwdGeo<K, M>::WAVES * 64)) void linear_fwd_kernel(
     wave_sync_lds();
     store_rows<K, ACT, TX>(rg, lane, Xt);
     wave_sync_lds();
-    tile_mult<K, M>(Xt, Wl, r, hh, acc);
+    tile_product<K, M>(Xt, Wl, r, hh, acc);
 #pragma unroll
     for (int b = 0; b < M / 32; ++b)
 #pragma unroll
@@ -445,62 +404,33 @@ __global__ __launch_bounds__((FwdGeo<K, M>::WAVES * 64)) void linear_fwd_kernel(
   }
 }
 
+// acc[a][b] += g[a]^T x[b] for one step of 16 rows: the six partial products, smallest first (this order fixes the rounding)
+template <int A, int B>
+__device__ __forceinline__ void mfma6_wgrad(const Split3 (&ga)[A], const Split3 (&xb)[B], f32x16 (&acc)[A][B]) {
+  auto term = [&](bf16x8 Split3::*gt, bf16x8 Split3::*xt) __attribute__((always_inline)) {
+#pragma unroll
+    for (int a = 0; a < A; ++a)
+#pragma unroll
+      for (int b = 0; b < B; ++b)
+        acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ga[a].*gt, xb[b].*xt, acc[a][b], 0, 0, 0);
+  };
+  term(&Split3::lo, &Split3::hi); term(&Split3::hi, &Split3::lo); term(&Split3::mid, &Split3::mid);
+  term(&Split3::mid, &Split3::hi); term(&Split3::hi, &Split3::mid); term(&Split3::hi, &Split3::hi);
+}
+
 // One 32-row tile of the weight gradient: acc[a][b] (32 x 32 block of gw[M][K]) += G_tile^T X_tile, gbp[a] += column sums
 // of G.  Split-bf16 product: 2 steps of 16 rows on v_mfma_f32_32x32x16_bf16 — both operands are data here, so both are
 // split (three exact bf16 terms each, six partial products, smallest first): per tile 96 column reads, 12 splits, 96 matrix
-// instructions of 8 passes instead of the f32 product's 128 of 16.
-// ACT = 1: Xt holds the PRE-activation rows and ELU is applied as a value is read (every value is read exactly once, so this
-// is store_rows<K, 1>'s instruction count; pq_backward_parts_kernel keeps the raw rows because they are also its gate).
-template <int K, int M, int ACT = 0>
-__device__ __forceinline__ void wgrad_tile(const float* Xt, const float* Gt, int r, int hh, f32x16 (&acc)[M / 32][K / 32],
+// instructions of 8 passes (v_mfma_f32_32x32x2_f32 would take 128 of 16).
+// x_of(row, b): the lane's X value X[row][r + 32 b] — read from a stored tile (TileX) or generated in registers
+// (gen_linear_wgrad_kernel).
+template <int K, int M, typename XOf>
+__device__ __forceinline__ void wgrad_tile(const float* Gt, int r, int hh, XOf x_of, f32x16 (&acc)[M / 32][K / 32],
                                            float (&gbp)[M / 32]) {
-  constexpr int KS = K + 4, MS = M + 4;
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int row0 = 16 * j + 8 * hh;
-    Split3 ga[M / 32], xb[K / 32];
-#pragma unroll
-    for (int a = 0; a < M / 32; ++a) {
-      float f[8];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) { f[q] = Gt[(row0 + q) * MS + r + 32 * a]; gbp[a] += f[q]; }
-      ga[a] = split8(make_float4(f[0], f[1], f[2], f[3]), make_float4(f[4], f[5], f[6], f[7]));
-    }
-#pragma unroll
-    for (int b = 0; b < K / 32; ++b) {
-      float f[8];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        f[q] = Xt[(row0 + q) * KS + r + 32 * b];
-        if (ACT == 1) f[q] = elu1(f[q]);
-      }
-      xb[b] = split8(make_float4(f[0], f[1], f[2], f[3]), make_float4(f[4], f[5], f[6], f[7]));
-    }
-#define PG_W3(GT, XT)                                                                                     \
-    _Pragma("unroll") for (int a = 0; a < M / 32; ++a)                                                    \
-    _Pragma("unroll") for (int b = 0; b < K / 32; ++b)                                                    \
-      acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ga[a].GT, xb[b].XT, acc[a][b], 0, 0, 0);
-    PG_W3(lo, hi) PG_W3(hi, lo) PG_W3(mid, mid) PG_W3(mid, hi) PG_W3(hi, mid) PG_W3(hi, hi)
-#undef PG_W3
-  }
-}
-
-// wgrad_tile's split-bf16 form with the X operand GENERATED in registers (functional._EmbedConvInLinear): lane (column
-// k = r + 32 b, row half hh) forms ELU(h[row][k]) for its 8 rows of a 16-row step from the rows' (r, s) — broadcast reads of
-// the wave's 64-float rs tile — and its own columns' (a, c, b_in).  Same values, same splits, same matrix instructions in
-// the same order as wgrad_tile over a stored tile: bit-identical accumulators, no [32][K] tile, no shuffles.
-template <int K, int M>
-__device__ __forceinline__ void gen_wgrad_tile_x3(const float* Gt, const float* rs, const float (&ca)[K / 32],
-                                                  const float (&cc)[K / 32], const float (&cb)[K / 32], int r, int hh,
-                                                  f32x16 (&acc)[M / 32][K / 32], float (&gbp)[M / 32]) {
   constexpr int MS = M + 4;
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const int row0 = 16 * j + 8 * hh;
-    const float4 R0 = *reinterpret_cast<const float4*>(rs + row0), R1 = *reinterpret_cast<const float4*>(rs + row0 + 4);
-    const float4 S0 = *reinterpret_cast<const float4*>(rs + 32 + row0), S1 = *reinterpret_cast<const float4*>(rs + 32 + row0 + 4);
-    const float rr[8] = {R0.x, R0.y, R0.z, R0.w, R1.x, R1.y, R1.z, R1.w};
-    const float ss[8] = {S0.x, S0.y, S0.z, S0.w, S1.x, S1.y, S1.z, S1.w};
     Split3 ga[M / 32], xb[K / 32];
 #pragma unroll
     for (int a = 0; a < M / 32; ++a) {
@@ -513,17 +443,25 @@ __device__ __forceinline__ void gen_wgrad_tile_x3(const float* Gt, const float* 
     for (int b = 0; b < K / 32; ++b) {
       float f[8];
 #pragma unroll
-      for (int q = 0; q < 8; ++q) f[q] = elu1(gen_h(rr[q], ss[q], ca[b], cc[b], cb[b]));
+      for (int q = 0; q < 8; ++q) f[q] = x_of(row0 + q, b);
       xb[b] = split8(make_float4(f[0], f[1], f[2], f[3]), make_float4(f[4], f[5], f[6], f[7]));
     }
-#define PG_W3(GT, XT)                                                                                     \
-    _Pragma("unroll") for (int a = 0; a < M / 32; ++a)                                                    \
-    _Pragma("unroll") for (int b = 0; b < K / 32; ++b)                                                    \
-      acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ga[a].GT, xb[b].XT, acc[a][b], 0, 0, 0);
-    PG_W3(lo, hi) PG_W3(hi, lo) PG_W3(mid, mid) PG_W3(mid, hi) PG_W3(hi, mid) PG_W3(hi, hi)
-#undef PG_W3
+    mfma6_wgrad(ga, xb, acc);
   }
 }
+
+// wgrad_tile's X values out of the wave's LDS tile [32][K + 4].  ACT = 1: Xt holds the PRE-activation rows and ELU is applied
+// as a value is read (every value is read exactly once, so this is store_rows<K, 1>'s instruction count;
+// pq_backward_parts_kernel keeps the raw rows because they are also its gate).
+template <int K, int ACT>
+struct TileX {
+  const float* Xt;
+  int r;
+  __device__ __forceinline__ float operator()(int row, int b) const {
+    const float v = Xt[row * (K + 4) + r + 32 * b];
+    return ACT == 1 ? elu1(v) : v;
+  }
+};
 
 template <int K, int M>
 struct WgradGeo {
@@ -617,7 +555,7 @@ __global__ __launch_bounds__(256) void linear_wgrad_kernel(const TG* __restrict_
     load_rows<K, TX>(x, ldx, n, (tile + stride) * 32, lane, rx);
     load_rows<M, TG>(g, ldg, n, (tile + stride) * 32, lane, rgm);
     wave_sync_lds();
-    wgrad_tile<K, M>(Xt, Gt, r, hh, acc, gbp);
+    wgrad_tile<K, M>(Gt, r, hh, TileX<K, 0>{Xt, r}, acc, gbp);     // store_rows has applied ACT
     wave_sync_lds();
   }
 #pragma unroll
@@ -644,22 +582,54 @@ static int num_cus() {
   return 256;
 }
 
+// workgroups of a launch whose `waves` waves per workgroup walk the 32-row tiles: min(ceil(n_tiles / waves), cus_mult x CUs),
+// and no fewer than `at_least` (1 where every launch must leave a slab, n = 0 included)
+static int64_t grid_of(int64_t n_tiles, int waves, int cus_mult = 1, int64_t at_least = 0) {
+  int64_t grid = (n_tiles + waves - 1) / waves;
+  const int64_t cap = cus_mult * (int64_t)num_cus();
+  if (grid > cap) grid = cap;
+  return grid < at_least ? at_least : grid;
+}
+
+// a kernel that leaves one slab of `slab_len` floats per workgroup in `ws`, then the slabs' sum in workgroup order:
+// elements [0, split) to out0, the rest to out1 (nullable)
+template <typename Launch>
+static int launch_then_reduce(Launch launch, const char* who, const char* who_reduce, float* ws, int64_t grid, int slab_len,
+                              int split, float* out0, float* out1, hipStream_t s) {
+  launch();
+  PG_CHECK_LAUNCH(who);
+  hipLaunchKernelGGL(slab_reduce_kernel, dim3((slab_len + kWave - 1) / kWave), dim3(kSumThreads), 0, s, ws, (int)grid, slab_len,
+                     split, out0, out1);
+  PG_CHECK_LAUNCH(who_reduce);
+  return 0;
+}
+
+// runtime (K, M) in {64, 128}^2 -> f(integral_constant K, integral_constant M)
+template <typename F>
+static int with_shape(int32_t K, int32_t M, F&& f) {
+  using C64 = std::integral_constant<int, 64>;
+  using C128 = std::integral_constant<int, 128>;
+  if (K == 64 && M == 64) return f(C64{}, C64{});
+  if (K == 64 && M == 128) return f(C64{}, C128{});
+  if (K == 128 && M == 64) return f(C128{}, C64{});
+  return f(C128{}, C128{});
+}
+
+// TG: the gate's storage type, void for a product without gate
 template <int K, int M, typename TX, typename TY, typename TG>
 static int launch_fwd_t(const void* x, int64_t ldx, const float* w, int w_trans, const float* bias, void* y, int64_t ldy,
                         int64_t n, int in_act, const void* gate, int64_t ldgate, hipStream_t s) {
   const int w_sm = w_trans ? 1 : K, w_sk = w_trans ? M : 1;
   constexpr int WAVES = FwdGeo<K, M>::WAVES;
   const int64_t n_tiles = (n + 31) / 32;
-  int64_t grid = (n_tiles + WAVES - 1) / WAVES;
-  const int64_t cap = (int64_t)num_cus();          // one workgroup per CU fills its LDS
-  if (grid > cap) grid = cap;
-  const dim3 g((unsigned)grid), b(WAVES * 64);
+  const dim3 g((unsigned)grid_of(n_tiles, WAVES)), b(WAVES * 64);          // one workgroup per CU fills its LDS
   const TX* xp = static_cast<const TX*>(x);
   TY* yp = static_cast<TY*>(y);
-  const TG* gp = static_cast<const TG*>(gate);
-  if (gate)
-    hipLaunchKernelGGL((linear_fwd_kernel<K, M, 0, true, TX, TY, TG>), g, b, 0, s, xp, ldx, w, w_sm, w_sk, bias, yp, ldy, n, n_tiles, gp, ldgate);
-  else if (in_act)
+  if constexpr (!std::is_void<TG>::value) {
+    static_assert(std::is_same<TG, TY>::value, "a gated product is stored like its gate: no other gated kernel is compiled");
+    hipLaunchKernelGGL((linear_fwd_kernel<K, M, 0, true, TX, TY, TG>), g, b, 0, s, xp, ldx, w, w_sm, w_sk, bias, yp, ldy, n, n_tiles,
+                       static_cast<const TG*>(gate), ldgate);
+  } else if (in_act)
     hipLaunchKernelGGL((linear_fwd_kernel<K, M, 1, false, TX, TY, float>), g, b, 0, s, xp, ldx, w, w_sm, w_sk, bias, yp, ldy, n, n_tiles,
                        static_cast<const float*>(nullptr), ldgate);
   else
@@ -670,8 +640,9 @@ static int launch_fwd_t(const void* x, int64_t ldx, const float* w, int w_trans,
 }
 
 // storage-type dispatch.  A gated product (dL/dx of "dense after ELU") writes the gradient of the gate tensor, so its
-// result is stored like the gate: (TG, TY) is (f32, f32) or (H, H).  H: the 2-byte format of this call's 16-bit operands
-// (bf16s or f16s — one call never mixes the two; x16 / y16 / gate16 say which operands are stored in it).
+// result is stored like the gate (linear_fwd_common checks it): (TG, TY) is (f32, f32) or (H, H).  H: the 2-byte format of
+// this call's 16-bit operands (bf16s or f16s — one call never mixes the two; x16 / y16 / gate16 say which operands are
+// stored in it).
 template <int K, int M, typename H>
 static int launch_fwd(const void* x, int x16, int64_t ldx, const float* w, int w_trans, const float* bias, void* y,
                       int y16, int64_t ldy, int64_t n, int in_act, const void* gate, int gate16, int64_t ldgate,
@@ -682,9 +653,9 @@ static int launch_fwd(const void* x, int x16, int64_t ldx, const float* w, int w
     if (x16) PG_FWD(H, float, float);
     PG_FWD(float, float, float);
   }
-  if (x16) { if (y16) PG_FWD(H, H, float); PG_FWD(H, float, float); }
-  if (y16) PG_FWD(float, H, float);
-  PG_FWD(float, float, float);
+  if (x16) { if (y16) PG_FWD(H, H, void); PG_FWD(H, float, void); }
+  if (y16) PG_FWD(float, H, void);
+  PG_FWD(float, float, void);
 #undef PG_FWD
 }
 
@@ -693,25 +664,21 @@ static int launch_wgrad_t(const void* g, int64_t ldg, const void* x, int64_t ldx
                           float* gb, float* ws, size_t ws_bytes, hipStream_t s) {
   constexpr int SLAB = WgradGeo<K, M>::SLAB;
   const int64_t n_tiles = (n + 31) / 32;
-  int64_t grid = (n_tiles + 3) / 4;
-  const int64_t cap = (int64_t)num_cus();
-  if (grid > cap) grid = cap;
-  if (grid < 1) grid = 1;
+  const int64_t grid = grid_of(n_tiles, 4, 1, 1);
   PG_CHECK_ARG(ws && ws_bytes >= (size_t)grid * SLAB * sizeof(float), PANGNN_E_WORKSPACE,
                "pangnn_linear_wgrad: workspace too small");
   const TG* gp = static_cast<const TG*>(g);
   const TX* xp = static_cast<const TX*>(x);
-  if (in_act)
-    hipLaunchKernelGGL((linear_wgrad_kernel<K, M, 1, TG, TX>), dim3((unsigned)grid), dim3(256), 0, s, gp, ldg, xp, ldx, n,
-                       n_tiles, ws);
-  else
-    hipLaunchKernelGGL((linear_wgrad_kernel<K, M, 0, TG, TX>), dim3((unsigned)grid), dim3(256), 0, s, gp, ldg, xp, ldx, n,
-                       n_tiles, ws);
-  PG_CHECK_LAUNCH("pangnn_linear_wgrad");
-  hipLaunchKernelGGL(slab_reduce_kernel, dim3((SLAB + kWave - 1) / kWave), dim3(kSumThreads), 0, s, ws, (int)grid,
-                     SLAB, M * K, gw, gb);
-  PG_CHECK_LAUNCH("pangnn_linear_wgrad(reduce)");
-  return 0;
+  return launch_then_reduce(
+      [&] {
+        if (in_act)
+          hipLaunchKernelGGL((linear_wgrad_kernel<K, M, 1, TG, TX>), dim3((unsigned)grid), dim3(256), 0, s, gp, ldg, xp, ldx, n,
+                             n_tiles, ws);
+        else
+          hipLaunchKernelGGL((linear_wgrad_kernel<K, M, 0, TG, TX>), dim3((unsigned)grid), dim3(256), 0, s, gp, ldg, xp, ldx, n,
+                             n_tiles, ws);
+      },
+      "pangnn_linear_wgrad", "pangnn_linear_wgrad(reduce)", ws, grid, SLAB, M * K, gw, gb, s);
 }
 
 template <int K, int M, typename H>
@@ -845,7 +812,6 @@ __global__ __launch_bounds__(256) void pq_backward_parts_kernel(PartTables pt, c
                                                                 int64_t ldgx, int64_t n, int64_t n_tiles,
                                                                 float* __restrict__ slabs) {
   static_assert(K == 64 && M == 128, "the decoder's P | Q layer");
-  static_assert(WImg<M, K>::X3, "dL/dx runs tile_product_x3<M, K> on the G tile, whose row stride M + 4 is that product's");
   constexpr int KS = K + 4, MS = M + 4;
   constexpr int PER_WAVE = 32 * KS + 32 * MS;
   constexpr int SLAB = WgradGeo<K, M>::SLAB;
@@ -888,10 +854,11 @@ __global__ __launch_bounds__(256) void pq_backward_parts_kernel(PartTables pt, c
     issue_parts(pt, rp, lane, pa);
     load_part_ptrs(pt, n, tile + 2 * stride, lane, rp_next);
     wave_sync_lds();
-    wgrad_tile<K, M, ACT>(Xt, Gt, r, hh, acc, gbp);
-    // dL/dx = (G w) * ELU'(x): linear_fwd_kernel<M, K, 0, GATE>'s product and epilogue, gate read from the x tile
+    wgrad_tile<K, M>(Gt, r, hh, TileX<K, ACT>{Xt, r}, acc, gbp);
+    // dL/dx = (G w) * ELU'(x): linear_fwd_kernel<M, K, 0, GATE>'s product (the G tile's row stride M + 4 is that product's)
+    // and epilogue, gate read from the x tile
     f32x16 dx[K / 32];
-    tile_product_x3<M, K>(Gt, Wl, r, hh, dx);
+    tile_product<M, K>(Gt, Wl, r, hh, dx);
     if (tile * 32 + 32 <= n) {                                      // wave-uniform: full tile, 128-byte row segments
       uint32_t loff = (4u * hh * (uint32_t)ldgx + r) * (uint32_t)sizeof(float);
       int64_t sbase = tile * 32;
@@ -930,23 +897,19 @@ static int launch_pq_backward_parts(const PartTables& pt, const float* x, int64_
                                     float* gx, int64_t ldgx, float* gw, float* gb, float* ws, size_t ws_bytes, hipStream_t s) {
   constexpr int K = 64, M = 128, SLAB = WgradGeo<K, M>::SLAB;
   const int64_t n_tiles = (n + 31) / 32;
-  int64_t grid = (n_tiles + 3) / 4;                                 // linear_wgrad_kernel's geometry: same slabs, same order
-  const int64_t cap = (int64_t)num_cus();
-  if (grid > cap) grid = cap;
-  if (grid < 1) grid = 1;
+  const int64_t grid = grid_of(n_tiles, 4, 1, 1);                   // linear_wgrad_kernel's geometry: same slabs, same order
   PG_CHECK_ARG(ws && ws_bytes >= (size_t)grid * SLAB * sizeof(float), PANGNN_E_WORKSPACE,
                "pangnn_linear_act_backward_parts_f32: workspace too small");
-  if (in_act)
-    hipLaunchKernelGGL((pq_backward_parts_kernel<K, M, 1>), dim3((unsigned)grid), dim3(256), 0, s, pt, x, ldx, w, gx, ldgx, n,
-                       n_tiles, ws);
-  else
-    hipLaunchKernelGGL((pq_backward_parts_kernel<K, M, 0>), dim3((unsigned)grid), dim3(256), 0, s, pt, x, ldx, w, gx, ldgx, n,
-                       n_tiles, ws);
-  PG_CHECK_LAUNCH("pangnn_linear_act_backward_parts_f32");
-  hipLaunchKernelGGL(slab_reduce_kernel, dim3((SLAB + kWave - 1) / kWave), dim3(kSumThreads), 0, s, ws, (int)grid, SLAB,
-                     M * K, gw, gb);
-  PG_CHECK_LAUNCH("pangnn_linear_act_backward_parts_f32(reduce)");
-  return 0;
+  return launch_then_reduce(
+      [&] {
+        if (in_act)
+          hipLaunchKernelGGL((pq_backward_parts_kernel<K, M, 1>), dim3((unsigned)grid), dim3(256), 0, s, pt, x, ldx, w, gx, ldgx, n,
+                             n_tiles, ws);
+        else
+          hipLaunchKernelGGL((pq_backward_parts_kernel<K, M, 0>), dim3((unsigned)grid), dim3(256), 0, s, pt, x, ldx, w, gx, ldgx, n,
+                             n_tiles, ws);
+      },
+      "pangnn_linear_act_backward_parts_f32", "pangnn_linear_act_backward_parts_f32(reduce)", ws, grid, SLAB, M * K, gw, gb, s);
 }
 
 
@@ -955,7 +918,7 @@ static int launch_pq_backward_parts(const PartTables& pt, const float* x, int64_
 //     h[i][k] = r_i a_k + s_i c_k + b_k          (functional._EmbedConvIn: r = A_hat x, s = A_hat 1, a = W_in w, c = W_in b_emb)
 //     y = ELU(h) W_out^T (+ bias)                 (conv_out's / linear_out's dense part)
 // The [N, H] rows of h are GENERATED inside the kernels that would read them — 8 bytes per row (r_i, s_i) instead of 4 H:
-//   gen_linear_fwd_kernel         y = ELU(h) W_out^T (+ bias)          (h is never written)
+//   gen_linear_fwd_reg_kernel     y = ELU(h) W_out^T (+ bias)          (h is never written)
 //   gen_linear_wgrad_kernel       dL/dW_out = g^T ELU(h), dL/dbias     (h regenerated)
 //   gen_linear_dgrad_sums_kernel  [r s 1]^T ((g W_out) * ELU'(h))      (dL/dh is never written: its three weighted column
 //                                                                       sums are all the first layer's parameters need)
@@ -988,87 +951,12 @@ __device__ __forceinline__ float gen_load(const float* __restrict__ rv, const fl
   return row < n ? p[row] : 0.f;
 }
 
-// the [32][C+4] LDS tile of ELU(h) for the 32 rows whose (r, s) sit in `rsv` (gen_load)
-template <int C>
-__device__ __forceinline__ void gen_store_rows(float rsv, int lane, float* tile, float4 a4, float4 c4, float4 b4) {
-  constexpr int LPR = C / 4;
-  constexpr int RPI = 64 / LPR;
-  constexpr int RS = C + 4;
-  const int q = lane % LPR, r0 = lane / LPR;
-#pragma unroll
-  for (int i = 0; i < 32 / RPI; ++i) {
-    const int row = i * RPI + r0;
-    const float rv = __shfl(rsv, row), sv = __shfl(rsv, 32 + row);
-    float4 v;
-    v.x = elu1(gen_h(rv, sv, a4.x, c4.x, b4.x));
-    v.y = elu1(gen_h(rv, sv, a4.y, c4.y, b4.y));
-    v.z = elu1(gen_h(rv, sv, a4.z, c4.z, b4.z));
-    v.w = elu1(gen_h(rv, sv, a4.w, c4.w, b4.w));
-    *reinterpret_cast<float4*>(tile + row * RS + 4 * q) = v;
-  }
-}
-
-template <int K, int M>
-__global__ __launch_bounds__((FwdGeo<K, M>::WAVES * 64)) void gen_linear_fwd_kernel(
-    const float* __restrict__ rvec, const float* __restrict__ svec, const float* __restrict__ w_emb,
-    const float* __restrict__ b_emb, const float* __restrict__ w_in, const float* __restrict__ b_in, int D,
-    const float* __restrict__ w, const float* __restrict__ bias, float* __restrict__ y, int64_t ldy, int64_t n,
-    int64_t n_tiles) {
-  constexpr int KS = K + 4;
-  constexpr int WAVES = FwdGeo<K, M>::WAVES;
-  constexpr int WF = (WImg<K, M>::FLOATS + 3) & ~3;
-  __shared__ __attribute__((aligned(16))) float lds[WF + WAVES * 32 * KS];
-  __shared__ __attribute__((aligned(16))) float acb[3 * K];
-  float* Wl = lds;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-  float* Xt = lds + WF + wave * (32 * KS);
-  stage_w<K, M>(w, K, 1, Wl, WAVES * 64);
-  gen_params<K>(w_emb, b_emb, w_in, b_in, D, acb, WAVES * 64);
-  __syncthreads();
-  const int q = lane % (K / 4);
-  const float4 a4 = *reinterpret_cast<const float4*>(acb + 4 * q), c4 = *reinterpret_cast<const float4*>(acb + K + 4 * q);
-  const float4 b4 = *reinterpret_cast<const float4*>(acb + 2 * K + 4 * q);
-  const int r = lane & 31, hh = lane >> 5;
-  const int64_t stride = (int64_t)gridDim.x * WAVES;
-  int64_t tile = (int64_t)blockIdx.x * WAVES + wave;
-  float bv[M / 32];
-#pragma unroll
-  for (int b = 0; b < M / 32; ++b) bv[b] = bias ? bias[r + 32 * b] : 0.f;
-  f32x16 acc[M / 32];
-  float rsv = gen_load(rvec, svec, n, tile * 32, lane);
-  for (; tile < n_tiles; tile += stride) {
-    gen_store_rows<K>(rsv, lane, Xt, a4, c4, b4);
-    rsv = gen_load(rvec, svec, n, (tile + stride) * 32, lane);
-    wave_sync_lds();
-    tile_mult<K, M>(Xt, Wl, r, hh, acc);
-    if (tile * 32 + 32 <= n) {                     // wave-uniform: full tile, 128-byte row segments
-      uint32_t loff = (4u * hh * (uint32_t)ldy + r) * (uint32_t)sizeof(float);
-      int64_t sbase = tile * 32;
-      pin(sbase, loff);
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        float* yr = y + (sbase + (i & 3) + 8 * (i >> 2)) * ldy;
-#pragma unroll
-        for (int b = 0; b < M / 32; ++b) st_f32(yr + 32 * b, loff, acc[b][i] + bv[b]);
-      }
-    } else {
-#pragma unroll
-      for (int b = 0; b < M / 32; ++b)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const int64_t row = tile * 32 + jrow(i, hh);
-          if (row < n) y[row * ldy + r + 32 * b] = acc[b][i] + bv[b];
-        }
-    }
-    wave_sync_lds();
-  }
-}
-
-// The forward product with the A operand generated IN REGISTERS (split-bf16 product only): lane (row r, half hh) of a
+// The forward product with the A operand generated IN REGISTERS: lane (row r, half hh) of a
 // 32x32x16 step needs ELU(h[r][k]) for 8 consecutive k — from its own row's (r_i, s_i) and the 8 columns' (a, c, b_in),
 // read from LDS as three broadcast pairs of ds_read_b128.  No row tile, no shuffles, no wave barrier: the only LDS
 // residents are the weight images and the 3 K parameter floats, so 8 waves (two per SIMD) share a workgroup and hide each
-// other's exp / split phases.  Same values, same products, same order as gen_linear_fwd_kernel: bit-identical results.
+// other's exp / split phases.  Same values, same products, same order as tile_product over a stored [32][K + 4] tile of
+// ELU(h) — linear_fwd_kernel<K, M, 1> on the rows embed_conv_in_rows_kernel writes: bit-identical results.
 template <int K, int M>
 __global__ __launch_bounds__(512) void gen_linear_fwd_reg_kernel(
     const float* __restrict__ rvec, const float* __restrict__ svec, const float* __restrict__ w_emb,
@@ -1103,10 +991,7 @@ __global__ __launch_bounds__(512) void gen_linear_fwd_reg_kernel(
     float rn, sn;
     row_rs(tile + stride, rn, sn);
     f32x16 acc[M / 32];
-#pragma unroll
-    for (int b = 0; b < M / 32; ++b)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) acc[b][i] = 0.f;
+    zero_acc(acc);
 #pragma unroll
     for (int i = 0; i < K / 16; ++i) {
       const int k0 = 16 * i + 8 * hh;
@@ -1123,12 +1008,7 @@ __global__ __launch_bounds__(512) void gen_linear_fwd_reg_kernel(
       x0.z = elu1(gen_h(rv, sv, a0.z, c0.z, b0.z)); x0.w = elu1(gen_h(rv, sv, a0.w, c0.w, b0.w));
       x1.x = elu1(gen_h(rv, sv, a1.x, c1.x, b1.x)); x1.y = elu1(gen_h(rv, sv, a1.y, c1.y, b1.y));
       x1.z = elu1(gen_h(rv, sv, a1.z, c1.z, b1.z)); x1.w = elu1(gen_h(rv, sv, a1.w, c1.w, b1.w));
-      const Split3 a = split8(x0, x1);
-#define PG_X3(AT, WT)                                                                                     \
-      _Pragma("unroll") for (int b = 0; b < M / 32; ++b)                                                  \
-        acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.AT, wf[b][WT], acc[b], 0, 0, 0);
-      PG_X3(lo, 0) PG_X3(hi, 2) PG_X3(mid, 1) PG_X3(mid, 0) PG_X3(hi, 1) PG_X3(hi, 0)
-#undef PG_X3
+      mfma6_fwd(split8(x0, x1), wf, acc);
     }
     if (tile * 32 + 32 <= n) {                     // wave-uniform: full tile, 128-byte row segments
       uint32_t loff = (4u * hh * (uint32_t)ldy + r) * (uint32_t)sizeof(float);
@@ -1176,6 +1056,11 @@ __global__ __launch_bounds__(256) void gen_linear_wgrad_kernel(const float* __re
   float ca[K / 32], cc[K / 32], cb[K / 32];      // (a, c, b_in) of this lane's columns r + 32 b
 #pragma unroll
   for (int b = 0; b < K / 32; ++b) { ca[b] = acb[r + 32 * b]; cc[b] = acb[K + r + 32 * b]; cb[b] = acb[2 * K + r + 32 * b]; }
+  // wgrad_tile's X operand GENERATED in registers (functional._EmbedConvInLinear): lane (column k = r + 32 b, row half hh)
+  // forms ELU(h[row][k]) for its 8 rows of a 16-row step from the rows' (r, s) — broadcast reads of the wave's 64-float rs
+  // tile — and its own columns' (a, c, b_in).  Same values, same splits, same matrix instructions in the same order as over a
+  // stored tile (TileX): bit-identical accumulators, no [32][K] tile, no shuffles.
+  auto gen_x = [&](int row, int b) { return elu1(gen_h(Xt[row], Xt[32 + row], ca[b], cc[b], cb[b])); };
   f32x16 acc[M / 32][K / 32];
   float gbp[M / 32];
 #pragma unroll
@@ -1197,7 +1082,7 @@ __global__ __launch_bounds__(256) void gen_linear_wgrad_kernel(const float* __re
     rsv = gen_load(rvec, svec, n, (tile + stride) * 32, lane);
     load_rows<M, float>(g, ldg, n, (tile + stride) * 32, lane, rgm);
     wave_sync_lds();
-    gen_wgrad_tile_x3<K, M>(Gt, Xt, ca, cc, cb, r, hh, acc, gbp);
+    wgrad_tile<K, M>(Gt, r, hh, gen_x, acc, gbp);
     wave_sync_lds();
   }
 #pragma unroll
@@ -1246,7 +1131,7 @@ __global__ __launch_bounds__((FwdGeo<KG, H>::WAVES * 64)) void gen_linear_dgrad_
     load_rows<KG, float>(g, ldg, n, (tile + stride) * 32, lane, rg);
     rsv = gen_load(rvec, svec, n, (tile + stride) * 32, lane);
     wave_sync_lds();
-    tile_mult<KG, H>(Xt, Wl, r, hh, acc);
+    tile_product<KG, H>(Xt, Wl, r, hh, acc);
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       const int row = jrow(i, hh);
@@ -1283,31 +1168,11 @@ static int launch_gen_fwd(const float* r, const float* sv, const float* w_emb, c
                           const float* b_in, int D, const float* w, const float* bias, float* y, int64_t ldy, int64_t n,
                           hipStream_t s) {
   const int64_t n_tiles = (n + 31) / 32;
-  if constexpr (WImg<K, M>::X3) {
-    int64_t grid = (n_tiles + 7) / 8;
-    const int64_t cap = 2 * (int64_t)num_cus();      // two 8-wave workgroups per CU fit (weight images <= 56 KB each)
-    if (grid > cap) grid = cap;
-    hipLaunchKernelGGL((gen_linear_fwd_reg_kernel<K, M>), dim3((unsigned)grid), dim3(512), 0, s, r, sv, w_emb, b_emb, w_in, b_in,
-                       D, w, bias, y, ldy, n, n_tiles);
-    PG_CHECK_LAUNCH("pangnn_embed_linear_fwd");
-    return 0;
-  }
-  constexpr int WAVES = FwdGeo<K, M>::WAVES;
-  int64_t grid = (n_tiles + WAVES - 1) / WAVES;
-  const int64_t cap = (int64_t)num_cus();
-  if (grid > cap) grid = cap;
-  hipLaunchKernelGGL((gen_linear_fwd_kernel<K, M>), dim3((unsigned)grid), dim3(WAVES * 64), 0, s, r, sv, w_emb, b_emb, w_in, b_in,
+  const int64_t grid = grid_of(n_tiles, 8, 2);       // two 8-wave workgroups per CU fit (weight images <= 56 KB each)
+  hipLaunchKernelGGL((gen_linear_fwd_reg_kernel<K, M>), dim3((unsigned)grid), dim3(512), 0, s, r, sv, w_emb, b_emb, w_in, b_in,
                      D, w, bias, y, ldy, n, n_tiles);
   PG_CHECK_LAUNCH("pangnn_embed_linear_fwd");
   return 0;
-}
-
-static int64_t gen_grid(int64_t n, int waves) {
-  const int64_t n_tiles = (n + 31) / 32;
-  int64_t grid = (n_tiles + waves - 1) / waves;
-  const int64_t cap = (int64_t)num_cus();
-  if (grid > cap) grid = cap;
-  return grid < 1 ? 1 : grid;
 }
 
 template <int K, int M>
@@ -1316,23 +1181,24 @@ static int launch_gen_bwd(const float* g, int64_t ldg, const float* r, const flo
                           float* g_b_out, float* sums, float* ws, hipStream_t s) {
   constexpr int SLAB = WgradGeo<K, M>::SLAB;
   const int64_t n_tiles = (n + 31) / 32;
-  const int64_t grid_w = gen_grid(n, 4);
-  hipLaunchKernelGGL((gen_linear_wgrad_kernel<K, M>), dim3((unsigned)grid_w), dim3(256), 0, s, g, ldg, r, sv, w_emb, b_emb, w_in,
-                     b_in, D, n, n_tiles, ws);
-  PG_CHECK_LAUNCH("pangnn_embed_linear_bwd(wgrad)");
-  hipLaunchKernelGGL(slab_reduce_kernel, dim3((SLAB + kWave - 1) / kWave), dim3(kSumThreads), 0, s, ws, (int)grid_w, SLAB,
-                     M * K, g_w_out, g_b_out);
-  PG_CHECK_LAUNCH("pangnn_embed_linear_bwd(wgrad reduce)");
+  const int64_t grid_w = grid_of(n_tiles, 4, 1, 1);
+  const int rc = launch_then_reduce(
+      [&] {
+        hipLaunchKernelGGL((gen_linear_wgrad_kernel<K, M>), dim3((unsigned)grid_w), dim3(256), 0, s, g, ldg, r, sv, w_emb, b_emb,
+                           w_in, b_in, D, n, n_tiles, ws);
+      },
+      "pangnn_embed_linear_bwd(wgrad)", "pangnn_embed_linear_bwd(wgrad reduce)", ws, grid_w, SLAB, M * K, g_w_out, g_b_out, s);
+  if (rc) return rc;
   float* ws2 = ws + (size_t)num_cus() * SLAB;
   constexpr int WAVES = FwdGeo<M, K>::WAVES;
-  const int64_t grid_d = gen_grid(n, WAVES);
-  hipLaunchKernelGGL((gen_linear_dgrad_sums_kernel<M, K>), dim3((unsigned)grid_d), dim3(WAVES * 64), 0, s, g, ldg, w_out, r, sv,
-                     w_emb, b_emb, w_in, b_in, D, n, n_tiles, ws2);
-  PG_CHECK_LAUNCH("pangnn_embed_linear_bwd(dgrad sums)");
-  hipLaunchKernelGGL(slab_reduce_kernel, dim3((3 * K + kWave - 1) / kWave), dim3(kSumThreads), 0, s, ws2, (int)grid_d, 3 * K,
-                     3 * K, sums, static_cast<float*>(nullptr));
-  PG_CHECK_LAUNCH("pangnn_embed_linear_bwd(sums reduce)");
-  return 0;
+  const int64_t grid_d = grid_of(n_tiles, WAVES, 1, 1);
+  return launch_then_reduce(
+      [&] {
+        hipLaunchKernelGGL((gen_linear_dgrad_sums_kernel<M, K>), dim3((unsigned)grid_d), dim3(WAVES * 64), 0, s, g, ldg, w_out, r,
+                           sv, w_emb, b_emb, w_in, b_in, D, n, n_tiles, ws2);
+      },
+      "pangnn_embed_linear_bwd(dgrad sums)", "pangnn_embed_linear_bwd(sums reduce)", ws2, grid_d, 3 * K, 3 * K, sums,
+      static_cast<float*>(nullptr), s);
 }
 
 }  // namespace pangnn
@@ -1379,16 +1245,11 @@ static int linear_fwd_common(const void* x, int32_t x_dtype, int64_t ldx, const 
   PG_CHECK_ARG(fmt >= 0, PANGNN_E_BADARG, "pangnn_linear_fwd: the 2-byte operands of one call are all bfloat16 or all float16");
   hipStream_t s = (hipStream_t)stream;
   const int xb = x_dtype != PANGNN_DTYPE_F32, yb = y_dtype != PANGNN_DTYPE_F32, gb = gate && gate_dtype != PANGNN_DTYPE_F32;
-#define PG_SHAPES(H)                                                                                                              \
-  do {                                                                                                                            \
-    if (K == 64 && M == 64) return launch_fwd<64, 64, H>(x, xb, ldx, w, w_trans, bias, y, yb, ldy, n, in_act, gate, gb, ldgate, s);   \
-    if (K == 64 && M == 128) return launch_fwd<64, 128, H>(x, xb, ldx, w, w_trans, bias, y, yb, ldy, n, in_act, gate, gb, ldgate, s); \
-    if (K == 128 && M == 64) return launch_fwd<128, 64, H>(x, xb, ldx, w, w_trans, bias, y, yb, ldy, n, in_act, gate, gb, ldgate, s); \
-    return launch_fwd<128, 128, H>(x, xb, ldx, w, w_trans, bias, y, yb, ldy, n, in_act, gate, gb, ldgate, s);                         \
-  } while (0)
-  if (fmt == PANGNN_DTYPE_F16) PG_SHAPES(f16s);
-  PG_SHAPES(bf16s);
-#undef PG_SHAPES
+  return with_shape(K, M, [&](auto k, auto m) {
+    constexpr int KK = decltype(k)::value, MM = decltype(m)::value;
+    if (fmt == PANGNN_DTYPE_F16) return launch_fwd<KK, MM, f16s>(x, xb, ldx, w, w_trans, bias, y, yb, ldy, n, in_act, gate, gb, ldgate, s);
+    return launch_fwd<KK, MM, bf16s>(x, xb, ldx, w, w_trans, bias, y, yb, ldy, n, in_act, gate, gb, ldgate, s);
+  });
 }
 
 extern "C" int pangnn_linear_act_fwd_mixed(const void* x, int32_t x_dtype, int64_t ldx, const float* w, const float* bias,
@@ -1441,24 +1302,25 @@ extern "C" int pangnn_linear_act_wgrad_mixed(const void* g, int32_t g_dtype, int
   hipStream_t s = (hipStream_t)stream;
   float* ws = static_cast<float*>(workspace);
   const int gbf = g_dtype != PANGNN_DTYPE_F32, xbf = x_dtype != PANGNN_DTYPE_F32;
-#define PG_SHAPES(H)                                                                                                                 \
-  do {                                                                                                                               \
-    if (K == 64 && M == 64) return launch_wgrad<64, 64, H>(g, gbf, ldg, x, xbf, ldx, n, in_act, gw, gb, ws, workspace_bytes, s);      \
-    if (K == 64 && M == 128) return launch_wgrad<64, 128, H>(g, gbf, ldg, x, xbf, ldx, n, in_act, gw, gb, ws, workspace_bytes, s);    \
-    if (K == 128 && M == 128) {                                                                                                      \
-      /* dW[0:64) from g[:, 0:64), dW[64:128) from g[:, 64:128): the <128, 64> kernel twice over column windows of g (same ldg), */  \
-      /* stream-ordered on one workspace.  x is read twice (N * 512 B more than a single pass would need). */                        \
-      const char* g_hi = static_cast<const char*>(g) + (size_t)64 * (gbf ? 2 : 4);                                                   \
-      int rc = launch_wgrad<128, 64, H>(g, gbf, ldg, x, xbf, ldx, n, in_act, gw, gb, ws, workspace_bytes, s);                         \
-      if (rc) return rc;                                                                                                             \
-      return launch_wgrad<128, 64, H>(g_hi, gbf, ldg, x, xbf, ldx, n, in_act, gw + (size_t)64 * 128, gb ? gb + 64 : nullptr, ws,      \
-                                      workspace_bytes, s);                                                                           \
-    }                                                                                                                                \
-    return launch_wgrad<128, 64, H>(g, gbf, ldg, x, xbf, ldx, n, in_act, gw, gb, ws, workspace_bytes, s);                             \
-  } while (0)
-  if (fmt == PANGNN_DTYPE_F16) PG_SHAPES(f16s);
-  PG_SHAPES(bf16s);
-#undef PG_SHAPES
+  return with_shape(K, M, [&](auto k, auto m) {
+    constexpr int KK = decltype(k)::value, MM = decltype(m)::value;
+    auto run = [&](auto h) {
+      using H = decltype(h);
+      if constexpr (KK == 128 && MM == 128) {
+        // dW[0:64) from g[:, 0:64), dW[64:128) from g[:, 64:128): the <128, 64> kernel twice over column windows of g (same
+        // ldg), stream-ordered on one workspace (one tile of 256 accumulator registers does not fit).  x is read twice
+        // (N * 512 B more than a single pass would need).
+        const char* g_hi = static_cast<const char*>(g) + (size_t)64 * (gbf ? 2 : 4);
+        const int rc = launch_wgrad<128, 64, H>(g, gbf, ldg, x, xbf, ldx, n, in_act, gw, gb, ws, workspace_bytes, s);
+        if (rc) return rc;
+        return launch_wgrad<128, 64, H>(g_hi, gbf, ldg, x, xbf, ldx, n, in_act, gw + (size_t)64 * 128, gb ? gb + 64 : nullptr, ws,
+                                        workspace_bytes, s);
+      } else {
+        return launch_wgrad<KK, MM, H>(g, gbf, ldg, x, xbf, ldx, n, in_act, gw, gb, ws, workspace_bytes, s);
+      }
+    };
+    return fmt == PANGNN_DTYPE_F16 ? run(f16s{}) : run(bf16s{});
+  });
 }
 
 extern "C" int pangnn_linear_act_wgrad_f32(const float* g, int64_t ldg, const float* x, int64_t ldx, int64_t n,
@@ -1519,9 +1381,11 @@ extern "C" int pangnn_embed_linear_fwd(const float* r, const float* s, int64_t n
   PG_CHECK_ARG(r && s && w_emb && b_emb && w_in && w_out && y && ldy >= M, PANGNN_E_BADARG, "%s: bad pointer / ld", who);
   PG_CHECK_ARG(aligned16(w_out), PANGNN_E_ALIGN, "%s: w_out must be 16-byte aligned", who);
   hipStream_t st = (hipStream_t)stream;
-  if (H == 64 && M == 64) return launch_gen_fwd<64, 64>(r, s, w_emb, b_emb, w_in, b_in, D, w_out, bias_out, y, ldy, n, st);
-  if (H == 64 && M == 128) return launch_gen_fwd<64, 128>(r, s, w_emb, b_emb, w_in, b_in, D, w_out, bias_out, y, ldy, n, st);
-  return launch_gen_fwd<128, 64>(r, s, w_emb, b_emb, w_in, b_in, D, w_out, bias_out, y, ldy, n, st);
+  return with_shape(H, M, [&](auto h, auto m) {
+    constexpr int HH = decltype(h)::value, MM = decltype(m)::value;
+    if constexpr (HH == 128 && MM == 128) return (int)PANGNN_E_BADARG;      // rejected above: no kernels for this shape
+    else return launch_gen_fwd<HH, MM>(r, s, w_emb, b_emb, w_in, b_in, D, w_out, bias_out, y, ldy, n, st);
+  });
 }
 
 extern "C" size_t pangnn_embed_linear_bwd_workspace_bytes(int32_t H, int32_t M) {
@@ -1544,9 +1408,9 @@ extern "C" int pangnn_embed_linear_bwd(const float* g, int64_t ldg, const float*
   PG_CHECK_ARG(n == 0 || aligned16(g), PANGNN_E_ALIGN, "%s: g rows must start on 16 bytes", who);
   hipStream_t st = (hipStream_t)stream;
   float* ws = static_cast<float*>(workspace);
-#define PG_GB(HH, MM) return launch_gen_bwd<HH, MM>(g, ldg, r, s, w_emb, b_emb, w_in, b_in, D, w_out, n, g_w_out, g_b_out, sums, ws, st)
-  if (H == 64 && M == 64) PG_GB(64, 64);
-  if (H == 64 && M == 128) PG_GB(64, 128);
-  PG_GB(128, 64);
-#undef PG_GB
+  return with_shape(H, M, [&](auto h, auto m) {
+    constexpr int HH = decltype(h)::value, MM = decltype(m)::value;
+    if constexpr (HH == 128 && MM == 128) return (int)PANGNN_E_BADARG;      // rejected above: no kernels for this shape
+    else return launch_gen_bwd<HH, MM>(g, ldg, r, s, w_emb, b_emb, w_in, b_in, D, w_out, n, g_w_out, g_b_out, sums, ws, st);
+  });
 }
