@@ -30,7 +30,8 @@ extern "C" {
 /* 3 (round 5, later): PANGNN_DTYPE_F16 accepted by the node-level *_dtype arguments, pangnn_spmm_csr_f16 added; the 128 x 128
  * weight gradient is covered (pangnn_linear_supported(128, 128, 1) = 1). */
 /* 3, extended: pangnn_linear_act_backward_parts_f32 added.  No entry point changed its signature or meaning, so the number
- * stays; the binding resolves every symbol at load, which refuses an older library of the same number. */
+ * stays; the binding resolves every symbol at load, which refuses an older library of the same number.
+ * Likewise pangnn_edge_dot_mixed, pangnn_gcn_norm_bwd_f32 and its _workspace_bytes (dL/d(edge_weight) of GCNConv). */
 #define PANGNN_ABI_VERSION 3
 
 #define PANGNN_E_BADARG    (-1)  /* null pointer / negative size / unsupported feature width */
@@ -799,6 +800,52 @@ int    pangnn_csr_plan(const int64_t* rowptr, int64_t n_rows, int64_t num_edges,
 int64_t pangnn_mask_k_smallest_workspace_bytes(int64_t n);
 int    pangnn_mask_k_smallest_i64(const int64_t* keys, int64_t n, int64_t k, uint8_t* keep, void* workspace,
                                   int64_t workspace_bytes, pangnn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * dL/d(edge_weight) of GCNConv (csrc/edge_weight_grad.hip).  With deg[v] = sum of w_e over the in-edges of v,
+ * dis = deg^-1/2 (0 where deg == 0), w^_e = dis[src_e] w_e dis[dst_e], out = A^ x + b and g = dL/dout:
+ *   gw_e    = <g[dst_e, :], x[src_e, :]>                  (pangnn_edge_dot_mixed over the by-target CSR)
+ *   t_e     = gw_e w_e
+ *   gdis[v] = sum_{e: dst_e = v} t_e dis[src_e] + sum_{e: src_e = v} t_e dis[dst_e]
+ *   gdeg[v] = -1/2 dis[v]^3 gdis[v], 0 where dis[v] == 0   (torch's masked_fill; a target whose in-edges all weigh 0 is
+ *                                                           0 * inf = NaN in torch and DEFINED as 0 here)
+ *   dL/dw_e = dis[src_e] dis[dst_e] gw_e + gdeg[dst_e]    (pangnn_gcn_norm_bwd_f32, in the caller's edge order)
+ *
+ * pangnn_edge_dot_mixed: for every entry k of row r of a CSR (rowptr int64 [n_rows + 1], idx int32 [nnz], perm int32
+ * [nnz]) out_sorted[k] = <g[r, 0:F], x[idx[k], 0:F]>, and the same value goes to out_orig[perm[k]] when out_orig is given
+ * (perm may be NULL otherwise).  g [g_rows >= n_rows, F] and x [x_rows, F] are separate tables (a rectangular structure is
+ * describable), each read as stored: *_dtype = PANGNN_DTYPE_F32 (rows on 16 bytes) or _BF16 / _F16 (rows on 8 bytes; two
+ * 2-byte tables of one call have the same type), row strides ldg / ldx in elements, multiples of 4.  F in {16, 32, 64, 128,
+ * 256} for float32 tables, {32, 64, 128, 256} as soon as one table has 2-byte rows (the widths the propagate gathers in that
+ * type); anything else: PANGNN_E_BADARG.  Every product and sum is fp32 in a fixed order (four fused multiply-adds per lane,
+ * a butterfly over the F / 4 lanes of an entry): 2-byte rows give the bits of the float32 call on the up-converted rows.
+ * Work is dealt out by entries, not rows (a wave per chunk of consecutive entries): a hub row is shared by many waves and,
+ * every output being one entry's own dot product, no part sums exist.  Along a row the g piece stays in registers.
+ * nnz == 0 launches nothing; nnz, n_rows or x_rows >= 2^31: PANGNN_E_TOOLARGE.
+ *
+ * pangnn_gcn_norm_bwd_f32: the four lines below gw_e above, for a SQUARE structure given as edge_index (int64 [2, ld], the
+ * caller's order) and both CSR orders (rowptr int64 [num_nodes + 1], other = opposite endpoint, perm = original edge id).
+ * A CSR order with hub rows also brings its segment table in the form pangnn_edge_score_bwd_mixed takes (seg_ptr int64
+ * [num_seg + 1], parts_rowptr int64 [num_nodes + 1], every row owning at least one segment; both NULL: the rows are walked
+ * as they are).  w, gw [num_edges] in the caller's order, dis [num_nodes]; gweight [num_edges] is written in the caller's
+ * order.  No float atomics: a 16-lane group per row (per segment) — lane j adds the entries j, j + 16, ... of the row in
+ * ascending CSR position, the 16 lane sums meet in a fixed butterfly; a hub row's segment partials are added in index
+ * order by the same scheme.  The result is a function of (structure, w, gw, dis): bit-reproducible.
+ * `workspace`: pangnn_gcn_norm_bwd_workspace_bytes(num_nodes, num_seg_dst, num_seg_src) bytes (segment counts 0 for an
+ * order without a table; passed as an int64_t), 16-byte aligned; smaller, negative or NULL: PANGNN_E_WORKSPACE.  num_edges == 0 launches nothing.
+ * ---------------------------------------------------------------------------------------- */
+int    pangnn_edge_dot_mixed(const int64_t* rowptr, const int32_t* idx, const int32_t* perm, const void* g, int32_t g_dtype,
+                             int64_t ldg, int64_t g_rows, const void* x, int32_t x_dtype, int64_t ldx, int64_t x_rows,
+                             int64_t n_rows, int64_t nnz, int32_t F, float* out_sorted, float* out_orig,
+                             pangnn_stream_t stream);
+int64_t pangnn_gcn_norm_bwd_workspace_bytes(int64_t num_nodes, int64_t num_seg_dst, int64_t num_seg_src);
+int    pangnn_gcn_norm_bwd_f32(const int64_t* edge_index, int64_t ld, int64_t num_edges, int64_t num_nodes,
+                               const int64_t* rowptr_dst, const int32_t* other_dst, const int32_t* perm_dst,
+                               const int64_t* seg_ptr_dst, const int64_t* parts_rowptr_dst, int64_t num_seg_dst,
+                               const int64_t* rowptr_src, const int32_t* other_src, const int32_t* perm_src,
+                               const int64_t* seg_ptr_src, const int64_t* parts_rowptr_src, int64_t num_seg_src,
+                               const float* w, const float* gw, const float* dis, float* gweight, void* workspace,
+                               int64_t workspace_bytes, pangnn_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -162,6 +162,14 @@ SIGNATURES = {
     # the mask of the k smallest keys (csrc/mask_select.hip): (keys, n, k, keep, workspace, bytes, stream)
     "pangnn_mask_k_smallest_workspace_bytes": (_i64, [_i64]),
     "pangnn_mask_k_smallest_i64": (C.c_int, [_p, _i64, _i64, _p, _p, _i64, _p]),
+    # dL/d(edge_weight) of GCNConv (csrc/edge_weight_grad.hip): (rowptr, idx, perm, g, g_dtype, ldg, g_rows, x, x_dtype, ldx,
+    # x_rows, n_rows, nnz, F, out_sorted, out_orig, stream)
+    "pangnn_edge_dot_mixed": (C.c_int, [_p, _p, _p, _p, _i32, _i64, _i64, _p, _i32, _i64, _i64, _i64, _i64, _i32, _p, _p, _p]),
+    # (edge_index, ld, num_edges, num_nodes, by target: rowptr / other / perm / seg_ptr / parts_rowptr / num_seg, by source:
+    # the same six, w, gw, dis, gweight, workspace, bytes, stream)
+    "pangnn_gcn_norm_bwd_workspace_bytes": (_i64, [_i64, _i64, _i64]),
+    "pangnn_gcn_norm_bwd_f32": (C.c_int, [_p, _i64, _i64, _i64, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _p, _i64,
+                                          _p, _p, _p, _p, _p, _i64, _p]),
 }
 
 ABI_VERSION = 3          # PANGNN_ABI_VERSION of include/pangnn_hip.h this binding was written against

@@ -134,10 +134,19 @@ class GCNConv(MessagePassing):
             # raise on the length mismatch, so do we
             raise ValueError(f"edge_weight has {edge_weight.shape[0]} entries for {st.num_edges} edges")
         norm = st.gcn_norm(edge_weight)
+        # differentiable edge weights: the propagate whose backward also yields dL/d(edge_weight) (PF.propagate_w: the same
+        # forward launch; ctypes route, no dispatcher op, no band kernel) — in every other case nothing below changes
+        wgrad = PF.wants_weight_grad(edge_weight)
+
+        def propagate(rows, bias, out_dtype=None):
+            if wgrad:
+                return PF.propagate_w(rows, bias, st, edge_weight, tag=name or None, out_dtype=out_dtype)
+            return PF.propagate_any(rows, bias, st, norm, edge_weight is None, tag=name or None, out_dtype=out_dtype)
+
         if dense_done:
             if self.in_channels < self.out_channels or x.shape[1] != self.out_channels:
                 raise ValueError("dense_done=True needs a dense-first layer (in >= out) and x = lin(input)")
-            return PF.propagate_any(x, self.bias, st, norm, edge_weight is None, tag=name or None)
+            return propagate(x, self.bias)
         if not (x.dtype in PF.ROWS16 and self.in_channels >= self.out_channels):
             x = x.float()          # (a 16-bit-stored input of a dense-first layer is read as stored by the linear kernel)
         # Under bf16 / fp16 autocast (`accelerate` mixed precision, SURVEY.md §8b, src/setup.py:50) PyG's propagate gathers
@@ -153,13 +162,12 @@ class GCNConv(MessagePassing):
             # 64 -> 128), then the dense layer with the bias fused
             # ... and their sum is what the autocast Linear casts to the autocast type first thing: cast once, stored
             # (out_dtype), so that the Linear reads 2-byte rows and the transposed propagate gathers its 16-bit gradient as stored
-            agg = PF.propagate_any(x.to(rows16) if rows16 else x, None, st, norm, edge_weight is None,
-                                   tag=name or None, out_dtype=rows16)
+            agg = propagate(x.to(rows16) if rows16 else x, None, rows16)
             # the autocast Linear's output is a 16-bit tensor (src/gnn.py:111 under mixed precision): stored as such
             return PF.linear(agg, self.lin.weight, self.bias, 0, rows16)
         # dense part first: under autocast its result is WRITTEN in the autocast type by the linear kernel (no separate cast)
         xw = self.lin(x, 1 if in_elu else 0, rows16)
-        return PF.propagate_any(xw, self.bias, st, norm, edge_weight is None, tag=name or None)
+        return propagate(xw, self.bias)
 
     def message(self, x_j, edge_weight):            # kept for API parity; forward() is fused
         return edge_weight.view(-1, 1) * x_j

@@ -733,6 +733,10 @@ class DistAlternateGCN(AlternateGCN):
         # a back end's `linear` need not take out_dtype (the CPU restatement of the tests does not): passed only when set
         return self.ops.linear(x, w, b, in_act, *(() if out_dtype is None else (out_dtype,)))
 
+    def _weight_grad(self, shard) -> bool:
+        """edge weights are constants on partitioned shards (the edge-weight gradient covers whole graphs only)"""
+        return False
+
     def _edge_weight(self, shard, name, conv=None):
         """as AlternateGCN._edge_weight; a shard keeps the union graph's weights beside the sim edges' (partition_graph)"""
         if name == "union" and conv is not self.conv_out:

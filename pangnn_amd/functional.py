@@ -146,8 +146,8 @@ def colsum(g: torch.Tensor) -> torch.Tensor:
 
 class _Propagate(torch.autograd.Function):
     """out = A_hat @ x + bias with A_hat given by (structure, norm).  Backward is the transposed
-    propagate over the source-grouped CSR (k5^T); edge weights are not differentiated (they are a
-    leaf without grad in the reference: SURVEY.md §8 a6)."""
+    propagate over the source-grouped CSR (k5^T); edge weights are not differentiated here (they are a
+    leaf without grad in the reference: SURVEY.md §8 a6) — weights that require grad take _PropagateW."""
 
     @staticmethod
     def forward(ctx, x, bias, st: EdgeStructure, norm: GcnNorm, tag=None, out_dtype=None):
@@ -236,6 +236,135 @@ def propagate(x, bias, st: EdgeStructure, norm: GcnNorm, tag=None, out_dtype=Non
     return _Propagate.apply(x, bias, st, norm, tag, out_dtype)
 
 
+# ---- dL/d(edge_weight) of the propagate (csrc/edge_weight_grad.hip; DESIGN.md "Edge-weight gradients")
+def _dot_rows(t: torch.Tensor) -> torch.Tensor:
+    """a table as pangnn_edge_dot_mixed reads it: bfloat16 / float16 rows as stored at the widths the propagate gathers in
+    that type, anything else as float32; unit column stride, rows on 8 / 16 bytes"""
+    two = t.dtype in ROWS16 and t.shape[1] in (32, 64, 128, 256)
+    if not two and t.dtype != torch.float32:
+        t = t.float()
+    if t.stride(1) != 1 or t.stride(0) % 4 or t.stride(0) < t.shape[1] or t.data_ptr() % (8 if two else 16):
+        t = t.contiguous()
+        if t.data_ptr() % 16:
+            t = t.clone()
+    return t
+
+
+def edge_dot(csr: CSR, g: torch.Tensor, x: torch.Tensor, want_orig: bool = True):
+    """(out_sorted, out_orig): out_sorted[k] = <g[r], x[csr.other[k]]> for every entry k of row r of `csr`, and the same
+    values in the caller's edge order (out_orig[csr.perm[k]]) when `want_orig` — pangnn_edge_dot_mixed.  `g` has a row per
+    CSR row; both tables are read as stored (float32 / bfloat16 / float16), every product and sum is fp32."""
+    lib = _lib.load()
+    _lib.require_device(g, x, csr.rowptr)
+    if g.dim() != 2 or x.dim() != 2 or g.shape[1] != x.shape[1]:
+        raise ValueError(f"edge_dot: g and x must be matrices of one width, got {tuple(g.shape)} and {tuple(x.shape)}")
+    g, x = _dot_rows(g), _dot_rows(x)
+    if g.dtype in ROWS16 and x.dtype in ROWS16 and g.dtype != x.dtype:
+        g, x = g.float(), x.float()              # (one call never mixes the two 2-byte types)
+    n_rows, nnz = csr.rowptr.shape[0] - 1, int(csr.other.shape[0])
+    out_sorted = torch.empty(nnz, dtype=torch.float32, device=x.device)
+    out_orig = torch.empty(nnz, dtype=torch.float32, device=x.device) if want_orig else None
+    with _lib.device_guard(x.device):
+        ev = _timer_start("wgrad.dot")
+        _lib.check(lib.pangnn_edge_dot_mixed(csr.rowptr.data_ptr(), _lib.ptr(csr.other), _lib.ptr(csr.perm), g.data_ptr(), _dt(g),
+                                             g.stride(0), g.shape[0], x.data_ptr(), _dt(x), x.stride(0), x.shape[0], n_rows,
+                                             nnz, x.shape[1], out_sorted.data_ptr(), _lib.ptr(out_orig), _lib.stream_ptr()),
+                   "pangnn_edge_dot_mixed")
+        _timer_stop("wgrad.dot", ev)
+    return out_sorted, out_orig
+
+
+def gcn_norm_backward(st: EdgeStructure, norm: GcnNorm, gw: torch.Tensor) -> torch.Tensor:
+    """dL/d(edge_weight) [E] (fp32, the caller's edge order) from gw = dL/d(normalised weight) [E] in the caller's order:
+    pangnn_gcn_norm_bwd_f32 on the weights `norm` was made of.  Whole (square) graphs."""
+    lib = _lib.load()
+    _whole_graph("gcn_norm_backward", st)
+    if norm.weight is None:
+        raise ValueError("gcn_norm_backward: the normalisation was made without edge weights")
+    _lib.require_device(gw)
+    gw = _f32c(gw)
+    e, n = st.num_edges, st.num_nodes
+    if gw.shape != (e,):
+        raise ValueError(f"gcn_norm_backward: gw must be [{e}], got {tuple(gw.shape)}")
+    d, s = st.by_dst, st.by_src
+    ld, ls = d.long_rows(), s.long_rows()
+    nd, ns = (0 if ld is None else ld[0].shape[0] - 1), (0 if ls is None else ls[0].shape[0] - 1)
+    out = torch.empty(e, dtype=torch.float32, device=gw.device)
+    with _lib.device_guard(gw.device):
+        ws_bytes = lib.pangnn_gcn_norm_bwd_workspace_bytes(n, nd, ns)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=gw.device)
+        ev = _timer_start("wgrad.norm")
+        _lib.check(lib.pangnn_gcn_norm_bwd_f32(
+            st.edge_index.data_ptr(), e, e, n,
+            d.rowptr.data_ptr(), _lib.ptr(d.other), _lib.ptr(d.perm), None if ld is None else ld[0].data_ptr(),
+            None if ld is None else ld[1].data_ptr(), nd,
+            s.rowptr.data_ptr(), _lib.ptr(s.other), _lib.ptr(s.perm), None if ls is None else ls[0].data_ptr(),
+            None if ls is None else ls[1].data_ptr(), ns,
+            norm.weight.data_ptr(), gw.data_ptr(), norm.deg_inv_sqrt.data_ptr(), out.data_ptr(), ws.data_ptr(), ws_bytes,
+            _lib.stream_ptr()), "pangnn_gcn_norm_bwd_f32")
+        _timer_stop("wgrad.norm", ev)
+    return out
+
+
+def wants_weight_grad(edge_weight) -> bool:
+    """the edge weights are a differentiable input of this call: propagate_w is the route.  That route is ctypes only, so
+    where a tracer or a dispatch / function mode is watching it raises instead of dropping the gradient."""
+    if edge_weight is None or not edge_weight.requires_grad or not torch.is_grad_enabled():
+        return False
+    if observed():
+        raise NotImplementedError("pangnn_amd: the gradient with respect to edge_weight has no dispatcher op yet — it cannot "
+                                  "be traced, compiled or run under a dispatch / function mode; detach the weights or run "
+                                  "eagerly")
+    return True
+
+
+class _PropagateW(torch.autograd.Function):
+    """_Propagate with the edge weights as a differentiable input: the same forward launches, the same gx / gb calls, and
+    dL/d(edge_weight) = gcn_norm's backward of the per-edge dot products <g[dst_e], x[src_e]> — computed only when asked for."""
+
+    @staticmethod
+    def forward(ctx, x, bias, edge_weight, st: EdgeStructure, tag=None, out_dtype=None):
+        norm = st.gcn_norm(edge_weight)
+        ctx.st, ctx.norm, ctx.tag = st, norm, tag
+        ctx.has_bias = bias is not None
+        ctx.x_dtype, ctx.w_dtype = x.dtype, edge_weight.dtype
+        ctx.save_for_backward(x)
+        out = spmm_csr(st.by_dst, norm.by_dst, x, st.num_nodes, bias=None if bias is None else _f32c(bias),
+                       tag=None if tag is None else tag + ".fwd")
+        return out.to(out_dtype) if out_dtype in ROWS16 else out
+
+    @staticmethod
+    def backward(ctx, g):
+        st, norm = ctx.st, ctx.norm
+        if not (g.dtype in ROWS16 and g.shape[1] in (32, 64, 128, 256)):     # 2-byte rows: gathered as stored
+            g = _f32c(g)
+        gx = spmm_csr(st.by_src, norm.by_src, g, st.num_src,
+                      tag=None if ctx.tag is None else ctx.tag + ".bwd") if ctx.needs_input_grad[0] else None
+        gb = colsum(g) if (ctx.has_bias and ctx.needs_input_grad[1]) else None
+        if gx is not None and gx.dtype != ctx.x_dtype:
+            gx = gx.to(ctx.x_dtype)
+        gw = None
+        if ctx.needs_input_grad[2]:
+            (x,) = ctx.saved_tensors
+            gw = gcn_norm_backward(st, norm, edge_dot(st.by_dst, g, x)[1])
+            if gw.dtype != ctx.w_dtype:
+                gw = gw.to(ctx.w_dtype)
+        return gx, gb, gw, None, None, None
+
+
+def propagate_w(x, bias, st: EdgeStructure, edge_weight, tag=None, out_dtype=None):
+    """out = A_hat x + bias like `propagate`, differentiable in `edge_weight` [E] too (a leaf or not).  The forward is
+    st.gcn_norm(edge_weight) + the propagate's launch — the bits `propagate` gives; ctypes route only (no dispatcher op, no
+    band kernel); whole (square) graphs."""
+    _lib.require_device(x, bias, edge_weight)
+    _whole_graph("propagate_w", st)
+    if edge_weight is None or edge_weight.dim() != 1 or edge_weight.shape[0] != st.num_edges:
+        raise ValueError(f"propagate_w: edge_weight must be [{st.num_edges}], got "
+                         f"{None if edge_weight is None else tuple(edge_weight.shape)}")
+    wants_weight_grad(edge_weight)               # (raises where a tracer / dispatch mode is watching: no dispatcher op)
+    return _PropagateW.apply(x, bias, edge_weight, st, tag, out_dtype)
+
+
 class _BandPropagate(torch.autograd.Function):
     """out = A_hat x + bias for the positional-neighbour band graph (EdgeStructure.band_width() = k > 0, unit weights):
     pangnn_band_propagate — the sums of the generic propagate in the same order, no index arrays.  The band is
@@ -300,7 +429,8 @@ def propagate_any(x, bias, st: EdgeStructure, norm: GcnNorm, unit_weights: bool,
 
 
 class _EdgeGatherConcat(torch.autograd.Function):
-    """cat(z[src], z[dst] [, extra]) per edge (gnn.py:173-175).  Backward = two segment sums."""
+    """cat(z[src], z[dst] [, extra]) per edge (gnn.py:173-175).  Backward = two segment sums; dL/dextra is the last column of
+    the upstream gradient."""
 
     @staticmethod
     def forward(ctx, z, st: EdgeStructure, extra):
@@ -317,6 +447,7 @@ class _EdgeGatherConcat(torch.autograd.Function):
                                                          out.data_ptr(), out.stride(0), d,
                                                          _lib.stream_ptr()), "pangnn_edge_gather_concat_f32")
         ctx.st, ctx.d = st, d
+        ctx.extra_like = None if extra is None else (extra.shape, extra.dtype)
         return out
 
     @staticmethod
@@ -326,7 +457,12 @@ class _EdgeGatherConcat(torch.autograd.Function):
         assert st.num_src == st.num_nodes, "edge_gather_concat is defined on a whole (square) graph"
         gz = segment_sum_rows(st.by_src, g, 0, d, st.num_nodes)
         segment_sum_rows(st.by_dst, g, d, d, st.num_nodes, out=gz, accumulate=True)
-        return gz, None, None
+        ge = None
+        if ctx.extra_like is not None and ctx.needs_input_grad[2]:
+            shape, dtype = ctx.extra_like
+            ge = torch.zeros(shape, dtype=dtype, device=g.device)      # (entries past the edge list were never read)
+            ge.view(-1)[: g.shape[0]] = g[:, 2 * d]
+        return gz, None, ge
 
 
 def edge_gather_concat(z, st: EdgeStructure, extra=None):

@@ -114,6 +114,14 @@ class AlternateGCN(nn.Module):
         union weights there), none on "nb" (gnn.py:165) and for conv_out (gnn.py:138,165)"""
         return None if (name == "nb" or conv is self.conv_out) else graph.edge_attr
 
+    def _weight_grad(self, graph) -> bool:
+        """`graph.edge_attr` is a differentiable input of this call (it requires grad and grad is on).  Then the operators
+        that rest on per-graph cached A_hat x, A_hat 1 do not apply (a cached vector cannot carry a gradient): the first layer
+        takes the layer-by-layer route, every weighted GCN layer goes through GCNConv's PF.propagate_w route, and with
+        `--skip_connections`, where the weights are also the decoder's per-edge input, the decoder is the literal
+        gather-concat form.  Raises NotImplementedError where a tracer / dispatch mode is watching (PF.wants_weight_grad)."""
+        return PF.wants_weight_grad(getattr(graph, "edge_attr", None))
+
     def _linear(self, x, w, b, in_act: int = 0, out_dtype=None):
         """one node-level dense layer"""
         return PF.linear(x, w, b, in_act, out_dtype)
@@ -129,7 +137,8 @@ class AlternateGCN(nn.Module):
         _lib.require_device(x)
         if self.categorical_nodes:
             return self._conv(conv, self.embedding(x.long().view(-1)), graph, name)
-        if self.fuse_embedding and (self.fuse_embedding != "propagate" or conv.in_channels < conv.out_channels):
+        if self.fuse_embedding and (self.fuse_embedding != "propagate" or conv.in_channels < conv.out_channels) \
+                and not self._weight_grad(graph):
             st, norm = self._first_layer_graph(graph, name)
             out_dtype = PF.autocast_rows_dtype(x)          # the autocast Linear's output type (bf16 / fp16 mixed precision)
             if self.fuse_embedding != "propagate":
@@ -161,7 +170,7 @@ class AlternateGCN(nn.Module):
         (the reference's autocast stores those rows in the autocast type; the generated rows are fp32)."""
         x, conv = graph.x, self.conv_in
         if self.categorical_nodes or not self.fuse_first_dense or not self._fold_elu() or not self.fuse_embedding \
-                or self.fuse_embedding == "propagate":
+                or self.fuse_embedding == "propagate" or self._weight_grad(graph):
             return None
         if w_out.shape[1] != conv.out_channels or not PF.embed_linear_supported(conv.out_channels, w_out.shape[0]):
             return None
@@ -183,6 +192,7 @@ class AlternateGCN(nn.Module):
         activation runs inside that layer's kernels (`in_elu` / `in_act`) and only the LAST one can be left pending for
         the caller.  `graph` is whatever the primitives above take: a Data / Batch here, a shard in dist.py."""
         fl, fold = self.flags, self._fold_elu()
+        self._weight_grad(graph)         # (differentiable edge weights under a tracer / dispatch mode: raises before any launch)
         pre = (lambda h: h) if fold else self.activation_fct      # an ELU that is not folded runs as its own op
         if fl.union_edge_weights:                                              # gnn.py:128-139
             hid = self.conv_hidden
@@ -231,6 +241,11 @@ class AlternateGCN(nn.Module):
         """the per-edge input of `--skip_connections` (gnn.py:173), else None"""
         return graph.edge_attr[: graph.edge_index.shape[1]] if self.flags.skip_connections else None
 
+    def _literal_decoder(self, graph) -> bool:
+        """the decoder's per-edge input needs a gradient (`--skip_connections` with differentiable edge weights): the literal
+        gather-concat decoder, whose backward hands dL/dextra on — no fused kernels, no DeferredLogits"""
+        return bool(self.flags.skip_connections) and self._weight_grad(graph)
+
     def _pq_operands(self, z):
         """(w_pq, b_pq, cvec) of the re-associated first decoder layer"""
         lin0 = self.mlp[0]
@@ -251,7 +266,8 @@ class AlternateGCN(nn.Module):
         PF.fused_pq_backward_applies) the P | Q product is left to that operator: pq is None and layer = (z, w_pq, b_pq,
         in_act)."""
         z, pending = self._encode_pre(graph)
-        fused = "mlp" in self.flags.decoder and self.fused_decoder is True and self._fused_width() and torch.is_grad_enabled()
+        fused = "mlp" in self.flags.decoder and self.fused_decoder is True and self._fused_width() and torch.is_grad_enabled() \
+            and not self._literal_decoder(graph)
         if not (fused and pending and self._fold_elu()):
             z, pending = (self.activation_fct(z) if pending else z), False
         if not fused:
@@ -325,7 +341,7 @@ class AlternateGCN(nn.Module):
     def decode_mlp(self, z, graph) -> torch.Tensor:
         st = structure_of(graph.edge_index, z.shape[0], holder=graph, name="sim")
         d = z.shape[1]
-        if self.fused_decoder and d % 4 == 0:
+        if self.fused_decoder and d % 4 == 0 and not self._literal_decoder(graph):
             # `fused_decoder="pair_add"` keeps the layer-by-layer form behind the P | Q rows, which reads them as fp32
             fused = self._fused_width() and self.fused_decoder != "pair_add"
             pq, extra, cvec = self._decoder_pq(z, graph, rows16=fused)
@@ -346,7 +362,7 @@ class AlternateGCN(nn.Module):
         encoder and the node-level half of `mlp[0]` run here (inside accelerate's autocast wrapper of `forward`), the per-edge
         decoder when the handle is used — as ONE pass with the loss and every gradient if that use is
         `BCEWithLogitsLoss(pos_weight)(output, labels)` (pangnn.py:98,203), through the inference kernel on any other use."""
-        if self._defers():
+        if self._defers() and not self._literal_decoder(graph):
             ops, z = self._fused_decoder_operands(graph)
             if ops is not None:
                 return self._deferred(graph, *ops)

@@ -556,6 +556,7 @@ class GcnNorm:
             if edge_weight.dim() != 1 or edge_weight.shape[0] < e:
                 raise ValueError(f"edge_weight must be [E>={e}], got {tuple(edge_weight.shape)}")
             edge_weight = edge_weight.detach().to(torch.float32).contiguous()
+        self.weight = edge_weight               # the fp32 contiguous weights that were normalised (functional.propagate_w's backward)
         d = st.by_dst
         ea, na = -(-e // 4) * 4, -(-n // 4) * 4                          # one allocation, 16-byte aligned segments
         small = e <= (1 << 20)                  # small graphs: the by-source table too (a launch-bound step counts allocations)
