@@ -313,12 +313,6 @@ View lookup(const char* op, const at::Tensor& edge_index, int64_t n_dst, const c
 // ---------------------------------------------------------------------------------------------------------------
 // small shared pieces
 // ---------------------------------------------------------------------------------------------------------------
-at::Tensor f32c(const at::Tensor& t) { return t.to(at::kFloat).contiguous(); }
-c10::optional<at::Tensor> f32c(const c10::optional<at::Tensor>& t) {
-  if (t.has_value() && t->defined()) return f32c(*t);
-  return c10::nullopt;
-}
-bool defined(const c10::optional<at::Tensor>& t) { return t.has_value() && t->defined(); }
 at::Tensor bytes(size_t n, const at::Tensor& ref) { return at::empty({(int64_t)n}, ref.options().dtype(at::kByte)); }
 
 // out[r] = bias + sum_{k in row r} val[k] x[other[k]] (f32 rows, or bfloat16 rows gathered as stored); fp32 result
@@ -338,26 +332,7 @@ at::Tensor spmm_rows(const Csr& csr, const at::Tensor& val, const at::Tensor& x,
              "pangnn_spmm_csr_f32(long-row parts)");
     return out;
   }
-  const bool rows16 = is_rows16(x) && (f == 32 || f == 64 || f == 128 || f == 256);
-  at::Tensor xc;
-  if (rows16) {
-    const bool ok = x.stride(1) == 1 && x.stride(0) % 4 == 0 && reinterpret_cast<uintptr_t>(x.data_ptr()) % 8 == 0;
-    xc = ok ? x : x.contiguous();
-  } else {
-    xc = f32c(x);
-  }
-  const auto bc = f32c(bias);
-  auto out = at::empty({n_rows, f}, x.options().dtype(at::kFloat));
-  const auto fn16 = xc.scalar_type() == at::kHalf ? pangnn_spmm_csr_f16 : pangnn_spmm_csr_bf16;
-  const int rc = rows16 ? fn16(csr.rowptr.data_ptr<int64_t>(), csr.other.data_ptr<int32_t>(), val.data_ptr<float>(), xc.data_ptr(),
-                               xc.stride(0), xc.size(0), opt_ptr<float>(bc), out.data_ptr<float>(), out.stride(0), n_rows,
-                               csr.other.size(0), (int32_t)f, 0, stream_of(x))
-                        : pangnn_spmm_csr_f32(csr.rowptr.data_ptr<int64_t>(), csr.other.data_ptr<int32_t>(), val.data_ptr<float>(),
-                                              xc.data_ptr<float>(), xc.stride(0), xc.size(0), opt_ptr<float>(bc),
-                                              out.data_ptr<float>(), out.stride(0), n_rows, csr.other.size(0), (int32_t)f, 0,
-                                              stream_of(x));
-  check_rc(rc, "pangnn_spmm_csr");
-  return out;
+  return spmm_gather(csr.rowptr, csr.other, val, x, bias, n_rows);
 }
 
 // column sums of dL/dout in fp32 (GCNConv's bias gradient): one launch for the short matrices of a mini-batch

@@ -1,5 +1,6 @@
 // Helpers shared by the two translation units of libpangnn_torch.so (torch_ops.cpp: the tensor ops; graph_ops.cpp: the
-// structure registry and the per-step ops that read a graph): stream / device guard / return-code / operand checks.
+// structure registry and the per-step ops that read a graph): stream / device guard / return-code / operand checks, row
+// preparation, and the one CSR gather launch both units make (spmm_gather).
 #pragma once
 #include <ATen/ATen.h>
 #include <ATen/core/dispatch/Dispatcher.h>
@@ -67,6 +68,13 @@ inline at::ScalarType scalar_of(int64_t code) {
   return code == PANGNN_DTYPE_BF16 ? at::kBFloat16 : code == PANGNN_DTYPE_F16 ? at::kHalf : at::kFloat;
 }
 
+inline bool defined(const c10::optional<at::Tensor>& t) { return t.has_value() && t->defined(); }
+inline at::Tensor f32c(const at::Tensor& t) { return t.to(at::kFloat).contiguous(); }
+inline c10::optional<at::Tensor> f32c(const c10::optional<at::Tensor>& t) {
+  if (defined(t)) return f32c(*t);
+  return c10::nullopt;
+}
+
 // rows as the kernels read them: f32 (any other float is converted) or bfloat16 / float16 as stored, unit column stride, a row stride
 // that keeps 16-byte loads aligned — column windows of a wider matrix pass through without a copy
 inline at::Tensor rows_any(const at::Tensor& t) {
@@ -83,6 +91,29 @@ inline at::Tensor rows_any(const at::Tensor& t) {
   return f.contiguous();
 }
 
+// out[r] = bias + sum_{k in row r} val[k] x[other[k]], f32 [n_rows, F]: ONE launch of pangnn_spmm_csr_f32, or of _bf16 / _f16 when
+// x holds 2-byte rows of a width the kernels gather as stored — those pass through with unit column stride, a row stride that is
+// a multiple of 4 elements and a base on 8 bytes (else .contiguous()); anything else is gathered as contiguous f32.  `val` and
+// `bias` are optional and read as contiguous f32; the operand checks are the caller's.
+inline at::Tensor spmm_gather(const at::Tensor& rowptr, const at::Tensor& other, const c10::optional<at::Tensor>& val,
+                              const at::Tensor& x, const c10::optional<at::Tensor>& bias, int64_t n_rows) {
+  const int64_t f = x.size(1);
+  const bool rows16 = is_rows16(x) && (f == 32 || f == 64 || f == 128 || f == 256);
+  const bool as_stored = rows16 && x.stride(1) == 1 && x.stride(0) % 4 == 0 && reinterpret_cast<uintptr_t>(x.data_ptr()) % 8 == 0;
+  const at::Tensor xc = as_stored ? x : rows16 ? x.contiguous() : f32c(x);
+  const auto vc = f32c(val), bc = f32c(bias);
+  auto out = at::empty({n_rows, f}, x.options().dtype(at::kFloat));
+  const auto fn16 = xc.scalar_type() == at::kHalf ? pangnn_spmm_csr_f16 : pangnn_spmm_csr_bf16;
+  const int rc = rows16 ? fn16(rowptr.data_ptr<int64_t>(), other.data_ptr<int32_t>(), opt_ptr<float>(vc), xc.data_ptr(),
+                               xc.stride(0), xc.size(0), opt_ptr<float>(bc), out.data_ptr<float>(), out.stride(0), n_rows,
+                               other.size(0), (int32_t)f, 0, stream_of(x))
+                        : pangnn_spmm_csr_f32(rowptr.data_ptr<int64_t>(), other.data_ptr<int32_t>(), opt_ptr<float>(vc),
+                                              xc.data_ptr<float>(), xc.stride(0), xc.size(0), opt_ptr<float>(bc),
+                                              out.data_ptr<float>(), out.stride(0), n_rows, other.size(0), (int32_t)f, 0,
+                                              stream_of(x));
+  check_rc(rc, "pangnn_spmm_csr");
+  return out;
+}
 
 template <typename Sig>
 auto typed_op(const char* name) {

@@ -76,23 +76,7 @@ at::Tensor spmm(const at::Tensor& rowptr, const at::Tensor& other, const c10::op
               "pangnn::spmm: val must have one entry per CSR entry (", other.size(0), ")");
   TORCH_CHECK(!(bias.has_value() && bias->defined()) || bias->numel() == x.size(1), "pangnn::spmm: bias must be [F]");
   const DeviceGuard guard(x.device());
-  const int64_t f = x.size(1);
-  const bool rows16 = is_rows16(x) && (f == 32 || f == 64 || f == 128 || f == 256);
-  at::Tensor xc = rows16 ? x.contiguous() : x.to(at::kFloat).contiguous();
-  c10::optional<at::Tensor> vc, bc;
-  if (val.has_value() && val->defined()) vc = val->to(at::kFloat).contiguous();
-  if (bias.has_value() && bias->defined()) bc = bias->to(at::kFloat).contiguous();
-  auto out = at::empty({n_rows, f}, x.options().dtype(at::kFloat));
-  const auto fn16 = xc.scalar_type() == at::kHalf ? pangnn_spmm_csr_f16 : pangnn_spmm_csr_bf16;
-  const int rc = rows16 ? fn16(rowptr.data_ptr<int64_t>(), other.data_ptr<int32_t>(), opt_ptr<float>(vc), xc.data_ptr(),
-                               xc.stride(0), xc.size(0), opt_ptr<float>(bc), out.data_ptr<float>(), out.stride(0), n_rows,
-                               other.size(0), (int32_t)f, 0, stream_of(x))
-                        : pangnn_spmm_csr_f32(rowptr.data_ptr<int64_t>(), other.data_ptr<int32_t>(), opt_ptr<float>(vc),
-                                              xc.data_ptr<float>(), xc.stride(0), xc.size(0), opt_ptr<float>(bc),
-                                              out.data_ptr<float>(), out.stride(0), n_rows, other.size(0), (int32_t)f, 0,
-                                              stream_of(x));
-  check_rc(rc, "pangnn_spmm_csr");
-  return out;
+  return spmm_gather(rowptr, other, val, x, bias, n_rows);
 }
 
 // propagate(rowptr, other, val, rowptr_t, other_t, val_t, x, bias?) -> f32 [N, F]: GCNConv's message passing

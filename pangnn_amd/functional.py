@@ -12,6 +12,9 @@ from .graph import CSR, EdgeStructure, GcnNorm
 
 
 ROWS16 = (torch.bfloat16, torch.float16)        # the two 2-byte row formats (PANGNN_DTYPE_BF16 / _F16)
+GATHER_WIDTHS = (32, 64, 128, 256)              # row widths the propagate kernels gather in a 2-byte format as stored
+PART_SUM_WIDTHS = (16, 32, 64, 128, 256)        # row widths of the contiguous part sum (the hub-row segments of spmm_csr)
+
 
 def _f32c(t: torch.Tensor) -> torch.Tensor:
     if t.dtype != torch.float32:
@@ -19,7 +22,51 @@ def _f32c(t: torch.Tensor) -> torch.Tensor:
     return t if t.is_contiguous() else t.contiguous()
 
 
-# Optional kernel timing for bench.py: when KERNEL_TIMER is a dict, every spmm launch whose `tag` is
+def _rows(t: torch.Tensor, keep16: bool, mult: int, align: int, may_overlap: bool = False,
+          realign: bool = False) -> torch.Tensor:
+    """`t` as a kernel reads a row table: float32 — or bfloat16 / float16 as stored when `keep16` — with unit column stride,
+    a row stride that is a multiple of `mult` elements (and no shorter than a row unless the rows `may_overlap`) and a base
+    on `align` bytes.  A table that already is all that comes back itself (a column window of a wider row-major matrix
+    passes without a copy); anything else as a contiguous copy, `realign`: one whose base lies on 16 bytes."""
+    if t.dtype != torch.float32 and not (keep16 and t.dtype in ROWS16):
+        t = t.float()
+    if t.dim() == 2 and t.stride(1) == 1 and t.stride(0) % mult == 0 and (may_overlap or t.stride(0) >= t.shape[1]) \
+            and t.data_ptr() % align == 0:
+        return t
+    t = t.contiguous()
+    return t.clone() if realign and t.data_ptr() % 16 else t
+
+
+def _rows_f32(t: torch.Tensor) -> torch.Tensor:
+    """fp32 with unit column stride and a 16-byte friendly row stride; column windows of a wider
+    row-major matrix pass through without a copy"""
+    return _rows(t, False, 4, 16)
+
+
+def _rows_any(t: torch.Tensor) -> torch.Tensor:
+    """_rows_f32 that lets bfloat16 / float16 storage through (the *_mixed entry points read it as stored)"""
+    return _rows(t, True, 8 if t.dtype in ROWS16 else 4, 16)
+
+
+def _gathered16(t: torch.Tensor) -> bool:
+    """2-byte rows that the propagate kernels gather as stored (half the bytes), not as float32 copies"""
+    return t.dtype in ROWS16 and t.shape[1] in GATHER_WIDTHS
+
+
+def _gather_rows(t: torch.Tensor) -> torch.Tensor:
+    """a table as pangnn_spmm_csr_* gathers it: 2-byte rows as stored (rows on 8 bytes) where _gathered16, else contiguous
+    float32"""
+    return _rows(t, True, 4, 8, may_overlap=True) if _gathered16(t) else _f32c(t)
+
+
+def _dot_rows(t: torch.Tensor) -> torch.Tensor:
+    """a table as pangnn_edge_dot_mixed reads it: bfloat16 / float16 rows as stored at the widths the propagate gathers in
+    that type, anything else as float32; unit column stride, rows on 8 / 16 bytes"""
+    two = _gathered16(t)
+    return _rows(t, two, 4, 8 if two else 16, realign=True)
+
+
+# Optional kernel timing for bench.py: when KERNEL_TIMER is a dict, every launch (_launch) whose `tag` is
 # a key gets a (start, end) torch.cuda.Event pair recorded on the launch stream (= torch's current
 # stream, the one passed to the C ABI) around the launch.
 KERNEL_TIMER = None
@@ -36,19 +83,27 @@ DECODER_PRECISION = int(os.environ.get("PANGNN_DECODER_PRECISION", "1"))
 DECODER_ND_WIDTHS = (32, 128)
 
 
-def _timer_start(tag):
-    if KERNEL_TIMER is None or tag not in KERNEL_TIMER:
-        return None
-    ev = torch.cuda.Event(enable_timing=True)
-    ev.record()
-    return ev
+def _launch(dev, name: str, *args, tag=None, label=None) -> None:
+    """One launch over the C ABI: entry point `name` with `args` + torch's current stream of `dev`, under the device guard.
+    When `tag` is a key of KERNEL_TIMER its event pair is recorded inside the guard, immediately around the launch.  `label`
+    replaces the name in the error text (the callers that say which of their launches failed)."""
+    fn = getattr(_lib.load(), name)
+    timed = KERNEL_TIMER is not None and tag in KERNEL_TIMER
+    with _lib.device_guard(dev):
+        if timed:
+            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            ev0.record()
+        _lib.check(fn(*args, _lib.stream_ptr()), label or name)
+        if timed:
+            ev1.record()
+            KERNEL_TIMER[tag].append((ev0, ev1))
 
 
-def _timer_stop(tag, ev0):
-    if ev0 is not None:
-        ev1 = torch.cuda.Event(enable_timing=True)
-        ev1.record()
-        KERNEL_TIMER[tag].append((ev0, ev1))
+def _workspace(dev, name: str, *args):
+    """(buffer, bytes): the scratch space `name`_workspace_bytes(*args) asks for on `dev` (some sizes count its compute units)"""
+    with _lib.device_guard(dev):
+        n = getattr(_lib.load(), name + "_workspace_bytes")(*args)
+    return torch.empty(n, dtype=torch.uint8, device=dev), n
 
 
 def spmm_csr(csr: CSR, val: Optional[torch.Tensor], x: torch.Tensor, n_rows: int,
@@ -56,10 +111,9 @@ def spmm_csr(csr: CSR, val: Optional[torch.Tensor], x: torch.Tensor, n_rows: int
              accumulate: bool = False, tag: Optional[str] = None) -> torch.Tensor:
     """out[r] (+)= bias + sum_e val[e] * x[other[e]]  — pangnn_spmm_csr_f32, or pangnn_spmm_csr_bf16 / _f16 when the
     gathered rows are stored as bfloat16 / float16 (fp32 weights / accumulation / result either way)."""
-    lib = _lib.load()
     _lib.require_device(x, csr.rowptr, val, bias)
     f = x.shape[1]
-    long = csr.long_rows() if csr.other is not None and f in (16, 32, 64, 128, 256) else None
+    long = csr.long_rows() if csr.other is not None and f in PART_SUM_WIDTHS else None
     if long is not None:
         # a hub row: the same kernel over segments of at most LONG_SEG entries (one partial row each), then the contiguous
         # part sum adds a row's partials in order, with the bias / accumulation of the call (graph.CSR.long_rows)
@@ -68,35 +122,18 @@ def spmm_csr(csr: CSR, val: Optional[torch.Tensor], x: torch.Tensor, n_rows: int
         if out is None:
             out = torch.empty(n_rows, f, dtype=torch.float32, device=x.device)
             accumulate = False
-        with _lib.device_guard(x.device):
-            _lib.check(lib.pangnn_spmm_csr_f32(parts_rowptr.data_ptr(), None, None, parts.data_ptr(), parts.stride(0),
-                                               parts.shape[0], _lib.ptr(None if bias is None else _f32c(bias)), out.data_ptr(),
-                                               out.stride(0), n_rows, parts.shape[0], f, int(accumulate), _lib.stream_ptr()),
-                       "pangnn_spmm_csr_f32(long-row parts)")
+        _launch(x.device, "pangnn_spmm_csr_f32", parts_rowptr.data_ptr(), None, None, parts.data_ptr(), parts.stride(0),
+                parts.shape[0], _lib.ptr(None if bias is None else _f32c(bias)), out.data_ptr(), out.stride(0), n_rows,
+                parts.shape[0], f, int(accumulate), label="pangnn_spmm_csr_f32(long-row parts)")
         return out
-    if x.dtype in ROWS16 and f in (32, 64, 128, 256):
-        if x.stride(1) != 1 or x.stride(0) % 4 or x.data_ptr() % 8:
-            x = x.contiguous()
-        fn, name = (lib.pangnn_spmm_csr_bf16, "pangnn_spmm_csr_bf16") if x.dtype == torch.bfloat16 \
-            else (lib.pangnn_spmm_csr_f16, "pangnn_spmm_csr_f16")
-    else:
-        x = _f32c(x)
-        fn, name = lib.pangnn_spmm_csr_f32, "pangnn_spmm_csr_f32"
+    x = _gather_rows(x)
     if out is None:
         out = torch.empty(n_rows, f, dtype=torch.float32, device=x.device)
         accumulate = False
-    timed = KERNEL_TIMER is not None and tag in KERNEL_TIMER
-    with _lib.device_guard(x.device):
-        if timed:
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record()
-        _lib.check(fn(csr.rowptr.data_ptr(), _lib.ptr(csr.other), _lib.ptr(val),
-                      x.data_ptr(), x.stride(0), x.shape[0], _lib.ptr(bias),
-                      out.data_ptr(), out.stride(0), n_rows, int(csr.other.shape[0]), f,
-                      int(accumulate), _lib.stream_ptr()), name)
-        if timed:
-            ev1.record()
-            KERNEL_TIMER[tag].append((ev0, ev1))
+    rows = "bf16" if x.dtype == torch.bfloat16 else "f16" if x.dtype == torch.float16 else "f32"
+    _launch(x.device, "pangnn_spmm_csr_" + rows, csr.rowptr.data_ptr(), _lib.ptr(csr.other), _lib.ptr(val), x.data_ptr(),
+            x.stride(0), x.shape[0], _lib.ptr(bias), out.data_ptr(), out.stride(0), n_rows, int(csr.other.shape[0]), f,
+            int(accumulate), tag=tag)
     return out
 
 
@@ -113,17 +150,13 @@ class _SegmentRows:
 def segment_sum_rows(csr: CSR, m: torch.Tensor, col_off: int, f: int, n_rows: int,
                      out: Optional[torch.Tensor] = None, accumulate: bool = False) -> torch.Tensor:
     """out[r] (+)= sum_{k in row r} m[perm[k], col_off:col_off+f] — pangnn_segment_sum_rows_f32."""
-    lib = _lib.load()
     _lib.require_device(m)
     assert m.dtype == torch.float32 and m.stride(1) == 1
     if out is None:
         out = torch.empty(n_rows, f, dtype=torch.float32, device=m.device)
         accumulate = False
-    with _lib.device_guard(m.device):
-        _lib.check(lib.pangnn_segment_sum_rows_f32(csr.rowptr.data_ptr(), _lib.ptr(csr.perm), m.data_ptr(),
-                                                   m.stride(0), m.shape[0], col_off, out.data_ptr(),
-                                                   out.stride(0), n_rows, f, int(accumulate),
-                                                   _lib.stream_ptr()), "pangnn_segment_sum_rows_f32")
+    _launch(m.device, "pangnn_segment_sum_rows_f32", csr.rowptr.data_ptr(), _lib.ptr(csr.perm), m.data_ptr(), m.stride(0),
+            m.shape[0], col_off, out.data_ptr(), out.stride(0), n_rows, f, int(accumulate))
     return out
 
 
@@ -135,13 +168,39 @@ def colsum(g: torch.Tensor) -> torch.Tensor:
     (torch's column reduction is a zero-fill + a reduce kernel there), torch's two-stage sum for long ones"""
     if g.is_cuda and g.dim() == 2 and g.shape[0] <= COLSUM_SMALL_ROWS and g.stride(1) == 1 and 0 < g.shape[1] <= 1024 \
             and (g.dtype == torch.float32 or g.dtype in ROWS16):
-        lib = _lib.load()
         out = torch.empty(g.shape[1], dtype=torch.float32, device=g.device)
-        with _lib.device_guard(g.device):
-            _lib.check(lib.pangnn_colsum_small(g.data_ptr(), _dt(g), g.stride(0), g.shape[0], g.shape[1], out.data_ptr(),
-                                               _lib.stream_ptr()), "pangnn_colsum_small")
+        _launch(g.device, "pangnn_colsum_small", g.data_ptr(), _dt(g), g.stride(0), g.shape[0], g.shape[1], out.data_ptr())
         return out
     return g.sum(dim=0, dtype=torch.float32)
+
+
+def _propagate_forward(ctx, x, bias, st: EdgeStructure, norm: GcnNorm, tag, out_dtype):
+    """the forward of _Propagate and _PropagateW: out = A_hat x + bias over the by-target CSR.
+    `out_dtype` = torch.bfloat16 / torch.float16 (autocast, a propagate-first GCNConv): the result is what an autocast
+    Linear consumes, i.e. it is cast to the autocast type first thing — done here once and stored, so the Linear reads
+    2-byte rows, its dL/dx comes back in that type (autograd's dtype rule; in the reference the backward of that cast hands
+    fp32 copies of the 16-bit values on) and the transposed propagate gathers it as stored: the same values as the
+    reference's, half the gather bytes."""
+    ctx.st, ctx.norm, ctx.tag = st, norm, tag
+    ctx.has_bias = bias is not None
+    ctx.x_dtype = x.dtype            # bfloat16 / float16 rows are gathered as stored (half the bytes); result fp32
+    out = spmm_csr(st.by_dst, norm.by_dst, x, st.num_nodes, bias=None if bias is None else _f32c(bias),
+                   tag=None if tag is None else tag + ".fwd")
+    return out.to(out_dtype) if out_dtype in ROWS16 else out
+
+
+def _propagate_backward(ctx, g):
+    """(g, gx, gb) of _Propagate and _PropagateW: the upstream gradient as the kernels read it, dL/dx by the transposed
+    propagate over the by-source CSR (k5^T) and dL/dbias, each only when asked for"""
+    st, norm = ctx.st, ctx.norm
+    if not _gathered16(g):
+        g = _f32c(g)
+    gx = spmm_csr(st.by_src, norm.by_src, g, st.num_src,
+                  tag=None if ctx.tag is None else ctx.tag + ".bwd") if ctx.needs_input_grad[0] else None
+    gb = colsum(g) if (ctx.has_bias and ctx.needs_input_grad[1]) else None
+    if gx is not None and gx.dtype != ctx.x_dtype:
+        gx = gx.to(ctx.x_dtype)
+    return g, gx, gb
 
 
 class _Propagate(torch.autograd.Function):
@@ -151,28 +210,11 @@ class _Propagate(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, bias, st: EdgeStructure, norm: GcnNorm, tag=None, out_dtype=None):
-        """`out_dtype` = torch.bfloat16 / torch.float16 (autocast, a propagate-first GCNConv): the result is what an autocast
-        Linear consumes, i.e. it is cast to the autocast type first thing — done here once and stored, so the Linear reads
-        2-byte rows, its dL/dx comes back in that type (autograd's dtype rule; in the reference the backward of that cast hands
-        fp32 copies of the 16-bit values on) and the transposed propagate gathers it as stored: the same values as the
-        reference's, half the gather bytes."""
-        ctx.st, ctx.norm, ctx.tag = st, norm, tag
-        ctx.has_bias = bias is not None
-        ctx.x_dtype = x.dtype            # bfloat16 / float16 rows are gathered as stored (half the bytes); result fp32
-        out = spmm_csr(st.by_dst, norm.by_dst, x, st.num_nodes, bias=None if bias is None else _f32c(bias),
-                       tag=None if tag is None else tag + ".fwd")
-        return out.to(out_dtype) if out_dtype in ROWS16 else out
+        return _propagate_forward(ctx, x, bias, st, norm, tag, out_dtype)
 
     @staticmethod
     def backward(ctx, g):
-        st, norm = ctx.st, ctx.norm
-        if not (g.dtype in ROWS16 and g.shape[1] in (32, 64, 128, 256)):     # 2-byte rows: gathered as stored
-            g = _f32c(g)
-        gx = spmm_csr(st.by_src, norm.by_src, g, st.num_src,
-                      tag=None if ctx.tag is None else ctx.tag + ".bwd") if ctx.needs_input_grad[0] else None
-        gb = colsum(g) if (ctx.has_bias and ctx.needs_input_grad[1]) else None
-        if gx is not None and gx.dtype != ctx.x_dtype:
-            gx = gx.to(ctx.x_dtype)
+        _, gx, gb = _propagate_backward(ctx, g)
         return gx, gb, None, None, None, None
 
 
@@ -228,33 +270,28 @@ def _whole_graph(op: str, st: EdgeStructure) -> None:
                          f"{st.num_nodes} target rows")
 
 
+def _torch_ops():
+    """pangnn_amd.torch_ops (the Python side of the dispatcher ops), imported on first use: that module imports this one half
+    way down"""
+    from . import torch_ops
+    return torch_ops
+
+
+def _op_route(st: EdgeStructure, norm, tag=None) -> bool:
+    """this call goes to its dispatcher op: _via_ops, and a normalisation that carries `weight_ref`, the caller's weight
+    tensor by which the ops' registry finds it (graph.GcnNorm, graph.TracedNorm; a stand-in object without one stays here)"""
+    return _via_ops(st, tag) and getattr(norm, "weight_ref", norm) is not norm
+
+
 def propagate(x, bias, st: EdgeStructure, norm: GcnNorm, tag=None, out_dtype=None):
-    if _via_ops(st, tag) and getattr(norm, "weight_ref", norm) is not norm:
-        from . import torch_ops
-        _lib.require_device(x, bias)
-        return torch_ops.gcn_propagate(x, bias, st, norm, False, out_dtype)
-    return _Propagate.apply(x, bias, st, norm, tag, out_dtype)
+    return propagate_any(x, bias, st, norm, False, tag, out_dtype)
 
 
 # ---- dL/d(edge_weight) of the propagate (csrc/edge_weight_grad.hip; DESIGN.md "Edge-weight gradients")
-def _dot_rows(t: torch.Tensor) -> torch.Tensor:
-    """a table as pangnn_edge_dot_mixed reads it: bfloat16 / float16 rows as stored at the widths the propagate gathers in
-    that type, anything else as float32; unit column stride, rows on 8 / 16 bytes"""
-    two = t.dtype in ROWS16 and t.shape[1] in (32, 64, 128, 256)
-    if not two and t.dtype != torch.float32:
-        t = t.float()
-    if t.stride(1) != 1 or t.stride(0) % 4 or t.stride(0) < t.shape[1] or t.data_ptr() % (8 if two else 16):
-        t = t.contiguous()
-        if t.data_ptr() % 16:
-            t = t.clone()
-    return t
-
-
 def edge_dot(csr: CSR, g: torch.Tensor, x: torch.Tensor, want_orig: bool = True):
     """(out_sorted, out_orig): out_sorted[k] = <g[r], x[csr.other[k]]> for every entry k of row r of `csr`, and the same
     values in the caller's edge order (out_orig[csr.perm[k]]) when `want_orig` — pangnn_edge_dot_mixed.  `g` has a row per
     CSR row; both tables are read as stored (float32 / bfloat16 / float16), every product and sum is fp32."""
-    lib = _lib.load()
     _lib.require_device(g, x, csr.rowptr)
     if g.dim() != 2 or x.dim() != 2 or g.shape[1] != x.shape[1]:
         raise ValueError(f"edge_dot: g and x must be matrices of one width, got {tuple(g.shape)} and {tuple(x.shape)}")
@@ -264,20 +301,15 @@ def edge_dot(csr: CSR, g: torch.Tensor, x: torch.Tensor, want_orig: bool = True)
     n_rows, nnz = csr.rowptr.shape[0] - 1, int(csr.other.shape[0])
     out_sorted = torch.empty(nnz, dtype=torch.float32, device=x.device)
     out_orig = torch.empty(nnz, dtype=torch.float32, device=x.device) if want_orig else None
-    with _lib.device_guard(x.device):
-        ev = _timer_start("wgrad.dot")
-        _lib.check(lib.pangnn_edge_dot_mixed(csr.rowptr.data_ptr(), _lib.ptr(csr.other), _lib.ptr(csr.perm), g.data_ptr(), _dt(g),
-                                             g.stride(0), g.shape[0], x.data_ptr(), _dt(x), x.stride(0), x.shape[0], n_rows,
-                                             nnz, x.shape[1], out_sorted.data_ptr(), _lib.ptr(out_orig), _lib.stream_ptr()),
-                   "pangnn_edge_dot_mixed")
-        _timer_stop("wgrad.dot", ev)
+    _launch(x.device, "pangnn_edge_dot_mixed", csr.rowptr.data_ptr(), _lib.ptr(csr.other), _lib.ptr(csr.perm), g.data_ptr(),
+            _dt(g), g.stride(0), g.shape[0], x.data_ptr(), _dt(x), x.stride(0), x.shape[0], n_rows, nnz, x.shape[1],
+            out_sorted.data_ptr(), _lib.ptr(out_orig), tag="wgrad.dot")
     return out_sorted, out_orig
 
 
 def gcn_norm_backward(st: EdgeStructure, norm: GcnNorm, gw: torch.Tensor) -> torch.Tensor:
     """dL/d(edge_weight) [E] (fp32, the caller's edge order) from gw = dL/d(normalised weight) [E] in the caller's order:
     pangnn_gcn_norm_bwd_f32 on the weights `norm` was made of.  Whole (square) graphs."""
-    lib = _lib.load()
     _whole_graph("gcn_norm_backward", st)
     if norm.weight is None:
         raise ValueError("gcn_norm_backward: the normalisation was made without edge weights")
@@ -290,19 +322,14 @@ def gcn_norm_backward(st: EdgeStructure, norm: GcnNorm, gw: torch.Tensor) -> tor
     ld, ls = d.long_rows(), s.long_rows()
     nd, ns = (0 if ld is None else ld[0].shape[0] - 1), (0 if ls is None else ls[0].shape[0] - 1)
     out = torch.empty(e, dtype=torch.float32, device=gw.device)
-    with _lib.device_guard(gw.device):
-        ws_bytes = lib.pangnn_gcn_norm_bwd_workspace_bytes(n, nd, ns)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=gw.device)
-        ev = _timer_start("wgrad.norm")
-        _lib.check(lib.pangnn_gcn_norm_bwd_f32(
-            st.edge_index.data_ptr(), e, e, n,
+    ws, ws_bytes = _workspace(gw.device, "pangnn_gcn_norm_bwd", n, nd, ns)
+    _launch(gw.device, "pangnn_gcn_norm_bwd_f32", st.edge_index.data_ptr(), e, e, n,
             d.rowptr.data_ptr(), _lib.ptr(d.other), _lib.ptr(d.perm), None if ld is None else ld[0].data_ptr(),
             None if ld is None else ld[1].data_ptr(), nd,
             s.rowptr.data_ptr(), _lib.ptr(s.other), _lib.ptr(s.perm), None if ls is None else ls[0].data_ptr(),
             None if ls is None else ls[1].data_ptr(), ns,
             norm.weight.data_ptr(), gw.data_ptr(), norm.deg_inv_sqrt.data_ptr(), out.data_ptr(), ws.data_ptr(), ws_bytes,
-            _lib.stream_ptr()), "pangnn_gcn_norm_bwd_f32")
-        _timer_stop("wgrad.norm", ev)
+            tag="wgrad.norm")
     return out
 
 
@@ -324,29 +351,17 @@ class _PropagateW(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, bias, edge_weight, st: EdgeStructure, tag=None, out_dtype=None):
-        norm = st.gcn_norm(edge_weight)
-        ctx.st, ctx.norm, ctx.tag = st, norm, tag
-        ctx.has_bias = bias is not None
-        ctx.x_dtype, ctx.w_dtype = x.dtype, edge_weight.dtype
+        ctx.w_dtype = edge_weight.dtype
         ctx.save_for_backward(x)
-        out = spmm_csr(st.by_dst, norm.by_dst, x, st.num_nodes, bias=None if bias is None else _f32c(bias),
-                       tag=None if tag is None else tag + ".fwd")
-        return out.to(out_dtype) if out_dtype in ROWS16 else out
+        return _propagate_forward(ctx, x, bias, st, st.gcn_norm(edge_weight), tag, out_dtype)
 
     @staticmethod
     def backward(ctx, g):
-        st, norm = ctx.st, ctx.norm
-        if not (g.dtype in ROWS16 and g.shape[1] in (32, 64, 128, 256)):     # 2-byte rows: gathered as stored
-            g = _f32c(g)
-        gx = spmm_csr(st.by_src, norm.by_src, g, st.num_src,
-                      tag=None if ctx.tag is None else ctx.tag + ".bwd") if ctx.needs_input_grad[0] else None
-        gb = colsum(g) if (ctx.has_bias and ctx.needs_input_grad[1]) else None
-        if gx is not None and gx.dtype != ctx.x_dtype:
-            gx = gx.to(ctx.x_dtype)
+        g, gx, gb = _propagate_backward(ctx, g)
         gw = None
         if ctx.needs_input_grad[2]:
             (x,) = ctx.saved_tensors
-            gw = gcn_norm_backward(st, norm, edge_dot(st.by_dst, g, x)[1])
+            gw = gcn_norm_backward(ctx.st, ctx.norm, edge_dot(ctx.st.by_dst, g, x)[1])
             if gw.dtype != ctx.w_dtype:
                 gw = gw.to(ctx.w_dtype)
         return gx, gb, gw, None, None, None
@@ -390,18 +405,14 @@ class _BandPropagate(torch.autograd.Function):
 
 
 def _band_call(x, bias, dis, k, want_colsum):
-    lib = _lib.load()
     _lib.require_device(x, bias, dis)
     x = _rows_any(x)
     n, f = x.shape
     out = torch.empty(n, f, dtype=torch.float32, device=x.device)
     cs = torch.empty(f, dtype=torch.float32, device=x.device) if want_colsum else None
-    with _lib.device_guard(x.device):
-        ws_bytes = lib.pangnn_band_propagate_workspace_bytes(f) if want_colsum else 0
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if want_colsum else None
-        _lib.check(lib.pangnn_band_propagate(x.data_ptr(), _dt(x), x.stride(0), dis.data_ptr(), _lib.ptr(bias), out.data_ptr(),
-                                             out.stride(0), n, f, k, _lib.ptr(cs), _lib.ptr(ws), ws_bytes,
-                                             _lib.stream_ptr()), "pangnn_band_propagate")
+    ws, ws_bytes = _workspace(x.device, "pangnn_band_propagate", f) if want_colsum else (None, 0)
+    _launch(x.device, "pangnn_band_propagate", x.data_ptr(), _dt(x), x.stride(0), dis.data_ptr(), _lib.ptr(bias), out.data_ptr(),
+            out.stride(0), n, f, k, _lib.ptr(cs), _lib.ptr(ws), ws_bytes)
     return out, cs
 
 
@@ -417,15 +428,14 @@ def _band_ok(x, st: EdgeStructure, unit_weights: bool) -> bool:
 
 def propagate_any(x, bias, st: EdgeStructure, norm: GcnNorm, unit_weights: bool, tag=None, out_dtype=None):
     """GCNConv's message passing: the band kernel when the structure is the positional-neighbour band with unit weights
-    (whole-graph mode of the reference), the general CSR kernels otherwise.  `out_dtype`: see _Propagate.forward."""
-    if _via_ops(st, tag) and getattr(norm, "weight_ref", norm) is not norm:
-        from . import torch_ops
+    (whole-graph mode of the reference), the general CSR kernels otherwise.  `out_dtype`: see _propagate_forward."""
+    if _op_route(st, norm, tag):
         _lib.require_device(x, bias)
-        return torch_ops.gcn_propagate(x, bias, st, norm, unit_weights, out_dtype)   # the op makes the same band / CSR choice
+        return _torch_ops().gcn_propagate(x, bias, st, norm, unit_weights, out_dtype)   # the op makes the same band / CSR choice
     if _band_ok(x, st, unit_weights) and (KERNEL_TIMER is None or tag is None or (tag + ".fwd") not in KERNEL_TIMER):
         y = band_propagate(x, bias, st, norm)
         return y.to(out_dtype) if out_dtype in ROWS16 else y
-    return propagate(x, bias, st, norm, tag, out_dtype)
+    return _Propagate.apply(x, bias, st, norm, tag, out_dtype)
 
 
 class _EdgeGatherConcat(torch.autograd.Function):
@@ -434,18 +444,14 @@ class _EdgeGatherConcat(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z, st: EdgeStructure, extra):
-        lib = _lib.load()
         _lib.require_device(z, extra)
         z = _f32c(z)
         e, d = st.num_edges, z.shape[1]
         width = 2 * d + (1 if extra is not None else 0)
         out = torch.empty(e, width, dtype=torch.float32, device=z.device)
         ex = None if extra is None else _f32c(extra)
-        with _lib.device_guard(z.device):
-            _lib.check(lib.pangnn_edge_gather_concat_f32(z.data_ptr(), z.stride(0), z.shape[0],
-                                                         st.edge_index.data_ptr(), e, 0, e, _lib.ptr(ex),
-                                                         out.data_ptr(), out.stride(0), d,
-                                                         _lib.stream_ptr()), "pangnn_edge_gather_concat_f32")
+        _launch(z.device, "pangnn_edge_gather_concat_f32", z.data_ptr(), z.stride(0), z.shape[0], st.edge_index.data_ptr(),
+                e, 0, e, _lib.ptr(ex), out.data_ptr(), out.stride(0), d)
         ctx.st, ctx.d = st, d
         ctx.extra_like = None if extra is None else (extra.shape, extra.dtype)
         return out
@@ -475,7 +481,6 @@ class _EdgePairAdd(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, p, q, st: EdgeStructure, extra, cvec):
-        lib = _lib.load()
         _lib.require_device(p, q, extra, cvec)
         p, q = _f32c(p), _f32c(q)
         assert p.shape[1] == q.shape[1] and p.stride(0) == q.stride(0)
@@ -483,11 +488,8 @@ class _EdgePairAdd(torch.autograd.Function):
         out = torch.empty(e, d, dtype=torch.float32, device=p.device)
         ex = None if extra is None else _f32c(extra)
         cv = None if cvec is None else _f32c(cvec)
-        with _lib.device_guard(p.device):
-            _lib.check(lib.pangnn_edge_pair_add_f32(p.data_ptr(), q.data_ptr(), p.stride(0), p.shape[0],
-                                                    st.edge_index.data_ptr(), e, 0, e, _lib.ptr(ex),
-                                                    _lib.ptr(cv), out.data_ptr(), out.stride(0), d,
-                                                    _lib.stream_ptr()), "pangnn_edge_pair_add_f32")
+        _launch(p.device, "pangnn_edge_pair_add_f32", p.data_ptr(), q.data_ptr(), p.stride(0), p.shape[0],
+                st.edge_index.data_ptr(), e, 0, e, _lib.ptr(ex), _lib.ptr(cv), out.data_ptr(), out.stride(0), d)
         ctx.st, ctx.d = st, d
         ctx.save_for_backward(ex)
         return out
@@ -513,18 +515,14 @@ class _SegmentMax(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, msg, st: EdgeStructure):
-        lib = _lib.load()
         _lib.require_device(msg)
         msg = _f32c(msg)
         n, f = st.num_nodes, msg.shape[1]
         d = st.by_dst
         out = torch.empty(n, f, dtype=torch.float32, device=msg.device)
         arg = torch.empty(n, f, dtype=torch.int32, device=msg.device)
-        with _lib.device_guard(msg.device):
-            _lib.check(lib.pangnn_segment_max_rows_f32(d.rowptr.data_ptr(), _lib.ptr(d.perm), msg.data_ptr(),
-                                                       msg.stride(0), out.data_ptr(), arg.data_ptr(),
-                                                       out.stride(0), n, f, _lib.stream_ptr()),
-                       "pangnn_segment_max_rows_f32")
+        _launch(msg.device, "pangnn_segment_max_rows_f32", d.rowptr.data_ptr(), _lib.ptr(d.perm), msg.data_ptr(),
+                msg.stride(0), out.data_ptr(), arg.data_ptr(), out.stride(0), n, f)
         ctx.st, ctx.e = st, msg.shape[0]
         ctx.save_for_backward(arg)
         ctx.mark_non_differentiable(arg)
@@ -532,16 +530,13 @@ class _SegmentMax(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        lib = _lib.load()
         (arg,) = ctx.saved_tensors
         st = ctx.st
         g = _f32c(g)
         n, f = g.shape
         gm = torch.zeros(ctx.e, f, dtype=torch.float32, device=g.device)
-        with _lib.device_guard(g.device):
-            _lib.check(lib.pangnn_segment_max_bwd_f32(g.data_ptr(), arg.data_ptr(), st.by_dst.rowptr.data_ptr(),
-                                                      gm.data_ptr(), gm.stride(0), g.stride(0), n, f,
-                                                      _lib.stream_ptr()), "pangnn_segment_max_bwd_f32")
+        _launch(g.device, "pangnn_segment_max_bwd_f32", g.data_ptr(), arg.data_ptr(), st.by_dst.rowptr.data_ptr(),
+                gm.data_ptr(), gm.stride(0), g.stride(0), n, f)
         return gm, None
 
 
@@ -592,8 +587,7 @@ def edge_conv(x, w1, b1, w2, b2, st: EdgeStructure, return_arg: bool = False):
     wa, wb = w1[:, :c], w1[:, c:]
     u = linear(x, (wa - wb).contiguous(), b1)
     v = linear(x, wb.contiguous(), None)
-    from . import torch_ops
-    out, arg = torch_ops.edge_conv(u, v, w2, b2, st)      # the only route: pangnn::edge_conv (csrc/graph_ops.cpp)
+    out, arg = _torch_ops().edge_conv(u, v, w2, b2, st)   # the only route: pangnn::edge_conv (csrc/graph_ops.cpp)
     return (out, arg) if return_arg else out
 
 
@@ -609,14 +603,11 @@ def _sum_parts(plan, part_buf: torch.Tensor, n_rows: int, out: torch.Tensor, acc
     """out[s - row_lo] (+)= sum of the consecutive part rows of source s, s in [row_lo, row_lo + n_rows)
     (pangnn_spmm_csr_f32, idx = NULL; the row pointer's entries are absolute part positions, so a window of rows is the same
     call on the shifted pointer)"""
-    lib = _lib.load()
     if n_rows <= 0:
         return out
-    with _lib.device_guard(part_buf.device):
-        _lib.check(lib.pangnn_spmm_csr_f32(plan.part_rowptr.data_ptr() + 8 * int(row_lo), None, None, _lib.ptr(part_buf),
-                                           part_buf.stride(0), part_buf.shape[0], None, out.data_ptr(),
-                                           out.stride(0), n_rows, part_buf.shape[0], part_buf.shape[1], int(accumulate),
-                                           _lib.stream_ptr()), "pangnn_spmm_csr_f32(parts)")
+    _launch(part_buf.device, "pangnn_spmm_csr_f32", plan.part_rowptr.data_ptr() + 8 * int(row_lo), None, None,
+            _lib.ptr(part_buf), part_buf.stride(0), part_buf.shape[0], None, out.data_ptr(), out.stride(0), n_rows,
+            part_buf.shape[0], part_buf.shape[1], int(accumulate), label="pangnn_spmm_csr_f32(parts)")
     return out
 
 
@@ -626,23 +617,15 @@ def _dgrad_sum(rec, st: EdgeStructure, by: Optional[str], w2, w3, n_rows: int = 
     kernel: pangnn_decoder_dgrad_f32 (run parts) + the short contiguous part sum.  `g_b2`: also filled with dL/db2
     (one call per step asks for it); by = None: the parameter sums alone.  `raw_parts`: no part sum — (plan, parts) come
     back for pangnn_linear_act_backward_parts_f32."""
-    lib = _lib.load()
     dev = rec.device
     plan = st.csr_plan(by, d16_chunk(st.num_edges)) if by else None
     csr = None if not by else (st.by_dst if by == "dst" else st.by_src)
     parts = None if plan is None else torch.empty(plan.n_parts, 64, dtype=torch.float32, device=dev)
-    with _lib.device_guard(dev):
-        ws_bytes = lib.pangnn_decoder_dgrad_workspace_bytes() if g_b2 is not None else 0
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
-        ev = _timer_start("dec.dgrad")
-        _lib.check(lib.pangnn_decoder_dgrad_f32(rec.data_ptr(), None if csr is None else _lib.ptr(csr.perm),
-                                                None if plan is None else plan.keys.data_ptr(),
-                                                w2.data_ptr(), w3.data_ptr(), st.num_edges, _lib.ptr(parts),
-                                                None if plan is None else plan.part_off.data_ptr(),
-                                                _lib.ptr(g_b2), _lib.ptr(live), _lib.ptr(ws), ws_bytes,
-                                                _lib.stream_ptr()),
-                   "pangnn_decoder_dgrad_f32")
-        _timer_stop("dec.dgrad", ev)
+    ws, ws_bytes = _workspace(dev, "pangnn_decoder_dgrad") if g_b2 is not None else (None, 0)
+    _launch(dev, "pangnn_decoder_dgrad_f32", rec.data_ptr(), None if csr is None else _lib.ptr(csr.perm),
+            None if plan is None else plan.keys.data_ptr(), w2.data_ptr(), w3.data_ptr(), st.num_edges, _lib.ptr(parts),
+            None if plan is None else plan.part_off.data_ptr(), _lib.ptr(g_b2), _lib.ptr(live), _lib.ptr(ws), ws_bytes,
+            tag="dec.dgrad")
     if plan is None:
         return None
     if raw_parts:
@@ -650,6 +633,14 @@ def _dgrad_sum(rec, st: EdgeStructure, by: Optional[str], w2, w3, n_rows: int = 
     if out is None:
         out, accumulate = torch.empty(n_rows, 64, device=dev), False
     return _sum_parts(plan, parts, n_rows, out, accumulate)
+
+
+def _grad_rows(out, n_rows: int, d: int, dev, empty_list: bool) -> torch.Tensor:
+    """the output rows of a decoder gradient: the given buffer or a fresh [n_rows, d] one, zeroed when the edge list is empty
+    (no kernel writes them then)"""
+    if out is None:
+        out = torch.empty(n_rows, d, device=dev)
+    return out.zero_() if empty_list else out
 
 
 def _decoder_train16(p, q, st: EdgeStructure, ex, cv, w2, b2, w3, b3, y=None, pw=None, denom=0, g_logits=None,
@@ -669,7 +660,6 @@ def _decoder_train16(p, q, st: EdgeStructure, ex, cv, w2, b2, w3, b3, y=None, pw
     the rows in between); the returned gp is then the list of those tensors.  `out_logits`: where the fused-loss logits go.
     `raw_parts` (a non-empty source-sorted list, no windows): neither part sum is launched — gp and gq are the (plan, parts)
     pairs of S and T, which pangnn_linear_act_backward_parts_f32 sums inside the P | Q layer's backward."""
-    lib = _lib.load()
     dev = p.device
     e, d = st.num_edges, p.shape[1]
     fused = y is not None
@@ -681,33 +671,29 @@ def _decoder_train16(p, q, st: EdgeStructure, ex, cv, w2, b2, w3, b3, y=None, pw
     rec = torch.empty(max(e, 1), 8, dtype=torch.int32, device=dev)
     plan = st.runsum_plan(d16_chunk(e)) if (need_p and e > 0) else None
     parts = None if plan is None else torch.empty(plan.n_parts, d, dtype=torch.float32, device=dev)
-    with _lib.device_guard(dev):
-        ws_bytes = lib.pangnn_decoder_train_workspace_bytes()
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        ev = _timer_start("dec.bwd")
-        if p.dtype != q.dtype:
-            raise ValueError("p and q must be stored alike (both float32, both bfloat16 or both float16)")
-        _lib.check(lib.pangnn_decoder_train_mixed(
+    if p.dtype != q.dtype:
+        raise ValueError("p and q must be stored alike (both float32, both bfloat16 or both float16)")
+    ws, ws_bytes = _workspace(dev, "pangnn_decoder_train")
+    _launch(dev, "pangnn_decoder_train_mixed",
             p.data_ptr(), p.stride(0), q.data_ptr(), q.stride(0), _dt(p), max(p.shape[0], q.shape[0]),
             st.edge_index.data_ptr(), e, e, _lib.ptr(ex), _lib.ptr(cv), w2.data_ptr(), b2.data_ptr(), w3.data_ptr(),
             b3.data_ptr(), d, _lib.ptr(y), _lib.ptr(pw), int(denom), _lib.ptr(g_logits), _lib.ptr(logits),
             _lib.ptr(loss), rec.data_ptr(), _lib.ptr(parts), None if plan is None else plan.part_off.data_ptr(),
-            g_w2.data_ptr(), g_w3.data_ptr(), g_b3.data_ptr(), _lib.ptr(g_cv), _lib.ptr(live), ws.data_ptr(),
-            ws_bytes, _lib.stream_ptr()), "pangnn_decoder_train_mixed")
-        _timer_stop("dec.bwd", ev)
+            g_w2.data_ptr(), g_w3.data_ptr(), g_b3.data_ptr(), _lib.ptr(g_cv), _lib.ptr(live), ws.data_ptr(), ws_bytes,
+            tag="dec.bwd")
     gp = gq = None
     b2_out = g_b2          # dL/db2 comes out of exactly one dgrad call
     if need_p:
         if e == 0 and p_windows is not None:
             gp = [o.zero_() for _, _, o in p_windows]
         elif e == 0:
-            gp = (out_p if out_p is not None else torch.empty(p.shape[0], d, device=dev)).zero_()
+            gp = _grad_rows(out_p, p.shape[0], d, dev, True)
         elif raw_parts:
             gp = (plan, parts)
         elif plan is not None and p_windows is not None:
             gp = [_sum_parts(plan, parts, hi - lo, o, row_lo=lo) for lo, hi, o in p_windows]
         elif plan is not None:
-            gp = _sum_parts(plan, parts, p.shape[0], out_p if out_p is not None else torch.empty(p.shape[0], d, device=dev))
+            gp = _sum_parts(plan, parts, p.shape[0], _grad_rows(out_p, p.shape[0], d, dev, False))
         else:
             gp = _dgrad_sum(rec, st, "src", w2, w3, p.shape[0], out_p, g_b2=b2_out, live=live)
             b2_out = None
@@ -718,7 +704,7 @@ def _decoder_train16(p, q, st: EdgeStructure, ex, cv, w2, b2, w3, b3, y=None, pw
     if need_q:
         acc_q = bool(accumulate_q) and out_q is not None
         if e == 0:
-            gq = out_q if acc_q else (out_q if out_q is not None else torch.empty(q.shape[0], d, device=dev)).zero_()
+            gq = out_q if acc_q else _grad_rows(out_q, q.shape[0], d, dev, True)
         else:
             gq = _dgrad_sum(rec, st, "dst", w2, w3, q.shape[0], out_q, g_b2=b2_out, live=live, accumulate=acc_q,
                             raw_parts=raw_parts)
@@ -729,27 +715,6 @@ def _decoder_train16(p, q, st: EdgeStructure, ex, cv, w2, b2, w3, b3, y=None, pw
         else:
             _dgrad_sum(rec, st, None, w2, w3, g_b2=b2_out, live=live)
     return loss, logits, gp, gq, g_cv, g_w2, g_b2, g_w3, g_b3
-
-
-def _rows_f32(t: torch.Tensor) -> torch.Tensor:
-    """fp32 with unit column stride and a 16-byte friendly row stride; column windows of a wider
-    row-major matrix pass through without a copy"""
-    if t.dtype != torch.float32:
-        t = t.float()
-    if t.dim() == 2 and t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.stride(0) >= t.shape[1] \
-            and t.data_ptr() % 16 == 0:
-        return t
-    return t.contiguous()
-
-
-def _rows_any(t: torch.Tensor) -> torch.Tensor:
-    """_rows_f32 that lets bfloat16 / float16 storage through (the *_mixed entry points read it as stored)"""
-    if t.dtype not in ROWS16:
-        return _rows_f32(t)
-    if t.dim() == 2 and t.stride(1) == 1 and t.stride(0) % 8 == 0 and t.stride(0) >= t.shape[1] \
-            and t.data_ptr() % 16 == 0:
-        return t
-    return t.contiguous()
 
 
 def autocast_rows_dtype(t: torch.Tensor):
@@ -814,7 +779,6 @@ def _decoder_f32(p, q, st: EdgeStructure, ex, cv, w2, b2, w3, b3, y=None, pw=Non
     dL/dQ by target, into `out_p` / `out_q` when given (e.g. the column windows of one [N, 2D] gradient)."""
     if live is not None:
         raise ValueError("live= (a padded fixed-shape batch) needs node_dim 64 in the default precision mode")
-    lib = _lib.load()
     dev = p.device
     e, d = st.num_edges, p.shape[1]
     nd = d in DECODER_ND_WIDTHS
@@ -828,31 +792,27 @@ def _decoder_f32(p, q, st: EdgeStructure, ex, cv, w2, b2, w3, b3, y=None, pw=Non
     g_cv = None if cv is None else torch.empty_like(cv)
     plan = st.runsum_plan() if (need_p and e > 0) else None
     parts = None if plan is None else torch.empty(plan.n_parts, d, dtype=torch.float32, device=dev)
-    with _lib.device_guard(dev):
-        ws_bytes = lib.pangnn_decoder_nd_bwd_workspace_bytes(d, e) if nd else lib.pangnn_decoder_mlp_bwd_workspace_bytes(e)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        head = _decoder_head(p, q, st, ex, cv, w2, b2, w3, b3)
-        tail = (_lib.ptr(g_h1), g_w2.data_ptr(), g_b2.data_ptr(), g_w3.data_ptr(), g_b3.data_ptr(), _lib.ptr(g_cv),
-                _lib.ptr(parts), None if plan is None else plan.part_off.data_ptr()) + (() if nd else (DECODER_PRECISION,)) + \
-               (ws.data_ptr(), ws_bytes, _lib.stream_ptr())
-        ev = _timer_start("dec.bwd")
-        if fused:
-            _lib.check(getattr(lib, name + "loss_f32")(*head, _lib.ptr(y), _lib.ptr(pw), int(denom), _lib.ptr(logits),
-                                                       loss.data_ptr(), *tail), name + "loss_f32")
-        else:
-            _lib.check(getattr(lib, name + "bwd_f32")(*head, _lib.ptr(g_logits), *tail), name + "bwd_f32")
-        _timer_stop("dec.bwd", ev)
+    ws, ws_bytes = _workspace(dev, name + "bwd", *((d, e) if nd else (e,)))
+    head = _decoder_head(p, q, st, ex, cv, w2, b2, w3, b3)
+    tail = (_lib.ptr(g_h1), g_w2.data_ptr(), g_b2.data_ptr(), g_w3.data_ptr(), g_b3.data_ptr(), _lib.ptr(g_cv),
+            _lib.ptr(parts), None if plan is None else plan.part_off.data_ptr()) + (() if nd else (DECODER_PRECISION,)) + \
+           (ws.data_ptr(), ws_bytes)
+    if fused:
+        _launch(dev, name + "loss_f32", *head, _lib.ptr(y), _lib.ptr(pw), int(denom), _lib.ptr(logits), loss.data_ptr(),
+                *tail, tag="dec.bwd")
+    else:
+        _launch(dev, name + "bwd_f32", *head, _lib.ptr(g_logits), *tail, tag="dec.bwd")
     gp = gq = None
     if need_p:
         if e == 0:
-            gp = (out_p if out_p is not None else torch.empty(p.shape[0], d, device=dev)).zero_()
+            gp = _grad_rows(out_p, p.shape[0], d, dev, True)
         elif plan is not None:     # per-run partial rows came out of the kernel: short contiguous sum
-            gp = _sum_parts(plan, parts, p.shape[0], out_p if out_p is not None else torch.empty(p.shape[0], d, device=dev))
+            gp = _sum_parts(plan, parts, p.shape[0], _grad_rows(out_p, p.shape[0], d, dev, False))
         else:
             gp = segment_sum_rows(st.by_src, g_h1, 0, d, p.shape[0], out=out_p)
     if need_q:
         if e == 0:
-            gq = (out_q if out_q is not None else torch.empty(q.shape[0], d, device=dev)).zero_()
+            gq = _grad_rows(out_q, q.shape[0], d, dev, True)
         else:
             gq = segment_sum_rows(st.by_dst, g_h1, 0, d, q.shape[0], out=out_q)
     return loss, logits, gp, gq, g_cv, g_w2, g_b2, g_w3, g_b3
@@ -881,24 +841,17 @@ class _DecoderMLP(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, p, q, st: EdgeStructure, extra, cvec, w2, b2, w3, b3, pq_joint=False):
-        lib = _lib.load()
         _lib.require_device(p, q, extra, cvec, w2, b2, w3, b3)
         p, q, ex, cv, w2, b2, w3, b3, _, _ = _decoder_operands(p, None if pq_joint else q, extra, cvec, w2, b2, w3, b3)
         e, d = st.num_edges, p.shape[1]
         logits = torch.empty(e, dtype=torch.float32, device=p.device)
-        with _lib.device_guard(p.device):
-            ev = _timer_start("dec.fwd")
-            head = _decoder_head(p, q, st, ex, cv, w2, b2, w3, b3)
-            if d in DECODER_ND_WIDTHS:
-                _lib.check(lib.pangnn_decoder_nd_fwd_f32(*head, _lib.ptr(logits), _lib.stream_ptr()),
-                           "pangnn_decoder_nd_fwd_f32")
-            elif p.dtype in ROWS16:         # the tables' storage type goes in after the four table arguments
-                _lib.check(lib.pangnn_decoder_mlp_infer_mixed(*head[:4], _dt(p), *head[4:], _lib.ptr(logits),
-                                                              _lib.stream_ptr()), "pangnn_decoder_mlp_infer_mixed")
-            else:
-                _lib.check(lib.pangnn_decoder_mlp_infer_f32(*head, _lib.ptr(logits), DECODER_PRECISION, _lib.stream_ptr()),
-                           "pangnn_decoder_mlp_infer_f32")
-            _timer_stop("dec.fwd", ev)
+        head = _decoder_head(p, q, st, ex, cv, w2, b2, w3, b3)
+        if d in DECODER_ND_WIDTHS:
+            _launch(p.device, "pangnn_decoder_nd_fwd_f32", *head, _lib.ptr(logits), tag="dec.fwd")
+        elif p.dtype in ROWS16:         # the tables' storage type goes in after the four table arguments
+            _launch(p.device, "pangnn_decoder_mlp_infer_mixed", *head[:4], _dt(p), *head[4:], _lib.ptr(logits), tag="dec.fwd")
+        else:
+            _launch(p.device, "pangnn_decoder_mlp_infer_f32", *head, _lib.ptr(logits), DECODER_PRECISION, tag="dec.fwd")
         ctx.st, ctx.joint = st, pq_joint
         ctx.save_for_backward(p, q, ex, cv, w2, b2, w3, b3)
         return logits
@@ -927,8 +880,7 @@ def decoder_mlp_pq(pq, st: EdgeStructure, extra, cvec, w2, b2, w3, b3):
     """p = pq[:, :D], q = pq[:, D:] (one [N, 2D] node-level product)"""
     _lib.require_device(pq, extra, cvec, w2, b2, w3, b3)
     if _via_ops(st, _timed_decoder()) and DECODER_PRECISION == 1 and pq.shape[1] // 2 not in DECODER_ND_WIDTHS:
-        from . import torch_ops
-        return torch_ops.decoder_mlp_pq(pq, st, extra, cvec, w2, b2, w3, b3)
+        return _torch_ops().decoder_mlp_pq(pq, st, extra, cvec, w2, b2, w3, b3)
     return _DecoderMLP.apply(pq, None, st, extra, cvec, w2, b2, w3, b3, True)
 
 
@@ -945,8 +897,7 @@ def unit_grad(device) -> torch.Tensor:
     if t is None:
         t = _UNIT_GRAD[key] = torch.ones((), dtype=torch.float32, device=key)
         if key.type == "cuda":             # the C++ autograd formula of pangnn::decoder_loss recognises it by address too
-            from . import torch_ops
-            torch_ops.ops._set_unit_grad(t)
+            _torch_ops().ops._set_unit_grad(t)
     return t
 
 
@@ -974,16 +925,19 @@ def scale_by_loss_grad_(ctx, tensors, go):
     for t in live:
         if t.dtype != torch.float32 or not t.is_contiguous():
             return [None if u is None else u * go for u in tensors]
-    lib = _lib.load()
     n = len(live)
     if n:
         import ctypes as C
         g32 = go if go.dtype == torch.float32 else go.float()
-        with _lib.device_guard(g32.device):
-            _lib.check(lib.pangnn_scale_unless_one_f32((C.c_void_p * n)(*[t.data_ptr() for t in live]),
-                                                       (C.c_int64 * n)(*[t.numel() for t in live]), n,
-                                                       g32.data_ptr(), _lib.stream_ptr()), "pangnn_scale_unless_one_f32")
+        _launch(g32.device, "pangnn_scale_unless_one_f32", (C.c_void_p * n)(*[t.data_ptr() for t in live]),
+                (C.c_int64 * n)(*[t.numel() for t in live]), n, g32.data_ptr())
     return list(tensors)
+
+
+def _stored_grads(ctx, grads, go):
+    """backward of a loss whose forward left every gradient in memory: hand them out, scaled by the upstream gradient `go`
+    of the loss unless that is the unit tensor (`loss.backward(unit_grad(device))`, train.train_step: nothing to scale)"""
+    return grads if is_unit_grad(go) else scale_by_loss_grad_(ctx, grads, go)
 
 
 class _DecoderLoss(torch.autograd.Function):
@@ -1009,10 +963,7 @@ class _DecoderLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, go, _go_logits):
         gp, gq, g_cv, g_w2, g_b2, g_w3, g_b3 = ctx.saved_tensors
-        if is_unit_grad(go):         # `loss.backward(unit_grad(device))` (train.train_step): nothing to scale
-            return (gp, gq if ctx.has_q else None, None, None, g_cv if ctx.has_cv else None,
-                    g_w2, g_b2, g_w3, g_b3, None, None, None, None, None)
-        gp, gq, g_cv, g_w2, g_b2, g_w3, g_b3 = scale_by_loss_grad_(
+        gp, gq, g_cv, g_w2, g_b2, g_w3, g_b3 = _stored_grads(
             ctx, [gp, gq if ctx.has_q else None, g_cv if ctx.has_cv else None, g_w2, g_b2, g_w3, g_b3], go)
         return (gp, gq, None, None, g_cv, g_w2, g_b2, g_w3, g_b3, None, None, None, None, None)
 
@@ -1026,8 +977,7 @@ def decoder_loss_pq(pq, st, extra, cvec, w2, b2, w3, b3, y, pos_weight, denom, l
     the loss is their mean and the padding contributes to no gradient"""
     _lib.require_device(pq, extra, cvec, w2, b2, w3, b3, y, pos_weight, live)
     if _via_ops(st, _timed_decoder()) and DECODER_PRECISION == 1 and pq.shape[1] // 2 not in DECODER_ND_WIDTHS:
-        from . import torch_ops
-        return torch_ops.decoder_loss_pq(pq, st, extra, cvec, w2, b2, w3, b3, y, pos_weight, denom, live)
+        return _torch_ops().decoder_loss_pq(pq, st, extra, cvec, w2, b2, w3, b3, y, pos_weight, denom, live)
     return _DecoderLoss.apply(pq, None, st, extra, cvec, w2, b2, w3, b3, y, pos_weight, denom, True, live)
 
 
@@ -1063,28 +1013,22 @@ class _DecoderLossZ(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z, w_pq, b_pq, in_act, st: EdgeStructure, extra, cvec, w2, b2, w3, b3, y, pos_weight, denom):
-        lib = _lib.load()
         _lib.require_device(z, w_pq, b_pq, extra, cvec, w2, b2, w3, b3, y, pos_weight)
         z, w_pq, b_pq = _rows_f32(z), _f32c(w_pq), _f32c(b_pq)
         n, dev = z.shape[0], z.device
         pq = torch.empty(n, 128, dtype=torch.float32, device=dev)
-        with _lib.device_guard(dev):
-            _lib.check(lib.pangnn_linear_act_fwd_mixed(z.data_ptr(), 0, z.stride(0), w_pq.data_ptr(), b_pq.data_ptr(),
-                                                       pq.data_ptr(), 0, pq.stride(0), n, 64, 128, int(in_act), None, 0, 0,
-                                                       _lib.stream_ptr()), "pangnn_linear_act_fwd_mixed")
+        _launch(dev, "pangnn_linear_act_fwd_mixed", z.data_ptr(), 0, z.stride(0), w_pq.data_ptr(), b_pq.data_ptr(),
+                pq.data_ptr(), 0, pq.stride(0), n, 64, 128, int(in_act), None, 0, 0)
         p, q, ex, cv, w2, b2, w3, b3, y, pw = _decoder_operands(pq, None, extra, cvec, w2, b2, w3, b3, y, pos_weight)
         loss, logits, (plan_s, parts_s), (plan_t, parts_t), g_cv, g_w2, g_b2, g_w3, g_b3 = _decoder_train16(
             p, q, st, ex, cv, w2, b2, w3, b3, y=y, pw=pw, denom=denom, raw_parts=True)
         g_z = torch.empty(n, 64, dtype=torch.float32, device=dev)
         g_wpq, g_bpq = torch.empty_like(w_pq), torch.empty_like(b_pq)
-        with _lib.device_guard(dev):
-            ws_bytes = lib.pangnn_linear_wgrad_workspace_bytes(64, 128)
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            _lib.check(lib.pangnn_linear_act_backward_parts_f32(
+        ws, ws_bytes = _workspace(dev, "pangnn_linear_wgrad", 64, 128)
+        _launch(dev, "pangnn_linear_act_backward_parts_f32",
                 parts_s.data_ptr(), plan_s.part_rowptr.data_ptr(), parts_s.shape[0], parts_t.data_ptr(),
                 plan_t.part_rowptr.data_ptr(), parts_t.shape[0], z.data_ptr(), z.stride(0), w_pq.data_ptr(), n, 64, 128,
-                int(in_act), g_z.data_ptr(), g_z.stride(0), g_wpq.data_ptr(), g_bpq.data_ptr(), ws.data_ptr(), ws_bytes,
-                _lib.stream_ptr()), "pangnn_linear_act_backward_parts_f32")
+                int(in_act), g_z.data_ptr(), g_z.stride(0), g_wpq.data_ptr(), g_bpq.data_ptr(), ws.data_ptr(), ws_bytes)
         ctx.has_cv = g_cv is not None
         ctx.save_for_backward(g_z, g_wpq, g_bpq, g_cv if g_cv is not None else g_z.new_empty(0), g_w2, g_b2, g_w3, g_b3)
         ctx.mark_non_differentiable(logits)
@@ -1095,9 +1039,7 @@ class _DecoderLossZ(torch.autograd.Function):
         g = list(ctx.saved_tensors)
         if not ctx.has_cv:
             g[3] = None
-        if not is_unit_grad(go):         # `loss.backward(unit_grad(device))` (train.train_step): nothing to scale
-            g = scale_by_loss_grad_(ctx, g, go)
-        g_z, g_wpq, g_bpq, g_cv, g_w2, g_b2, g_w3, g_b3 = g
+        g_z, g_wpq, g_bpq, g_cv, g_w2, g_b2, g_w3, g_b3 = _stored_grads(ctx, g, go)
         return (g_z, g_wpq, g_bpq, None, None, None, g_cv, g_w2, g_b2, g_w3, g_b3, None, None, None)
 
 
@@ -1106,8 +1048,7 @@ def decoder_loss_z(z, w_pq, b_pq, in_act, st, extra, cvec, w2, b2, w3, b3, y, po
     fused_pq_backward_applies"""
     _lib.require_device(z, w_pq, b_pq, extra, cvec, w2, b2, w3, b3, y, pos_weight)
     if _via_ops(st, _timed_decoder()):
-        from . import torch_ops
-        return torch_ops.decoder_loss_z(z, w_pq, b_pq, in_act, st, extra, cvec, w2, b2, w3, b3, y, pos_weight, denom)
+        return _torch_ops().decoder_loss_z(z, w_pq, b_pq, in_act, st, extra, cvec, w2, b2, w3, b3, y, pos_weight, denom)
     return _DecoderLossZ.apply(z, w_pq, b_pq, int(in_act), st, extra, cvec, w2, b2, w3, b3, y, pos_weight, denom)
 
 
@@ -1126,8 +1067,7 @@ def edge_score(z, st: EdgeStructure, mode: str):
     m = SCORE_MODES[mode]
     _whole_graph("edge_score", st)
     _lib.require_device(z)
-    from . import torch_ops
-    return torch_ops.edge_score(z, st, m)                # the only route: pangnn::edge_score (csrc/graph_ops.cpp)
+    return _torch_ops().edge_score(z, st, m)             # the only route: pangnn::edge_score (csrc/graph_ops.cpp)
 
 
 def edge_score_loss(z, st: EdgeStructure, mode: str, y, pos_weight=None, denom=None):
@@ -1136,8 +1076,7 @@ def edge_score_loss(z, st: EdgeStructure, mode: str, y, pos_weight=None, denom=N
     _whole_graph("edge_score_loss", st)
     _lib.require_device(z, y, pos_weight)
     denom = st.num_edges if denom is None else denom
-    from . import torch_ops
-    return torch_ops.edge_score_loss(z, st, m, y, pos_weight, denom)     # the only route: pangnn::edge_score_loss
+    return _torch_ops().edge_score_loss(z, st, m, y, pos_weight, denom)  # the only route: pangnn::edge_score_loss
 
 
 @torch.compiler.assume_constant_result
@@ -1161,8 +1100,7 @@ def linear(x, w, bias=None, in_act: int = 0, out_dtype=None):
             and not (x.dtype in ROWS16 and out_dtype in ROWS16 and x.dtype != out_dtype):
         # ONE route (round 4): the dispatcher op, whose HIP implementation and autograd formula are C++
         # (csrc/torch_ops.cpp) — the ctypes autograd.Function twin of rounds 1-3 is gone
-        from . import torch_ops
-        return torch_ops.ops.linear(x, w, bias, int(in_act), dtype_code(out_dtype))
+        return _torch_ops().ops.linear(x, w, bias, int(in_act), dtype_code(out_dtype))
     if in_act:
         x = torch.nn.functional.elu(x)
     y = torch.nn.functional.linear(x.float(), w, bias)
@@ -1174,8 +1112,7 @@ def bce_with_logits(logits, y, pos_weight=None, denom=None):
     edge count), loss and dL/dlogits from one pass: pangnn::bce_with_logits — implementation and autograd formula in C++
     (csrc/torch_ops.cpp), the only route"""
     _lib.require_device(logits, y, pos_weight)
-    from . import torch_ops
-    return torch_ops.ops.bce_with_logits(logits, y, pos_weight, int(logits.shape[0] if denom is None else denom))[0]
+    return _torch_ops().ops.bce_with_logits(logits, y, pos_weight, int(logits.shape[0] if denom is None else denom))[0]
 
 
 
@@ -1189,15 +1126,12 @@ def _node_actions(x_tab, st, norm):
     if key not in cache:
         # ONE launch (pangnn_node_actions_f32: a wave per row of the by-target CSR) — a fresh mini-batch pays this every step
         # (rounds 2-4: the generic propagate on a 16-column table (x, 1, 0, ...): table build + propagate + a transposing copy)
-        lib = _lib.load()
         xv = xv.contiguous()
         rs = torch.empty(2, st.num_nodes, dtype=torch.float32, device=xv.device)
         csr, val = st.by_dst, norm.by_dst
         _lib.require_device(xv, csr.rowptr, val)
-        with _lib.device_guard(xv.device):
-            _lib.check(lib.pangnn_node_actions_f32(csr.rowptr.data_ptr(), _lib.ptr(csr.other), _lib.ptr(val), xv.data_ptr(),
-                                                   st.num_nodes, rs[0].data_ptr(), rs[1].data_ptr(), _lib.stream_ptr()),
-                       "pangnn_node_actions_f32")
+        _launch(xv.device, "pangnn_node_actions_f32", csr.rowptr.data_ptr(), _lib.ptr(csr.other), _lib.ptr(val), xv.data_ptr(),
+                st.num_nodes, rs[0].data_ptr(), rs[1].data_ptr())
         cache.clear()
         cache[key] = (rs[0], rs[1], x_tab)                                   # x_tab kept alive: key is its address
     r, s, _ = cache[key]
@@ -1227,25 +1161,20 @@ class _EmbedPropagate(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        lib = _lib.load()
         r, s = ctx.saved_tensors
         g = _rows_f32(g)
         n, f = g.shape
         out = torch.empty(2, f, dtype=torch.float32, device=g.device)
-        with _lib.device_guard(g.device):
-            ws_bytes = lib.pangnn_weighted_colsum_workspace_bytes(f)
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=g.device)
-            _lib.check(lib.pangnn_weighted_colsum_f32(g.data_ptr(), g.stride(0), r.data_ptr(), s.data_ptr(), n, f,
-                                                      out.data_ptr(), ws.data_ptr(), ws_bytes, _lib.stream_ptr()),
-                       "pangnn_weighted_colsum_f32")
+        ws, ws_bytes = _workspace(g.device, "pangnn_weighted_colsum", f)
+        _launch(g.device, "pangnn_weighted_colsum_f32", g.data_ptr(), g.stride(0), r.data_ptr(), s.data_ptr(), n, f,
+                out.data_ptr(), ws.data_ptr(), ws_bytes)
         return None, out[0].reshape(ctx.d, 1), out[1], None, None, None
 
 
 def embed_propagate(x_tab, w, b, st, norm, tag=None):
     _lib.require_device(x_tab, w, b)
-    if _via_ops(st, tag) and getattr(norm, "weight_ref", norm) is not norm:
-        from . import torch_ops
-        return torch_ops.embed_propagate(x_tab, w, b, st, norm)
+    if _op_route(st, norm, tag):
+        return _torch_ops().embed_propagate(x_tab, w, b, st, norm)
     return _EmbedPropagate.apply(x_tab, w, b, st, norm, tag)
 
 
@@ -1265,25 +1194,21 @@ class _EmbedConvIn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x_tab, w, b, w_in, b_in, st, norm, out_dtype):
-        lib = _lib.load()
         _lib.require_device(x_tab, w, b, w_in, b_in)
         r, s = _node_actions(x_tab, st, norm)
         wv, bv, win = _f32c(w.detach().reshape(-1)), _f32c(b.detach().reshape(-1)), _f32c(w_in.detach())
         n, h, d = st.num_nodes, win.shape[0], win.shape[1]
         bias = None if b_in is None else _f32c(b_in.detach())
         out = torch.empty(n, h, dtype=out_dtype or torch.float32, device=r.device)
-        with _lib.device_guard(r.device):
-            # a = W w and c = W b are formed inside the kernel: the whole layer is this one launch
-            _lib.check(lib.pangnn_embed_conv_in_rows(r.data_ptr(), s.data_ptr(), wv.data_ptr(), bv.data_ptr(), win.data_ptr(),
-                                                     _lib.ptr(bias), d, out.data_ptr(), _dt(out), out.stride(0), n, h,
-                                                     _lib.stream_ptr()), "pangnn_embed_conv_in_rows")
+        # a = W w and c = W b are formed inside the kernel: the whole layer is this one launch
+        _launch(r.device, "pangnn_embed_conv_in_rows", r.data_ptr(), s.data_ptr(), wv.data_ptr(), bv.data_ptr(), win.data_ptr(),
+                _lib.ptr(bias), d, out.data_ptr(), _dt(out), out.stride(0), n, h)
         ctx.save_for_backward(r, s, wv, bv, win)
         ctx.has_bias = b_in is not None
         return out
 
     @staticmethod
     def backward(ctx, g):
-        lib = _lib.load()
         r, s, wv, bv, win = ctx.saved_tensors
         g = _rows_any(g)
         n, h = g.shape
@@ -1292,21 +1217,17 @@ class _EmbedConvIn(torch.autograd.Function):
         g_w, g_b = torch.empty(d, 1, dtype=torch.float32, device=dev), torch.empty(d, dtype=torch.float32, device=dev)
         g_win = torch.empty(h, d, dtype=torch.float32, device=dev)
         g_bin = torch.empty(h, dtype=torch.float32, device=dev) if ctx.has_bias else None
-        with _lib.device_guard(dev):
-            ws_bytes = lib.pangnn_embed_conv_in_grads_workspace_bytes(h)
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            _lib.check(lib.pangnn_embed_conv_in_grads(g.data_ptr(), _dt(g), g.stride(0), r.data_ptr(), s.data_ptr(), n,
-                                                      wv.data_ptr(), bv.data_ptr(), win.data_ptr(), d, h, g_w.data_ptr(),
-                                                      g_b.data_ptr(), g_win.data_ptr(), _lib.ptr(g_bin), ws.data_ptr(), ws_bytes,
-                                                      _lib.stream_ptr()), "pangnn_embed_conv_in_grads")
+        ws, ws_bytes = _workspace(dev, "pangnn_embed_conv_in_grads", h)
+        _launch(dev, "pangnn_embed_conv_in_grads", g.data_ptr(), _dt(g), g.stride(0), r.data_ptr(), s.data_ptr(), n,
+                wv.data_ptr(), bv.data_ptr(), win.data_ptr(), d, h, g_w.data_ptr(), g_b.data_ptr(), g_win.data_ptr(),
+                _lib.ptr(g_bin), ws.data_ptr(), ws_bytes)
         return None, g_w, g_b, g_win, g_bin, None, None, None
 
 
 def embed_conv_in(x_tab, w, b, w_in, b_in, st, norm, out_dtype=None):
     _lib.require_device(x_tab, w, b, w_in, b_in)
-    if _via_ops(st) and getattr(norm, "weight_ref", norm) is not norm and (out_dtype in (None, torch.float32) or out_dtype in ROWS16):
-        from . import torch_ops
-        return torch_ops.embed_conv_in(x_tab, w, b, w_in, b_in, st, norm, out_dtype)
+    if _op_route(st, norm) and (out_dtype in (None, torch.float32) or out_dtype in ROWS16):
+        return _torch_ops().embed_conv_in(x_tab, w, b, w_in, b_in, st, norm, out_dtype)
     return _EmbedConvIn.apply(x_tab, w, b, w_in, b_in, st, norm, out_dtype)
 
 
@@ -1321,7 +1242,6 @@ class _EmbedConvInLinear(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x_tab, w, b, w_in, b_in, w_out, bias_out, st, norm):
-        lib = _lib.load()
         _lib.require_device(x_tab, w, b, w_in, b_in, w_out, bias_out)
         r, s = _node_actions(x_tab, st, norm)
         wv, bv, win = _f32c(w.detach().reshape(-1)), _f32c(b.detach().reshape(-1)), _f32c(w_in.detach())
@@ -1329,20 +1249,17 @@ class _EmbedConvInLinear(torch.autograd.Function):
         wout = _f32c(w_out.detach())
         bout = None if bias_out is None else _f32c(bias_out.detach())
         n, h, d, m = st.num_nodes, win.shape[0], win.shape[1], wout.shape[0]
-        if wout.shape[1] != h or not lib.pangnn_embed_linear_supported(h, m):
+        if wout.shape[1] != h or not embed_linear_supported(h, m):
             raise ValueError(f"embed_conv_in_linear: unsupported widths H={h}, M={m}")
         y = torch.empty(n, m, dtype=torch.float32, device=r.device)
-        with _lib.device_guard(r.device):
-            _lib.check(lib.pangnn_embed_linear_fwd(r.data_ptr(), s.data_ptr(), n, wv.data_ptr(), bv.data_ptr(), win.data_ptr(),
-                                                   _lib.ptr(bin_), d, h, wout.data_ptr(), _lib.ptr(bout), m, y.data_ptr(),
-                                                   y.stride(0), _lib.stream_ptr()), "pangnn_embed_linear_fwd")
+        _launch(r.device, "pangnn_embed_linear_fwd", r.data_ptr(), s.data_ptr(), n, wv.data_ptr(), bv.data_ptr(),
+                win.data_ptr(), _lib.ptr(bin_), d, h, wout.data_ptr(), _lib.ptr(bout), m, y.data_ptr(), y.stride(0))
         ctx.save_for_backward(r, s, wv, bv, win, wout, bin_ if bin_ is not None else wv.new_empty(0))
         ctx.has_bin, ctx.has_bout = b_in is not None, bias_out is not None
         return y
 
     @staticmethod
     def backward(ctx, g):
-        lib = _lib.load()
         r, s, wv, bv, win, wout, bin_ = ctx.saved_tensors
         bin_ = bin_ if ctx.has_bin else None
         g = _rows_f32(g)
@@ -1358,18 +1275,12 @@ class _EmbedConvInLinear(torch.autograd.Function):
         g_b, o = out[o:o + d], o + d
         g_win, o = out[o:o + h * d].view(h, d), o + h * d
         g_bin = out[o:o + h]
-        with _lib.device_guard(dev):
-            ws_bytes = lib.pangnn_embed_linear_bwd_workspace_bytes(h, m)
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            _lib.check(lib.pangnn_embed_linear_bwd(g.data_ptr(), g.stride(0), r.data_ptr(), s.data_ptr(), n, wv.data_ptr(),
-                                                   bv.data_ptr(), win.data_ptr(), _lib.ptr(bin_), d, h, wout.data_ptr(), m,
-                                                   g_wout.data_ptr(), g_bout.data_ptr() if ctx.has_bout else None,
-                                                   sums.data_ptr(), ws.data_ptr(), ws_bytes, _lib.stream_ptr()),
-                       "pangnn_embed_linear_bwd")
-            _lib.check(lib.pangnn_embed_conv_in_grads_from_sums(sums.data_ptr(), wv.data_ptr(), bv.data_ptr(), win.data_ptr(),
-                                                                d, h, g_w.data_ptr(), g_b.data_ptr(), g_win.data_ptr(),
-                                                                g_bin.data_ptr() if ctx.has_bin else None,
-                                                                _lib.stream_ptr()), "pangnn_embed_conv_in_grads_from_sums")
+        ws, ws_bytes = _workspace(dev, "pangnn_embed_linear_bwd", h, m)
+        _launch(dev, "pangnn_embed_linear_bwd", g.data_ptr(), g.stride(0), r.data_ptr(), s.data_ptr(), n, wv.data_ptr(),
+                bv.data_ptr(), win.data_ptr(), _lib.ptr(bin_), d, h, wout.data_ptr(), m, g_wout.data_ptr(),
+                g_bout.data_ptr() if ctx.has_bout else None, sums.data_ptr(), ws.data_ptr(), ws_bytes)
+        _launch(dev, "pangnn_embed_conv_in_grads_from_sums", sums.data_ptr(), wv.data_ptr(), bv.data_ptr(), win.data_ptr(),
+                d, h, g_w.data_ptr(), g_b.data_ptr(), g_win.data_ptr(), g_bin.data_ptr() if ctx.has_bin else None)
         return (None, g_w, g_b, g_win, g_bin if ctx.has_bin else None, g_wout, g_bout if ctx.has_bout else None, None, None)
 
 
@@ -1380,9 +1291,8 @@ def embed_linear_supported(h: int, m: int) -> bool:
 
 def embed_conv_in_linear(x_tab, w, b, w_in, b_in, w_out, bias_out, st, norm):
     _lib.require_device(x_tab, w, b, w_in, b_in, w_out, bias_out)
-    if _via_ops(st) and getattr(norm, "weight_ref", norm) is not norm:
-        from . import torch_ops
-        return torch_ops.embed_conv_in_linear(x_tab, w, b, w_in, b_in, w_out, bias_out, st, norm)
+    if _op_route(st, norm):
+        return _torch_ops().embed_conv_in_linear(x_tab, w, b, w_in, b_in, w_out, bias_out, st, norm)
     return _EmbedConvInLinear.apply(x_tab, w, b, w_in, b_in, w_out, bias_out, st, norm)
 
 
@@ -1400,14 +1310,11 @@ class _PQOperands(torch.autograd.Function):
         if w.is_cuda and not observed() and w.dtype == torch.float32 and b.dtype == torch.float32 and w.dim() == 2 \
                 and w.stride(1) == 1 and b.is_contiguous() and w.shape[1] >= 2 * d + int(bool(skip)):
             # one launch (a fresh or replayed mini-batch step is made of launches: cat + pad + copy were three)
-            lib = _lib.load()
             out = torch.empty(2 * d * d + 2 * d + (d if skip else 0), dtype=torch.float32, device=w.device)
             w_pq, b_pq = out[:2 * d * d].view(2 * d, d), out[2 * d * d:2 * d * d + 2 * d]
             cvec = out[2 * d * d + 2 * d:] if skip else None
-            with _lib.device_guard(w.device):
-                _lib.check(lib.pangnn_pq_operands_f32(w.data_ptr(), w.stride(0), b.data_ptr(), d, int(bool(skip)),
-                                                      w_pq.data_ptr(), b_pq.data_ptr(), _lib.ptr(cvec), _lib.stream_ptr()),
-                           "pangnn_pq_operands_f32")
+            _launch(w.device, "pangnn_pq_operands_f32", w.data_ptr(), w.stride(0), b.data_ptr(), d, int(bool(skip)),
+                    w_pq.data_ptr(), b_pq.data_ptr(), _lib.ptr(cvec))
             return w_pq, b_pq, cvec
         w_pq = torch.cat([w[:, :d], w[:, d:2 * d]], dim=0)
         b_pq = torch.nn.functional.pad(b, (d, 0))
