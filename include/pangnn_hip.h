@@ -31,7 +31,8 @@ extern "C" {
  * weight gradient is covered (pangnn_linear_supported(128, 128, 1) = 1). */
 /* 3, extended: pangnn_linear_act_backward_parts_f32 added.  No entry point changed its signature or meaning, so the number
  * stays; the binding resolves every symbol at load, which refuses an older library of the same number.
- * Likewise pangnn_edge_dot_mixed, pangnn_gcn_norm_bwd_f32 and its _workspace_bytes (dL/d(edge_weight) of GCNConv). */
+ * Likewise pangnn_edge_dot_mixed, pangnn_gcn_norm_bwd_f32 and its _workspace_bytes (dL/d(edge_weight) of GCNConv), and
+ * pangnn_qscore_fwd / pangnn_qscore_bwd with PANGNN_DTYPE_F64 (the differentiable Q-score edge weights). */
 #define PANGNN_ABI_VERSION 3
 
 #define PANGNN_E_BADARG    (-1)  /* null pointer / negative size / unsupported feature width */
@@ -45,6 +46,7 @@ extern "C" {
 #define PANGNN_DTYPE_F16  2   /* IEEE half rows (--mixed_precision fp16): accepted wherever a *_dtype argument accepts _BF16
                                * (dense layers, propagate gathers, generated rows, column sums, the decoder's P | Q tables); the
                                * 2-byte operands of one call are all bfloat16 or all float16. */
+#define PANGNN_DTYPE_F64  3   /* float64 as stored: the *_dtype arguments of pangnn_qscore_fwd / pangnn_qscore_bwd only */
 
 typedef void* pangnn_stream_t;   /* hipStream_t */
 
@@ -846,6 +848,42 @@ int    pangnn_gcn_norm_bwd_f32(const int64_t* edge_index, int64_t ld, int64_t nu
                                const int64_t* seg_ptr_src, const int64_t* parts_rowptr_src, int64_t num_seg_src,
                                const float* w, const float* gw, const float* dis, float* gweight, void* workspace,
                                int64_t workspace_bytes, pangnn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The Q-score edge weights of normalize_sim_scores (src/preprocessing.py:454-548) as a differentiable function of the bit
+ * scores and of the softmax temperature (csrc/qscore.hip; pangnn_amd/weights.py).  A segment plan describes the (source
+ * gene, candidate genome) groups over the graph's OWN edge list: rowptr int64 [num_segments + 1] (starts at 0, ends at
+ * num_edges, no empty segment) and item int32 [num_edges], the edge id at every position of the segment order.  Scores are
+ * read and weights / gradients written at item[pos]: every per-edge array is in the caller's edge order.  score is float32
+ * or float64 as stored (score_dtype = PANGNN_DTYPE_F32 / _F64; any other code: PANGNN_E_BADARG); all arithmetic is float64.
+ * t [1] is a DEVICE double (a parameter's value: never read on the host); 0 < epsilon < 0.5.
+ *
+ * pangnn_qscore_fwd: per segment x_i = score_i / t, lse = log sum_j exp(x_j - max_j x_j) + max_j x_j, p_i = exp(x_i - lse),
+ *   weight_i = -10 log10(clip(1 - p_i, epsilon, 1 - epsilon)) + pseudo_count    (one candidate: p = 1; a NaN p: 1 - epsilon
+ *   in place of the clip, the reference's nan_to_num), written as float32 or float64 (weight_dtype); lse [2 * num_segments]
+ * is kept for the backward: lse of every segment, then r, what the last addition rounded away (log sum + max = lse + r
+ * exactly).  The operations and their order (lanes stride the segment, xor-shuffle tree) are those of
+ * pangnn_softmax_qscore_f64: float64 weights have its bits.
+ *
+ * pangnn_qscore_bwd: with g [num_edges] = dL/dweight (float32 or float64, g_dtype), c_i = 1 - p_i,
+ *   a_i = g_i (10 / ln 10) / c_i where epsilon <= c_i <= 1 - epsilon, else 0          (torch.clamp's inclusive mask)
+ *   S = sum_j p_j a_j,  gx_i = p_i ((a_i - S) + S r),  gscore_i = gx_i / t,  gt[0] = sum over segments of -(sum_i gx_i score_i) / t^2
+ * (S (1 - r): S times the probability of the unrounded lse, as autograd's chain through lse = log sum + max has it; the two
+ * terms cancel down to c_i of their size, so r matters where c_i is near epsilon).
+ * gscore [num_edges] has the type of score; a one-candidate segment gives zeros.  Either output may be NULL and is then not
+ * computed.  t_parts: float64 [num_segments + PANGNN_QSCORE_SUM_PARTS] scratch (needed with gt): the segments' shares of
+ * dL/dt, then their block sums, added in an order that num_segments alone fixes.  No float atomics: two calls give the same
+ * bits.  Non-finite scores are not special-cased: a NaN score makes its segment's gscore and gt NaN, as the formula does.
+ * One wave per segment (segments are bounded by the genes of one genome; any length is correct).  num_edges == 0 launches
+ * nothing; num_edges or num_segments >= 2^31: PANGNN_E_TOOLARGE.
+ * ---------------------------------------------------------------------------------------- */
+#define PANGNN_QSCORE_SUM_PARTS 1024
+int    pangnn_qscore_fwd(const int64_t* rowptr, const int32_t* item, const void* score, int32_t score_dtype,
+                         int64_t num_segments, int64_t num_edges, const double* t, double epsilon, double pseudo_count,
+                         void* weight, int32_t weight_dtype, double* lse, pangnn_stream_t stream);
+int    pangnn_qscore_bwd(const int64_t* rowptr, const int32_t* item, const void* score, int32_t score_dtype, const void* g,
+                         int32_t g_dtype, const double* lse, int64_t num_segments, int64_t num_edges, const double* t,
+                         double epsilon, void* gscore, double* gt, double* t_parts, pangnn_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -15,7 +15,9 @@ from .gnn import AlternateGCN                                 # noqa: E402
 from .graph import EdgeStructure, structure_of                # noqa: E402
 from .predict import predict_homolog_genes                    # noqa: E402
 from .sampling import filter_edges, sub_sample_graph_edges     # noqa: E402
+from .weights import QScoreWeights, ScoreSegments, qscore_weights, score_segments   # noqa: E402
 
 __all__ = ["AlternateGCN", "GCNConv", "MessagePassing", "EdgeConv", "Data", "Batch", "DataLoader",
            "EdgeStructure", "structure_of", "BCEWithLogitsLoss", "DeferredLogits",
-           "predict_homolog_genes", "filter_edges", "sub_sample_graph_edges"]
+           "predict_homolog_genes", "filter_edges", "sub_sample_graph_edges",
+           "QScoreWeights", "ScoreSegments", "qscore_weights", "score_segments"]

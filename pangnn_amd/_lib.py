@@ -170,6 +170,11 @@ SIGNATURES = {
     "pangnn_gcn_norm_bwd_workspace_bytes": (_i64, [_i64, _i64, _i64]),
     "pangnn_gcn_norm_bwd_f32": (C.c_int, [_p, _i64, _i64, _i64, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _p, _i64,
                                           _p, _p, _p, _p, _p, _i64, _p]),
+    # differentiable Q-score edge weights (csrc/qscore.hip): (rowptr, item, score, score_dtype, num_segments, num_edges, t,
+    # epsilon, pseudo_count, weight, weight_dtype, lse, stream)
+    "pangnn_qscore_fwd": (C.c_int, [_p, _p, _p, _i32, _i64, _i64, _p, C.c_double, C.c_double, _p, _i32, _p, _p]),
+    # (rowptr, item, score, score_dtype, g, g_dtype, lse, num_segments, num_edges, t, epsilon, gscore, gt, t_parts, stream)
+    "pangnn_qscore_bwd": (C.c_int, [_p, _p, _p, _i32, _p, _i32, _p, _i64, _i64, _p, C.c_double, _p, _p, _p, _p]),
 }
 
 ABI_VERSION = 3          # PANGNN_ABI_VERSION of include/pangnn_hip.h this binding was written against

@@ -91,19 +91,28 @@ def neighbour_edges(num_nodes: int, neighbours: int = 1, device=None) -> torch.T
     return torch.stack([i[keep], j[keep]])
 
 
+def _graph_edges(num_nodes: int, src, dst, value):
+    """the relation's entries that become edges (no self loops, ids in [0, N): preprocessing.py:98-109), canonical order"""
+    ok = (src != dst) & (src >= 0) & (dst >= 0) & (src < num_nodes) & (dst < num_nodes)
+    s, d, v = src[ok], dst[ok], value[ok]
+    o = canonical_order(s, d, num_nodes)
+    return s[o], d[o], v[o]
+
+
 def whole_graph(num_nodes: int, src, dst, weight, group_of: Optional[torch.Tensor], neighbours: int = 1,
-                pair_src=None, pair_dst=None):
+                pair_src=None, pair_dst=None, keep_raw: bool = False, raw=None, genome_of=None):
     """dataset.py:325-384: one Data-like object for the whole graph.
 
     (src, dst, weight): normalised relation.  Self loops and ids outside [0, N) are skipped
     (preprocessing.py:98-109).  Labels: 1 iff the two genes are in the same ortholog group —
     given either as `group_of[node]` or as explicit directed pairs (pair_src, pair_dst) which are
-    matched in both directions (preprocessing.py:145-148)."""
+    matched in both directions (preprocessing.py:145-148).
+
+    keep_raw: the object also carries `raw_score` — the bit score of every edge, in the graph's edge order, dtype as
+    given — and `genome_of`, the inputs of pangnn_amd.weights (a learnable normalisation of the same scores).  `raw` is the
+    relation (src, dst, score) that was normalised: one score per ordered pair, any order."""
     dev = src.device
-    ok = (src != dst) & (src >= 0) & (dst >= 0) & (src < num_nodes) & (dst < num_nodes)
-    s, d, w = src[ok], dst[ok], weight[ok]
-    o = canonical_order(s, d, num_nodes)
-    s, d, w = s[o], d[o], w[o]
+    s, d, w = _graph_edges(num_nodes, src, dst, weight)
     if group_of is not None:
         gs, gd = group_of[s], group_of[d]
         y = ((gs == gd) & (gs >= 0)).to(torch.float32)
@@ -112,7 +121,7 @@ def whole_graph(num_nodes: int, src, dst, weight, group_of: Optional[torch.Tenso
         e = s * num_nodes + d
         pos = torch.searchsorted(k, e).clamp_(max=max(k.numel() - 1, 0))
         y = (k[pos] == e).to(torch.float32) if k.numel() else torch.zeros_like(e, dtype=torch.float32)
-    return SimpleNamespace(
+    g = SimpleNamespace(
         x=torch.ones(num_nodes, 1, dtype=torch.float32, device=dev),
         edge_index=torch.stack([s, d]),
         edge_attr=w.to(torch.float32),
@@ -120,14 +129,24 @@ def whole_graph(num_nodes: int, src, dst, weight, group_of: Optional[torch.Tenso
         neighbour_edge_index=neighbour_edges(num_nodes, neighbours, dev),
         num_nodes=num_nodes,
     )
+    if keep_raw:
+        if raw is None or genome_of is None:
+            raise ValueError("whole_graph: keep_raw needs `raw` = (src, dst, score) and `genome_of`")
+        rs, rd, rsc = _graph_edges(num_nodes, *raw)
+        if not (torch.equal(rs, s) and torch.equal(rd, d)):
+            raise ValueError("whole_graph: `raw` does not hold exactly the normalised relation's pairs")
+        g.raw_score, g.genome_of = rsc.contiguous(), genome_of
+    return g
 
 
 def build_from_raw(num_nodes, raw_src, raw_dst, raw_score, genome_of, group_of=None, pair_src=None,
-                   pair_dst=None, neighbours: int = 1, t: float = 0.8, include_trivial: bool = False):
+                   pair_dst=None, neighbours: int = 1, t: float = 0.8, include_trivial: bool = False,
+                   keep_raw: bool = False):
     """raw relation -> remove_trivial_cases -> normalize_sim_scores -> whole-graph tensors
-    (dataset.py:70,103,111-112 then generate_graphs)."""
+    (dataset.py:70,103,111-112 then generate_graphs).  keep_raw: see whole_graph."""
     s, d, sc = raw_src, raw_dst, raw_score
     if not include_trivial:
         s, d, sc = remove_trivial_cases(s, d, sc, genome_of)
+    raw = (s, d, sc) if keep_raw else None
     s, d, w = normalize_sim_scores(s, d, sc, genome_of, t=t)
-    return whole_graph(num_nodes, s, d, w, group_of, neighbours, pair_src, pair_dst)
+    return whole_graph(num_nodes, s, d, w, group_of, neighbours, pair_src, pair_dst, keep_raw, raw, genome_of)

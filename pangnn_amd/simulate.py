@@ -218,15 +218,16 @@ def simulate_shard(n: int, genomes: int, frac_pos: float, num_fragments: float =
 
 def simulate_graph(n: int, genomes: int, frac_pos: float, num_fragments: float = 10, n_shuffle: float = 2,
                    neighbours: int = 1, seed: int = 0, device="cpu", temperature: float = 0.8, mean_neg=None,
-                   adjacent_only: bool = False):
+                   adjacent_only: bool = False, keep_raw: bool = False):
     """whole simulated graph as the reference's `generate_graphs()` would emit it (dataset.py:157-158):
-    x, edge_index (canonical order), edge_attr, y, neighbour_edge_index, class_balance."""
+    x, edge_index (canonical order), edge_attr, y, neighbour_edge_index, class_balance.  keep_raw: also `raw_score`, the
+    bit score of every edge (construct.whole_graph)."""
     # adjacent_only: skip the ortholog pairs of non-adjacent genomes — remove_trivial_cases drops every one of them
     # anyway (same graph), and at config-5 scale they are most of the raw relation
     raw = simulate_raw(n, genomes, frac_pos, num_fragments, n_shuffle, seed=seed, device=device, mean_neg=mean_neg,
                        blocks=list(range(int(genomes) - 1)) if adjacent_only else None)
     g = construct.build_from_raw(raw.num_nodes, raw.src, raw.dst, raw.score, raw.genome_of,
-                                 group_of=raw.group_of, neighbours=neighbours, t=temperature)
+                                 group_of=raw.group_of, neighbours=neighbours, t=temperature, keep_raw=keep_raw)
     pos = g.y.sum()
     g.class_balance = ((g.y == 0).sum() / pos.clamp_min(1)).to(torch.float32)      # dataset.py:346
     g.genome_of = raw.genome_of
