@@ -32,7 +32,8 @@ extern "C" {
 /* 3, extended: pangnn_linear_act_backward_parts_f32 added.  No entry point changed its signature or meaning, so the number
  * stays; the binding resolves every symbol at load, which refuses an older library of the same number.
  * Likewise pangnn_edge_dot_mixed, pangnn_gcn_norm_bwd_f32 and its _workspace_bytes (dL/d(edge_weight) of GCNConv), and
- * pangnn_qscore_fwd / pangnn_qscore_bwd with PANGNN_DTYPE_F64 (the differentiable Q-score edge weights). */
+ * pangnn_qscore_fwd / pangnn_qscore_bwd with PANGNN_DTYPE_F64 (the differentiable Q-score edge weights), and
+ * pangnn_csr_plan_tpos + pangnn_decoder_dgrad_stream_f32 (the T pass on one position word per edge). */
 #define PANGNN_ABI_VERSION 3
 
 #define PANGNN_E_BADARG    (-1)  /* null pointer / negative size / unsupported feature width */
@@ -365,7 +366,11 @@ int pangnn_decoder_nd_loss_f32(const float* p, int64_t ldp, const float* q, int6
  *   g_b2[D] (nullable) = dL/db2 = w3[j] sum_e g_e [h2[j][e] > 0] — ask for it in exactly one dgrad call per step.
  *   part_buf / part_off / keys may all be NULL to get the parameter sum alone.  workspace (with g_b2):
  *   pangnn_decoder_dgrad_workspace_bytes().
- * live_edges (both entry points; nullable, DEVICE int64[1]): the list is a fixed-shape batch whose first *live_edges edges
+ * pangnn_decoder_dgrad_stream_f32: the same pass and the same results, bit for bit, for an order given as ONE word per
+ *   position, tpos[k] = perm[k] | closes_k << 31 (pangnn_csr_plan_tpos below: built once per graph) in place of perm and
+ *   keys: one load per position instead of three, no per-step key compares.  tpos, part_buf and part_off are required
+ *   (num_edges > 0); every edge is real (no live_edges: a padded batch takes pangnn_decoder_dgrad_f32).
+ * live_edges (pangnn_decoder_train_* and pangnn_decoder_dgrad_f32; nullable, DEVICE int64[1]): the list is a fixed-shape batch whose first *live_edges edges
  *   are real and whose tail is padding (a mini-batch collated by pangnn_collate_subgraphs_padded so that one captured
  *   HIP graph serves every batch): in S the padded edges keep their own logit / record slots but enter every sum with
  *   dL/dlogit = 0 (the record itself keeps the unmasked value, see `rec`) and the fused loss is the mean over *live_edges
@@ -410,6 +415,9 @@ size_t pangnn_decoder_dgrad_workspace_bytes(void);
 int pangnn_decoder_dgrad_f32(const uint32_t* rec, const int32_t* perm, const int32_t* keys, const float* w2,
                              const float* w3, int64_t num_edges, float* part_buf, const int32_t* part_off, float* g_b2,
                              const int64_t* live_edges, void* workspace, size_t workspace_bytes, pangnn_stream_t stream);
+int pangnn_decoder_dgrad_stream_f32(const uint32_t* rec, const uint32_t* tpos, const float* w2, const float* w3,
+                                    int64_t num_edges, float* part_buf, const int32_t* part_off, float* g_b2,
+                                    void* workspace, int64_t workspace_bytes, pangnn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Node-level dense layers with a short inner dimension, K (in) and M (out) in {64, 128}
@@ -788,6 +796,12 @@ int64_t pangnn_csr_plan_workspace_bytes(int64_t n_rows);
 int    pangnn_csr_plan(const int64_t* rowptr, int64_t n_rows, int64_t num_edges, int32_t span, int32_t* keys,
                        int32_t* part_off, int64_t* part_rowptr, int64_t* last, void* workspace, int64_t workspace_bytes,
                        pangnn_stream_t stream);
+/* The position words of that order for pangnn_decoder_dgrad_stream_f32: perm [E] int32 (the order's edge ids, each in
+ * [0, 2^31)), keys [E] int32 as written by pangnn_csr_plan (non-decreasing), span as above ->
+ *   tpos [E] uint32   perm[p] | closes_p << 31,  closes_p = (p + 1 == E  ||  (p + 1) % span == 0  ||  keys[p + 1] != keys[p])
+ * i.e. bit 31 says that a part row ends behind position p.  One elementwise launch, plain stores; num_edges >= 1. */
+int    pangnn_csr_plan_tpos(const int32_t* perm, const int32_t* keys, int64_t num_edges, int32_t span, uint32_t* tpos,
+                            pangnn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * The mask of the k smallest keys (csrc/mask_select.hip): keep[i] = 0 for exactly the k entries that come first in

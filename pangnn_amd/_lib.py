@@ -121,6 +121,8 @@ SIGNATURES = {
     # T kernel: dL/dh1 run sums in a permuted (CSR) edge order from the records
     "pangnn_decoder_dgrad_workspace_bytes": (_sz, []),
     "pangnn_decoder_dgrad_f32": (C.c_int, [_p, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _p, _sz, _p]),
+    # (rec, tpos, w2, w3, num_edges, part_buf, part_off, g_b2, workspace, workspace_bytes, stream)
+    "pangnn_decoder_dgrad_stream_f32": (C.c_int, [_p, _p, _p, _p, _i64, _p, _p, _p, _p, _i64, _p]),
     # (host array of device pointers, host array of element counts, n_tensors, device scalar, stream)
     "pangnn_scale_unless_one_f32": (C.c_int, [_p, _p, _i32, _p, _p]),
     # weightless link decoders (csrc/edge_score.hip): (z, z_dtype, ldz, num_nodes, edge_index, ld, num_edges, d, mode, ...)
@@ -159,6 +161,8 @@ SIGNATURES = {
     # part_rowptr, last, workspace, bytes, stream)
     "pangnn_csr_plan_workspace_bytes": (_i64, [_i64]),
     "pangnn_csr_plan": (C.c_int, [_p, _i64, _i64, _i32, _p, _p, _p, _p, _p, _i64, _p]),
+    # the T pass's position words of that order: (perm, keys, num_edges, span, tpos, stream)
+    "pangnn_csr_plan_tpos": (C.c_int, [_p, _p, _i64, _i32, _p, _p]),
     # the mask of the k smallest keys (csrc/mask_select.hip): (keys, n, k, keep, workspace, bytes, stream)
     "pangnn_mask_k_smallest_workspace_bytes": (_i64, [_i64]),
     "pangnn_mask_k_smallest_i64": (C.c_int, [_p, _i64, _i64, _p, _p, _i64, _p]),

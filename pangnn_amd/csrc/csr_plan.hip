@@ -17,6 +17,11 @@
 // rows between are read once, coalesced, and each non-empty one marks its first entry in LDS; a max-scan of the marks is the
 // key of every entry.  A hub row costs its tiles two searches and no row reads, rows of one entry cost one rowptr read each:
 // E * 4 bytes written, n_rows * 8 + tiles * 2 * log2(n_rows) * 8 read.  Integer sums, plain stores to distinct addresses.
+//
+// pangnn_csr_plan_tpos: the position words of the T kernel's stream route (decoder16.hip) from that order's perm and the
+// keys above — tpos[p] = perm[p] | closes_p << 31, closes_p = [p + 1 == E  or  (p + 1) % span == 0  or  keys[p + 1] != keys[p]]:
+// the edge id at position p and "a part ends behind p", which the kernel otherwise re-derives from three loads per position in
+// every step.  One elementwise launch per graph, 4 bytes per edge kept.
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>
@@ -127,10 +132,38 @@ __global__ __launch_bounds__(kBlock) void csr_plan_kernel(
   }
 }
 
+__global__ __launch_bounds__(kBlock) void csr_plan_tpos_kernel(const int32_t* __restrict__ perm, const int32_t* __restrict__ keys,
+                                                              int64_t e, int64_t span, uint32_t* __restrict__ tpos) {
+  const int64_t nthreads = (int64_t)gridDim.x * kBlock;
+  for (int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x; p < e; p += nthreads) {
+    const int64_t q = p + 1;
+    const bool closes = q == e || q % span == 0 || keys[q] != keys[p];
+    tpos[p] = ((uint32_t)perm[p] & 0x7fffffffu) | (closes ? 0x80000000u : 0u);
+  }
+}
+
 }  // namespace
 }  // namespace pangnn
 
 using namespace pangnn;
+
+extern "C" int pangnn_csr_plan_tpos(const int32_t* perm, const int32_t* keys, int64_t num_edges, int32_t span, uint32_t* tpos,
+                                    pangnn_stream_t stream) {
+  const char* name = "pangnn_csr_plan_tpos";
+  const int64_t e = num_edges;
+  PG_CHECK_ARG(e >= 1, PANGNN_E_BADARG, "%s: bad size (E=%lld: at least one edge)", name, (long long)e);
+  PG_CHECK_ARG(e < ((int64_t)1 << 31) - 1, PANGNN_E_TOOLARGE, "%s: E must fit int32 (an edge id takes 31 bits of a word)", name);
+  PG_CHECK_ARG(span >= 32 && span % 32 == 0, PANGNN_E_BADARG, "%s: span %d is not a positive multiple of 32", name, (int)span);
+  PG_CHECK_ARG(perm && keys && tpos, PANGNN_E_BADARG, "%s: null pointer", name);
+  PG_CHECK_ARG((((uintptr_t)perm | (uintptr_t)keys | (uintptr_t)tpos) & 3u) == 0, PANGNN_E_ALIGN,
+               "%s: a pointer is not aligned to its element size", name);
+  int64_t blocks = (e + kBlock - 1) / kBlock;
+  if (blocks > kPlanMaxBlocks) blocks = kPlanMaxBlocks;
+  hipLaunchKernelGGL(csr_plan_tpos_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, perm, keys, e,
+                     (int64_t)span, tpos);
+  PG_CHECK_LAUNCH(name);
+  return 0;
+}
 
 // workspace layout: [Cin n_rows * 4][rocPRIM temp], each on 256 bytes
 extern "C" int64_t pangnn_csr_plan_workspace_bytes(int64_t n_rows) {

@@ -16,8 +16,8 @@
 //       P3  dL/dW2[j][k] = w3[j] sum_e m2[j][e] (g_e h1[e][k])        (A = m2 exact, B = g_e h1 split three
 //           ways: v_mfma_f32_32x32x16_bf16 with K = the 16 edges)
 //     and a 32-byte record per edge {m1 | m2 bit masks (16 B), g_e} for the target side.
-//  T  decoder_dgrad16_kernel   edges in by-target order (through the CSR permutation): rebuilds m2 / m1 / g_e
-//       from the records (no node-row gathers, no P1), runs P2 and sums dL/dh1 over target runs.
+//  T  decoder_dgrad16_kernel   edges in by-target order (through the CSR permutation, or the plan's position words: STREAM):
+//       rebuilds m2 / m1 / g_e from the records (no node-row gathers, no P1), runs P2 and sums dL/dh1 over target runs.
 //
 // Per wave and 16 edges: 48 + 24 MFMA(16x16x32) + 12 MFMA(32x32x16) in S, 24 in T; every product carries
 // fp32-level error (no two-term shortcuts).  No divergent control flow around matrix operands: the last tile is
@@ -36,6 +36,13 @@
 // would not raise), the split terms of W2 / 2 and g_e / 2 normal (an entry of W2 or a dL/dlogit below 2^-125 loses its last
 // bit), and h2 outside [2^-134, 2^-133) (where the mask of 2 h2 is on and the mask of h2 was off).  And -inf: relu2x(-inf) =
 // -inf + inf = NaN where relu(-inf) = 0 (tests/test_nonfinite.py holds exactly that difference).
+//
+// INVARIANT — T's mask m2 is held as 2^-7 and its W2' images as 128 W2' (T_MASK16; stage_weights16 with w2p_scale = 128).  The
+// half-word 0x3c00 is bf16 2^-7 AND IEEE-half 1.0: P2 multiplies it with the three terms of 128 (w3[j] W2[j][k]), the dL/db2 sums
+// take it as the half operand of v_fma_mix_f32.  Both factors are powers of two, so P2's accumulators — and through them the
+// part rows — are bit-identical to those of a 1.0 mask beside W2' (what S's own P2 uses: the S-vs-T equality of the run sums)
+// on the domain 128 |w3[j] W2[j][k]| <= FLT_MAX: above it T's image is inf where S's is finite (an alarm S would not raise).
+// Non-finite entries of W2 or w3 propagate alike: 2^-7 inf = inf, 0 inf = NaN, as with 1.0 (tests/test_dgrad_stream.py).
 #include "common.h"
 
 // This file is compiled TWICE (csrc/Makefile): as decoder16.o — everything, the 2-byte table format of the PQ16 instances being
@@ -58,6 +65,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef short short4v __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
 constexpr int D16 = 64;
 constexpr int SLAB16 = 64 * 64 + 64 + 64 + 64 + 16;   // gW2 | gb2 | gw3 | gcvec | gb3, loss (+pad): layout of decoder.hip
@@ -83,6 +91,8 @@ __device__ __forceinline__ int64_t next_tile(int64_t tile, int64_t cstride, int6
   last = (t1 & ((1 << clog) - 1)) == 0 || t1 >= n_tiles;
   return last ? ((tile >> clog) + cstride) << clog : t1;
 }
+// T's relu-mask value, one half-word read two ways: bf16 2^-7 in P2 (beside images of 128 W2'), IEEE half 1.0 in the dL/db2 sums
+constexpr uint32_t T_MASK16 = 0x3c00u;
 constexpr int T_WAVES = 16;                           // dgrad kernel: four waves per SIMD (128 registers each): its record gathers are latency bound
 
 // ---- LDS images.  Rows of 64 bf16 = 128 B = 8 chunks of 16 B, unpadded; chunk ch of row r sits at
@@ -219,9 +229,11 @@ __device__ __forceinline__ uint4 ld_row16u(const void* table, uint32_t byte_off)
   return *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(table) + byte_off);
 }
 
-// ---- weights -> LDS images (once per workgroup).  which = 1: W2 (P1), 2: W2'^T (P2), 3: both.
+// ---- weights -> LDS images (once per workgroup).  which = 1: W2 (P1), 2: W2'^T (P2), 3: both.  w2p_scale: a power of two
+// the W2' images are multiplied by (1 in S; 128 in T, whose mask operand is 2^-7: T_MASK16) — exact for all three terms.
 __device__ __forceinline__ void stage_weights16(const float* w2, const float* b2, const float* w3, const float* cvec,
-                                                char* lds, int nthreads, int which, int w2p_base, int vec_base) {
+                                                char* lds, int nthreads, int which, int w2p_base, int vec_base,
+                                                float w2p_scale = 1.f) {
   // the loads of several rounds in flight (a mini-batch launch is a handful of workgroups that all start here)
 #pragma unroll 8
   for (int i = threadIdx.x; i < 64 * 64; i += nthreads) {
@@ -242,7 +254,10 @@ __device__ __forceinline__ void stage_weights16(const float* w2, const float* b2
     if (which & 2) {
       // row k; the 64 j of a row in the order P1's accumulator hands them to P2: K-step t = j >> 5, lane group
       // g = (j >> 2) & 3, element s = 4 ((j >> 4) & 1) + (j & 3)   <->   chunk 4 t + g, element s
-      const float wp = w3[j] * w;
+      // the scale goes onto w3 BEFORE the product: hipcc contracts `wp - (float)h` below into fma(w3 * scale, w, -h), the
+      // residual of the UNROUNDED product — scaling the rounded product instead would give T other mid / lo terms than S
+      // (test_full_size_S_and_T_kernels_agree_on_by_source_sums fails on every row)
+      const float wp = (w2p_scale * w3[j]) * w;
       const __bf16 h = (__bf16)wp;
       const float r1 = wp - (float)h;
       const __bf16 m = (__bf16)r1;
@@ -969,20 +984,31 @@ __global__ __launch_bounds__(S_WAVES * 64) void decoder_train16_kernel(
 // Addressing (round 4): every per-position load is `scalar tile base + 32-bit lane offset` (the saddr form of
 // global_load: no 64-bit vector arithmetic), and a record is read through ONE 64-bit address per lane — mask dword g at
 // +0, g_e at +16 (S replicates dL/dlogit into dwords 4 .. 7) — instead of three 64-bit adds per load.
-struct TIds { uint32_t e; int key, key_nxt; };
-struct TIn { uint32_t recw; float g_e; int key, key_nxt; };
-template <bool PERM, bool KEYS>
-__device__ __forceinline__ TIds load_ids(const int32_t* perm, const int32_t* keys, int64_t E, int64_t tile, int64_t n_tiles,
-                                         int hx, int c) {
+// STREAM: the by-target plan carries ONE word per position, tpos[k] = perm[k] | closes_k << 31 (csr_plan.hip,
+// pangnn_csr_plan_tpos: closes_k = the key changes behind position k, or k is the last position of its chunk — a function of
+// the graph and the chunk size alone, built once per graph).  load_ids is then one 4-byte load per position; the keys[k] /
+// keys[k + 1] loads, the second clamp and the compare are gone, and the record address takes the word as it is: the 32-bit
+// e << 1 of load_rec drops bit 31.  Without a stream (no permutation, a padded batch with e_live, a structure whose plan has
+// none) the keys route below runs exactly as before.
+struct TIds { uint32_t e; int key, key_nxt; };       // STREAM: e = the word, keys unused (dead registers)
+struct TIn { uint32_t recw; float g_e; uint32_t e; int key, key_nxt; };
+template <bool PERM, bool KEYS, bool STREAM>
+__device__ __forceinline__ TIds load_ids(const int32_t* perm, const int32_t* keys, const uint32_t* tpos, int64_t E, int64_t tile,
+                                         int64_t n_tiles, int hx, int c) {
   TIds t;
   const int64_t tc = tile < n_tiles ? tile : n_tiles - 1;
   const int64_t p_tile = tc * 32;
   const int64_t rest = E - 1 - p_tile;
   const uint32_t lim = (uint32_t)(rest < 31 ? rest : 31);                 // uniform: last valid position inside the tile
-  const uint32_t lim_n = (uint32_t)(rest < 32 ? rest : 32);               // position 32 = first position of the next tile
   const uint32_t k = min((uint32_t)(16 * hx + c), lim);
-  const uint32_t kn = min(k + 1u, lim_n);
   t.key = t.key_nxt = 0;
+  if (STREAM) {
+    // the padding of the last tile repeats the last position's word; its close bit is sorted out per tile (close_mask)
+    t.e = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(tpos + p_tile) + 4u * k);
+    return t;
+  }
+  const uint32_t lim_n = (uint32_t)(rest < 32 ? rest : 32);               // position 32 = first position of the next tile
+  const uint32_t kn = min(k + 1u, lim_n);
   if (KEYS) {                                                             // (the parameter sums alone take no keys: NULL)
     const char* kt = reinterpret_cast<const char*>(keys + p_tile);        // uniform base, 32-bit lane offsets
     t.key = *reinterpret_cast<const int32_t*>(kt + 4u * k);
@@ -996,20 +1022,29 @@ __device__ __forceinline__ TIds load_ids(const int32_t* perm, const int32_t* key
 __device__ __forceinline__ TIn load_rec(const char* recg, const TIds& id) {
   TIn t;
   const char* r = recg + ((uint64_t)(id.e << 1) << 4);     // e < 2^31; a shift of 4 folds into v_lshl_add_u64, one of 5 does not
-  t.recw = *reinterpret_cast<const uint32_t*>(r);
+  t.recw = *reinterpret_cast<const uint32_t*>(r);          // (a stream word's close bit leaves with the 32-bit e << 1)
   t.g_e = *reinterpret_cast<const float*>(r + 16);
+  t.e = id.e;
   t.key = id.key;
   t.key_nxt = id.key_nxt;
   return t;
+}
+// STREAM: the close bits of a tile's 32 positions that count.  In the last tile of a list whose length is no multiple of 32,
+// positions lim .. 31 all repeat the word of position lim (the last of the list, whose bit is set: it ends its chunk): the
+// run closes ONCE, at position 31 — where the keys route closes it (its clamped key == key_nxt everywhere but there).
+__device__ __forceinline__ uint32_t close_mask(int64_t E, int64_t tile) {
+  const int64_t rest = E - 1 - tile * 32;
+  return rest < 31 ? (((1u << (uint32_t)rest) - 1u) | 0x80000000u) : 0xffffffffu;
 }
 
 // PERM (a permutation is given) / RUN (run sums wanted; false: the parameter sums alone) are compile-time, so that the
 // loads of the loop body sit in straight-line code.  Whether dL/db2 is wanted stays a runtime-uniform branch: as a template
 // parameter the scheduler's longer reach costs its 16 accumulators 25 spilled registers at the 128-register cap.
-template <bool PERM, bool RUN>
+// STREAM (with PERM and RUN): ids and run ends from the plan's position words `tpos`; perm / keys are not read.
+template <bool PERM, bool RUN, bool STREAM>
 __global__ __launch_bounds__(T_WAVES * 64) void decoder_dgrad16_kernel(
     const uint32_t* __restrict__ rec, const int32_t* __restrict__ perm, const int32_t* __restrict__ keys,
-    const float* __restrict__ w2, const float* __restrict__ w3, int64_t E, const int64_t* __restrict__ e_live_p, D16Run rs,
+    const uint32_t* __restrict__ tpos, const float* __restrict__ w2, const float* __restrict__ w3, int64_t E, const int64_t* __restrict__ e_live_p, D16Run rs,
     float* __restrict__ gb2_slabs, int64_t n_tiles) {
   // LDS: W2'^T hi | mid | lo, (b2 w3 cvec: w3 used by the dL/db2 finish), per wave: run-sum tile [17][64] floats | recl |
   // gl of both halves of the wave's 32-edge tile
@@ -1020,7 +1055,7 @@ __global__ __launch_bounds__(T_WAVES * 64) void decoder_dgrad16_kernel(
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   const int c = lane & 15, g = lane >> 4;
   char* wv = lds + T_WAVE0 + wave * TW_BYTES;
-  stage_weights16(w2, nullptr, w3, nullptr, lds, T_WAVES * 64, 2, 0, T_VEC);
+  stage_weights16(w2, nullptr, w3, nullptr, lds, T_WAVES * 64, 2, 0, T_VEC, 128.f);
   __syncthreads();
   const int wfrag0 = c * 128 + ((g ^ wsw(c)) << 4), wfrag1 = wfrag0 ^ 64;
   const int colp = 16 * (((g & 1) << 1) | (g >> 1)) + c;
@@ -1042,8 +1077,8 @@ __global__ __launch_bounds__(T_WAVES * 64) void decoder_dgrad16_kernel(
   int64_t tile1 = next_tile(tile, cstride, n_tiles, last1, clog);      // the wave's next tile
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
-    cur[h] = load_rec(recg, load_ids<PERM, RUN>(perm, keys, E, tile, n_tiles, h, c));
-    ids_nxt[h] = load_ids<PERM, RUN>(perm, keys, E, tile1, n_tiles, h, c);
+    cur[h] = load_rec(recg, load_ids<PERM, RUN, STREAM>(perm, keys, tpos, E, tile, n_tiles, h, c));
+    ids_nxt[h] = load_ids<PERM, RUN, STREAM>(perm, keys, tpos, E, tile1, n_tiles, h, c);
   }
   int poff_cur = (RUN && tile < n_tiles) ? rs.part_off[tile >> clog] : 0;
   float carry = 0.f;
@@ -1062,7 +1097,7 @@ __global__ __launch_bounds__(T_WAVES * 64) void decoder_dgrad16_kernel(
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       nxt[h] = load_rec(recg, ids_nxt[h]);
-      ids_nxt[h] = load_ids<PERM, RUN>(perm, keys, E, tile2, n_tiles, h, c);
+      ids_nxt[h] = load_ids<PERM, RUN, STREAM>(perm, keys, tpos, E, tile2, n_tiles, h, c);
     }
     bf16x8 a2[2][2];
 #pragma unroll
@@ -1072,7 +1107,10 @@ __global__ __launch_bounds__(T_WAVES * 64) void decoder_dgrad16_kernel(
       *reinterpret_cast<uint32_t*>(wv + TW_REC + 256 * h + 16 * c + 4 * g) = recw;
       *reinterpret_cast<float*>(wv + TW_GL + 64 * h + 4 * c) = g_e;
       // m2 bits of lane (c, g): pair n = 4 t + qd (elements 2 qd, 2 qd + 1 of K-step t) sits at bits 7 - n and 23 - n:
-      // (recw & (0x10001 << p)) * (0x3f80 >> p) = bf16 1.0 / 0.0 in each half (p <= 7: the products stay inside their halves)
+      // (recw & (0x10001 << p)) * (0x3c00 >> p) = 0x3c00 / 0 in each half (p <= 7: the products stay inside their halves).
+      // 0x3c00 is T's mask value (T_MASK16): 2^-7 as the bf16 A operand of P2, whose B images are 128 W2' (stage_weights16,
+      // which = 2 with scale 128) — the products, hence P2's accumulators, are bit for bit those of 1.0 x W2' — and 1.0 as
+      // an IEEE half, which v_fma_mix_f32 takes as an operand of the dL/db2 sums below.
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
         u32x4 w;
@@ -1082,19 +1120,21 @@ __global__ __launch_bounds__(T_WAVES * 64) void decoder_dgrad16_kernel(
           const int p = 7 - (4 * t + qd);
           yb[qd] = recw & (0x00010001u << p);
           asm volatile("" : "+v"(yb[qd]));      // opaque: keeps ONE and per pair (the optimiser otherwise re-derives byte 0
-          w[qd] = __umul24(yb[qd], 0x3f80u >> p);     //                                  from recw with a second and below)
+          w[qd] = __umul24(yb[qd], T_MASK16 >> p);    //                                  from recw with a second and below)
         }
         a2[h][t] = __builtin_bit_cast(bf16x8, w);
         if (gb2_slabs != nullptr) {
-          // dL/db2 partials: the masked record bits themselves as floats — byte 0 / byte 2 of (recw & (0x10001 << p)) is
-          // 2^p or 0, one v_cvt_f32_ubyte each — so accumulator (jb, i) carries 2^p times its sum, p = 7 - 2 jb - (i >> 1),
-          // an exact scale taken out once at the end.  (Round 3 rebuilt 1.0 / 0.0 from the bf16 operand: the optimiser
-          // folded that into a v_mul_lo_u32 per pair, a quarter-rate instruction, 16 per tile.)
+          // dL/db2 partials: the mask halves of the operand words themselves, 1.0 / 0.0 as IEEE halves — one v_fma_mix_f32
+          // per element (half operand by op_sel; tools/valu_issue_rate.hip: issues like v_fma_f32, every lane right beside
+          // bf16 MFMAs, profiles/t_vector_stream.md).  (Until this form each element cost a v_cvt_f32_ubyte of its record
+          // bit + a v_fma_f32, the sums carrying a factor 2^p; round 3 rebuilt 1.0 / 0.0 from a bf16 1.0 operand: the
+          // optimiser folded that into a v_mul_lo_u32 per pair, a quarter-rate instruction, 16 per tile.)
 #pragma unroll
           for (int qd = 0; qd < 4; ++qd) {
             const int jb = 2 * t + (qd >> 1), i0 = 2 * (qd & 1);
-            gb2a[jb][i0] = fmaf((float)(yb[qd] & 0xffu), g_e, gb2a[jb][i0]);
-            gb2a[jb][i0 + 1] = fmaf((float)((yb[qd] >> 16) & 0xffu), g_e, gb2a[jb][i0 + 1]);
+            const f16x2 m = __builtin_bit_cast(f16x2, (uint32_t)w[qd]);
+            gb2a[jb][i0] = fmaf((float)m[0], g_e, gb2a[jb][i0]);
+            gb2a[jb][i0 + 1] = fmaf((float)m[1], g_e, gb2a[jb][i0 + 1]);
           }
         }
       }
@@ -1103,13 +1143,20 @@ __global__ __launch_bounds__(T_WAVES * 64) void decoder_dgrad16_kernel(
     if (RUN) {
       f32x4 v[2][4];
       dgrad_tile2(lds, a2, wfrag0, wfrag1, v);
+      const uint32_t cmask = STREAM ? close_mask(E, tile) : 0u;          // scalar: wave-uniform operands
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
         f32x4 gm[4];
         dgrad_masks(wv + TW_REC + 256 * h, wv + TW_GL + 64 * h, c, g, gm);
-        const bool closes = cur[h].key != cur[h].key_nxt || (h == 1 && c == 15 && last_tile);   // key change, or end of the chunk
-        const unsigned long long bal = __ballot(closes);
-        const unsigned m16 = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(bal & 0xffffull));
+        unsigned m16;
+        if (STREAM) {
+          const unsigned long long bal = __ballot((int)cur[h].e < 0);                           // the word's close bit
+          m16 = ((unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(bal & 0xffffull)) & (cmask >> (16 * h))) & 0xffffu;
+        } else {
+          const bool closes = cur[h].key != cur[h].key_nxt || (h == 1 && c == 15 && last_tile);   // key change, or end of the chunk
+          const unsigned long long bal = __ballot(closes);
+          m16 = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(bal & 0xffffull));
+        }
         run_sums(v[h], gm, m16, carry, rs.part, pidx, wv, lane, c, g, colp);
       }
     }
@@ -1139,10 +1186,7 @@ __global__ __launch_bounds__(T_WAVES * 64) void decoder_dgrad16_kernel(
 #pragma unroll
       for (int jb = 0; jb < 4; ++jb)
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const float unscale = __builtin_bit_cast(float, (uint32_t)(127 - (7 - 2 * jb - (i >> 1))) << 23);   // 2^-p
-          red[wave * 64 + 16 * jb + 4 * g + i] = gb2a[jb][i] * unscale;
-        }
+        for (int i = 0; i < 4; ++i) red[wave * 64 + 16 * jb + 4 * g + i] = gb2a[jb][i];
     }
     __syncthreads();
     if (threadIdx.x < 64) {
@@ -1423,13 +1467,14 @@ extern "C" int pangnn_decoder_train_f32(const float* p, int64_t ldp, const float
 
 extern "C" size_t pangnn_decoder_dgrad_workspace_bytes(void) { return (size_t)cu_count() * 64 * sizeof(float); }
 
-extern "C" int pangnn_decoder_dgrad_f32(const uint32_t* rec, const int32_t* perm, const int32_t* keys, const float* w2,
-                                        const float* w3, int64_t num_edges, float* part_buf, const int32_t* part_off,
-                                        float* g_b2, const int64_t* live_edges, void* workspace, size_t workspace_bytes,
-                                        pangnn_stream_t stream) {
-  const char* who = "pangnn_decoder_dgrad_f32";
+// pangnn_decoder_dgrad_f32 (tpos = NULL) and pangnn_decoder_dgrad_stream_f32 (perm = keys = live_edges = NULL)
+static int decoder_dgrad_any(const char* who, const uint32_t* rec, const int32_t* perm, const int32_t* keys, const uint32_t* tpos,
+                             const float* w2, const float* w3, int64_t num_edges, float* part_buf, const int32_t* part_off,
+                             float* g_b2, const int64_t* live_edges, void* workspace, size_t workspace_bytes,
+                             pangnn_stream_t stream) {
   PG_CHECK_ARG(num_edges >= 0, PANGNN_E_BADARG, "%s: bad size", who);
-  // edge ids are int32 in perm and 32-bit in the kernel's record addressing ((e << 1) << 4 with a 32-bit e << 1)
+  // edge ids are int32 in perm, 31 bits of a tpos word, and 32-bit in the kernel's record addressing ((e << 1) << 4 with a
+  // 32-bit e << 1)
   PG_CHECK_ARG(num_edges < 2147483647LL, PANGNN_E_TOOLARGE, "%s: num_edges must fit int32 (partition the graph first)", who);
   hipStream_t s = (hipStream_t)stream;
   if (num_edges == 0) {
@@ -1439,9 +1484,11 @@ extern "C" int pangnn_decoder_dgrad_f32(const uint32_t* rec, const int32_t* perm
     }
     return 0;
   }
-  PG_CHECK_ARG(rec && w2 && w3 && (part_buf == nullptr) == (part_off == nullptr) && (!part_buf || keys),
+  PG_CHECK_ARG(rec && w2 && w3 && (part_buf == nullptr) == (part_off == nullptr) && (!part_buf || keys || tpos),
                PANGNN_E_BADARG, "%s: null pointer", who);
   PG_CHECK_ARG(part_buf || g_b2, PANGNN_E_BADARG, "%s: nothing to compute", who);
+  PG_CHECK_ARG(!tpos || (((uintptr_t)tpos & 3u) == 0 && part_buf), PANGNN_E_BADARG,
+               "%s: tpos must be 4-byte aligned and comes with part_buf / part_off", who);
   const int64_t n_tiles = (num_edges + 31) / 32;
   const int clog = chunk_log_for(n_tiles);
   const int64_t n_chunks = (n_tiles + (1 << clog) - 1) >> clog;
@@ -1452,13 +1499,15 @@ extern "C" int pangnn_decoder_dgrad_f32(const uint32_t* rec, const int32_t* perm
                "%s: workspace too small", who);
   const D16Run rs{part_buf, part_off, clog};
   float* b2_slabs = g_b2 ? static_cast<float*>(workspace) : nullptr;
-#define PG_T(P, R)                                                                                                   \
-  hipLaunchKernelGGL((decoder_dgrad16_kernel<P, R>), dim3((unsigned)grid), dim3(T_WAVES * 64), 0, s, rec, perm, keys, \
-                     w2, w3, num_edges, live_edges, rs, b2_slabs, n_tiles)
+#define PG_T(P, R, S)                                                                                                   \
+  hipLaunchKernelGGL((decoder_dgrad16_kernel<P, R, S>), dim3((unsigned)grid), dim3(T_WAVES * 64), 0, s, rec, perm, keys, \
+                     tpos, w2, w3, num_edges, live_edges, rs, b2_slabs, n_tiles)
   if (part_buf) {
-    if (perm) PG_T(true, true); else PG_T(false, true);
+    if (tpos) PG_T(true, true, true);
+    else if (perm) PG_T(true, true, false);
+    else PG_T(false, true, false);
   } else {
-    PG_T(false, false);                   // the parameter sum alone: the order of the positions does not matter
+    PG_T(false, false, false);            // the parameter sum alone: the order of the positions does not matter
   }
 #undef PG_T
   PG_CHECK_LAUNCH(who);
@@ -1467,5 +1516,24 @@ extern "C" int pangnn_decoder_dgrad_f32(const uint32_t* rec, const int32_t* perm
     PG_CHECK_LAUNCH(who);
   }
   return 0;
+}
+
+extern "C" int pangnn_decoder_dgrad_f32(const uint32_t* rec, const int32_t* perm, const int32_t* keys, const float* w2,
+                                        const float* w3, int64_t num_edges, float* part_buf, const int32_t* part_off,
+                                        float* g_b2, const int64_t* live_edges, void* workspace, size_t workspace_bytes,
+                                        pangnn_stream_t stream) {
+  return decoder_dgrad_any("pangnn_decoder_dgrad_f32", rec, perm, keys, nullptr, w2, w3, num_edges, part_buf, part_off, g_b2,
+                           live_edges, workspace, workspace_bytes, stream);
+}
+
+extern "C" int pangnn_decoder_dgrad_stream_f32(const uint32_t* rec, const uint32_t* tpos, const float* w2, const float* w3,
+                                               int64_t num_edges, float* part_buf, const int32_t* part_off, float* g_b2,
+                                               void* workspace, int64_t workspace_bytes, pangnn_stream_t stream) {
+  const char* who = "pangnn_decoder_dgrad_stream_f32";
+  PG_CHECK_ARG(num_edges <= 0 || (tpos && part_buf && part_off), PANGNN_E_BADARG, "%s: tpos, part_buf and part_off are required",
+               who);
+  PG_CHECK_ARG(workspace_bytes >= 0, PANGNN_E_BADARG, "%s: negative workspace size", who);
+  return decoder_dgrad_any(who, rec, nullptr, nullptr, tpos, w2, w3, num_edges, part_buf, part_off, g_b2, nullptr, workspace,
+                           (size_t)workspace_bytes, stream);
 }
 #endif  // !PANGNN_D16_TABLES_F16

@@ -34,7 +34,8 @@ enum Need : int64_t {          // bits of pangnn::_prepare_structure(..., need);
 };
 
 struct Csr { at::Tensor rowptr, other, perm, seg_ptr, parts_rowptr; };     // seg_ptr / parts_rowptr: long rows (graph.CSR.long_rows)
-struct Plan { at::Tensor part_off, part_rowptr, keys; int64_t n_parts = 0; };
+// tpos (by-target plans of the D16 chunk size only, may be undefined): the T kernel's position words (pangnn_csr_plan_tpos)
+struct Plan { at::Tensor part_off, part_rowptr, keys; int64_t n_parts = 0; at::Tensor tpos; };
 
 struct Ident {                 // identity of a tensor: storage (weak), address, version
   c10::optional<c10::weak_intrusive_ptr<c10::StorageImpl>> storage;
@@ -165,7 +166,8 @@ void register_structure(const at::Tensor& edge_index, int64_t n_dst, int64_t n_s
 }
 
 void register_plan(const at::Tensor& edge_index, int64_t n_dst, int64_t kind, int64_t chunk_tiles, const at::Tensor& part_off,
-                   const at::Tensor& part_rowptr, const at::Tensor& keys, int64_t n_parts) {
+                   const at::Tensor& part_rowptr, const at::Tensor& keys, int64_t n_parts,
+                   const c10::optional<at::Tensor>& tpos) {
   check_edge_index("_register_plan", edge_index);
   TORCH_CHECK(kind >= 0 && kind <= 2 && chunk_tiles >= 1 && n_parts >= 0, "pangnn::_register_plan: bad kind / chunk size");
   operand("_register_plan", "part_off", part_off, edge_index, at::kInt);
@@ -174,10 +176,16 @@ void register_plan(const at::Tensor& edge_index, int64_t n_dst, int64_t kind, in
   const int64_t e = edge_index.size(1), span = 32 * chunk_tiles;
   TORCH_CHECK(keys.size(0) == e && part_off.size(0) >= (e + span - 1) / span, "pangnn::_register_plan: keys [E] and one part "
               "offset per chunk of ", span, " edges");
+  at::Tensor words;
+  if (tpos.has_value() && tpos->defined()) {
+    operand("_register_plan", "tpos", *tpos, edge_index, at::kInt);
+    TORCH_CHECK(kind != 0 && tpos->size(0) == e, "pangnn::_register_plan: tpos [E] goes with the plan of a CSR order");
+    words = *tpos;
+  }
   std::lock_guard<std::mutex> lock(g_mu);
   Entry* en = find_locked(edge_index, n_dst);
   TORCH_CHECK(en != nullptr, "pangnn::_register_plan: register the structure first");
-  en->plans[{(int)kind, (int)chunk_tiles}] = Plan{part_off, part_rowptr, keys, n_parts};
+  en->plans[{(int)kind, (int)chunk_tiles}] = Plan{part_off, part_rowptr, keys, n_parts, words};
 }
 
 void register_norm(const at::Tensor& edge_index, int64_t n_dst, const c10::optional<at::Tensor>& weight, const at::Tensor& dis,
@@ -625,13 +633,22 @@ void dgrad_sum(const at::Tensor& rec, const View& v, int by /* 1 dst, 2 src, 0 n
     wsb = pangnn_decoder_dgrad_workspace_bytes();
     ws = bytes(wsb, in.w2);
   }
-  check_rc(pangnn_decoder_dgrad_f32(reinterpret_cast<const uint32_t*>(rec.data_ptr<int32_t>()),
-                                    csr ? csr->perm.data_ptr<int32_t>() : nullptr, plan ? plan->keys.data_ptr<int32_t>() : nullptr,
-                                    in.w2.data_ptr<float>(), in.w3.data_ptr<float>(), v.num_edges,
-                                    plan ? parts.data_ptr<float>() : nullptr, plan ? plan->part_off.data_ptr<int32_t>() : nullptr,
-                                    g_b2 ? g_b2->data_ptr<float>() : nullptr, opt_ptr<int64_t>(live), g_b2 ? ws.data_ptr() : nullptr,
-                                    wsb, stream_of(rec)),
-           "pangnn_decoder_dgrad_f32");
+  const uint32_t* recp = reinterpret_cast<const uint32_t*>(rec.data_ptr<int32_t>());
+  if (plan && plan->tpos.defined() && !defined(live)) {
+    // the plan carries the order as one word per position (built once per graph): the stream route of T
+    check_rc(pangnn_decoder_dgrad_stream_f32(recp, reinterpret_cast<const uint32_t*>(plan->tpos.data_ptr<int32_t>()),
+                                             in.w2.data_ptr<float>(), in.w3.data_ptr<float>(), v.num_edges, parts.data_ptr<float>(),
+                                             plan->part_off.data_ptr<int32_t>(), g_b2 ? g_b2->data_ptr<float>() : nullptr,
+                                             g_b2 ? ws.data_ptr() : nullptr, (int64_t)wsb, stream_of(rec)),
+             "pangnn_decoder_dgrad_stream_f32");
+  } else {
+    check_rc(pangnn_decoder_dgrad_f32(recp, csr ? csr->perm.data_ptr<int32_t>() : nullptr,
+                                      plan ? plan->keys.data_ptr<int32_t>() : nullptr, in.w2.data_ptr<float>(),
+                                      in.w3.data_ptr<float>(), v.num_edges, plan ? parts.data_ptr<float>() : nullptr,
+                                      plan ? plan->part_off.data_ptr<int32_t>() : nullptr, g_b2 ? g_b2->data_ptr<float>() : nullptr,
+                                      opt_ptr<int64_t>(live), g_b2 ? ws.data_ptr() : nullptr, wsb, stream_of(rec)),
+             "pangnn_decoder_dgrad_f32");
+  }
   if (plan && keep_parts) *keep_parts = parts;
   else if (plan) sum_parts(*plan, parts, n_rows, *out);
 }
@@ -1345,7 +1362,7 @@ TORCH_LIBRARY_FRAGMENT(pangnn, m) {
   m.def("_register_structure(Tensor edge_index, int n_dst, int n_src, Tensor ei_contig, Tensor[] by_dst, Tensor[] by_src, int band, "
         "int sorted_by_src) -> ()");
   m.def("_register_plan(Tensor edge_index, int n_dst, int kind, int chunk_tiles, Tensor part_off, Tensor part_rowptr, Tensor keys, "
-        "int n_parts) -> ()");
+        "int n_parts, Tensor? tpos=None) -> ()");
   m.def("_register_norm(Tensor edge_index, int n_dst, Tensor? weight, Tensor dis, Tensor by_dst, Tensor orig, Tensor? by_src) -> ()");
   m.def("_register_actions(Tensor edge_index, int n_dst, Tensor? weight, Tensor x, Tensor r, Tensor s) -> ()");
   m.def("_prepare_structure(Tensor edge_index, int n_dst, Tensor? edge_weight, Tensor? x, int need) -> ()");

@@ -614,7 +614,7 @@ def _sum_parts(plan, part_buf: torch.Tensor, n_rows: int, out: torch.Tensor, acc
 def _dgrad_sum(rec, st: EdgeStructure, by: Optional[str], w2, w3, n_rows: int = 0, out=None, g_b2=None, live=None,
                accumulate: bool = False, raw_parts: bool = False):
     """dL/dh1 summed over the rows of CSR order `by` ("src" / "dst") from the per-edge records of the training
-    kernel: pangnn_decoder_dgrad_f32 (run parts) + the short contiguous part sum.  `g_b2`: also filled with dL/db2
+    kernel: pangnn_decoder_dgrad_f32 / _stream_f32 (run parts) + the short contiguous part sum.  `g_b2`: also filled with dL/db2
     (one call per step asks for it); by = None: the parameter sums alone.  `raw_parts`: no part sum — (plan, parts) come
     back for pangnn_linear_act_backward_parts_f32."""
     dev = rec.device
@@ -622,10 +622,15 @@ def _dgrad_sum(rec, st: EdgeStructure, by: Optional[str], w2, w3, n_rows: int = 
     csr = None if not by else (st.by_dst if by == "dst" else st.by_src)
     parts = None if plan is None else torch.empty(plan.n_parts, 64, dtype=torch.float32, device=dev)
     ws, ws_bytes = _workspace(dev, "pangnn_decoder_dgrad") if g_b2 is not None else (None, 0)
-    _launch(dev, "pangnn_decoder_dgrad_f32", rec.data_ptr(), None if csr is None else _lib.ptr(csr.perm),
-            None if plan is None else plan.keys.data_ptr(), w2.data_ptr(), w3.data_ptr(), st.num_edges, _lib.ptr(parts),
-            None if plan is None else plan.part_off.data_ptr(), _lib.ptr(g_b2), _lib.ptr(live), _lib.ptr(ws), ws_bytes,
-            tag="dec.dgrad")
+    tpos = None if (plan is None or live is not None) else getattr(plan, "tpos", None)
+    if tpos is not None:          # the plan carries the order as one word per position: the stream route of T
+        _launch(dev, "pangnn_decoder_dgrad_stream_f32", rec.data_ptr(), tpos.data_ptr(), w2.data_ptr(), w3.data_ptr(),
+                st.num_edges, _lib.ptr(parts), plan.part_off.data_ptr(), _lib.ptr(g_b2), _lib.ptr(ws), ws_bytes, tag="dec.dgrad")
+    else:
+        _launch(dev, "pangnn_decoder_dgrad_f32", rec.data_ptr(), None if csr is None else _lib.ptr(csr.perm),
+                None if plan is None else plan.keys.data_ptr(), w2.data_ptr(), w3.data_ptr(), st.num_edges, _lib.ptr(parts),
+                None if plan is None else plan.part_off.data_ptr(), _lib.ptr(g_b2), _lib.ptr(live), _lib.ptr(ws), ws_bytes,
+                tag="dec.dgrad")
     if plan is None:
         return None
     if raw_parts:

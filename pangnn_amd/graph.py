@@ -378,11 +378,14 @@ class EdgeStructure:
         return plan
 
     @staticmethod
-    def _plan_of_rowptr(rowptr: torch.Tensor, num_edges: int, chunk_tiles: int = 1):
+    def _plan_of_rowptr(rowptr: torch.Tensor, num_edges: int, chunk_tiles: int = 1, perm: Optional[torch.Tensor] = None):
         """The plan `_plan_of_sorted_keys` makes of a CSR order's keys, from that order's row pointer alone (device tensors;
         pangnn_csr_plan, csrc/csr_plan.hip): the keys are non-decreasing, so the key changes sit at rowptr[r] of the
         non-empty rows — one scan over the rows and one write of `keys`, no pass over a key array.  Same fields, dtypes and
-        shapes, entry for entry (tests/test_csr_plan.py)."""
+        shapes, entry for entry (tests/test_csr_plan.py).
+        `perm` (that order's int32 edge ids): the plan also carries `tpos` — one word per position, perm[p] | closes_p << 31
+        with closes_p = "a part ends behind p" (pangnn_csr_plan_tpos; held as int32, read as uint32) — the stream the
+        decoder's T pass walks instead of perm and keys (pangnn_decoder_dgrad_stream_f32): 4 more bytes per edge kept."""
         from types import SimpleNamespace
         lib = _lib.load()
         e, n_rows, ct = int(num_edges), rowptr.shape[0] - 1, int(chunk_tiles)
@@ -402,8 +405,14 @@ class EdgeStructure:
             _lib.check(lib.pangnn_csr_plan(rowptr.data_ptr(), n_rows, e, span, keys.data_ptr(), part_off.data_ptr(),
                                            part_rowptr.data_ptr(), last.data_ptr(), ws.data_ptr(), ws_bytes,
                                            _lib.stream_ptr()), "pangnn_csr_plan")
+            tpos = None
+            if perm is not None:
+                perm = perm if perm.is_contiguous() else perm.contiguous()
+                tpos = torch.empty(e, dtype=torch.int32, device=dev)
+                _lib.check(lib.pangnn_csr_plan_tpos(perm.data_ptr(), keys.data_ptr(), e, span, tpos.data_ptr(),
+                                                    _lib.stream_ptr()), "pangnn_csr_plan_tpos")
         plan = SimpleNamespace(n_parts=nc + min(n_rows, e), part_off=part_off, part_rowptr=part_rowptr, keys=keys,
-                               chunk_tiles=ct, _last=last)
+                               chunk_tiles=ct, _last=last, tpos=tpos)
         plan.n_parts_exact = lambda: int(plan._last) + 1
         return plan
 
@@ -419,7 +428,12 @@ class EdgeStructure:
             if not self.num_edges:
                 cache[key] = None
             elif PLAN_KERNEL and csr.rowptr.is_cuda:
-                cache[key] = self._plan_of_rowptr(csr.rowptr, self.num_edges, chunk_tiles)
+                # the by-target plan of a square structure at the S / T kernels' chunk size also carries T's position words;
+                # every other plan (by source, a shard's rectangular structure, the strict-fp32 kernels' one-tile chunks of a
+                # long list, the small build, the index-op route) has none and T takes its keys route
+                stream = by == "dst" and self.num_src == self.num_nodes and csr.perm.dtype == torch.int32 and \
+                    int(chunk_tiles) == int(_lib.load().pangnn_decoder_chunk_tiles_for(self.num_edges))
+                cache[key] = self._plan_of_rowptr(csr.rowptr, self.num_edges, chunk_tiles, csr.perm if stream else None)
             else:
                 keys = self.edge_index[1 if by == "dst" else 0][csr.perm.long()]
                 cache[key] = self._plan_of_sorted_keys(keys, n_rows, chunk_tiles)
@@ -503,7 +517,8 @@ class EdgeStructure:
             if need & bit & ~have:
                 if e:
                     plan = self.csr_plan(by, ct)
-                    ops._register_plan(ei, n, kind, ct, plan.part_off, plan.part_rowptr, plan.keys, int(plan.n_parts))
+                    ops._register_plan(ei, n, kind, ct, plan.part_off, plan.part_rowptr, plan.keys, int(plan.n_parts),
+                                       getattr(plan, "tpos", None))
                 have |= bit
         self._native = have
         nb = need & _NORM_BITS
