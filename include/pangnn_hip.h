@@ -33,7 +33,8 @@ extern "C" {
  * stays; the binding resolves every symbol at load, which refuses an older library of the same number.
  * Likewise pangnn_edge_dot_mixed, pangnn_gcn_norm_bwd_f32 and its _workspace_bytes (dL/d(edge_weight) of GCNConv), and
  * pangnn_qscore_fwd / pangnn_qscore_bwd with PANGNN_DTYPE_F64 (the differentiable Q-score edge weights), and
- * pangnn_csr_plan_tpos + pangnn_decoder_dgrad_stream_f32 (the T pass on one position word per edge). */
+ * pangnn_csr_plan_tpos + pangnn_decoder_dgrad_stream_f32 (the T pass on one position word per edge), and
+ * pangnn_csr_plan_spos + pangnn_decoder_train_stream_f32 / _mixed (the S pass on one word pair per position). */
 #define PANGNN_ABI_VERSION 3
 
 #define PANGNN_E_BADARG    (-1)  /* null pointer / negative size / unsupported feature width */
@@ -357,6 +358,11 @@ int pangnn_decoder_nd_loss_f32(const float* p, int64_t ldp, const float* q, int6
  *   dL/dW2 = diag(w3) m2 (g_e h1) with the relu mask m2 as the EXACT bf16 operand and the other operand split
  *   three ways.  The last tile is padded by clamping edge ids (one tile body, no divergent matrix operands).
  *   workspace: pangnn_decoder_train_workspace_bytes().
+ * pangnn_decoder_train_stream_f32 / _mixed: the same pass and the same results, bit for bit, for a source-sorted list given
+ *   as ONE 8-byte word pair per position, spos[k] = { src_k | closes_k << 31, dst_k } (pangnn_csr_plan_spos below: built once
+ *   per graph) in place of edge_index: one id load per position instead of three, row offsets by shifts, no per-step key
+ *   compares.  spos, part_buf and part_off are required (num_edges > 0); ldp and ldq times the element size must be powers
+ *   of two (PANGNN_E_BADARG otherwise: such tables take pangnn_decoder_train_*); every edge is real (no live_edges).
  *
  * pangnn_decoder_dgrad_f32  ("T"): dL/dh1 summed over runs of equal keys in a permuted edge order, from `rec`:
  *   position k of the order is edge perm[k] (NULL = identity) with run key keys[k] (non-decreasing, e.g. the
@@ -406,6 +412,20 @@ int pangnn_decoder_train_mixed(const void* p, int64_t ldp, const void* q, int64_
                                float* part_buf, const int32_t* part_off, float* g_w2, float* g_w3, float* g_b3,
                                float* g_cvec, const int64_t* live_edges, void* workspace, size_t workspace_bytes,
                                pangnn_stream_t stream);
+int pangnn_decoder_train_stream_f32(const float* p, int64_t ldp, const float* q, int64_t ldq, int64_t num_nodes,
+                                    const uint32_t* spos, int64_t num_edges, const float* extra, const float* cvec,
+                                    const float* w2, const float* b2, const float* w3, const float* b3, int32_t D,
+                                    const float* y, const float* pos_weight, int64_t denom, const float* g_logits,
+                                    float* logits, float* loss, uint32_t* rec, float* part_buf, const int32_t* part_off,
+                                    float* g_w2, float* g_w3, float* g_b3, float* g_cvec, void* workspace,
+                                    int64_t workspace_bytes, pangnn_stream_t stream);
+int pangnn_decoder_train_stream_mixed(const void* p, int64_t ldp, const void* q, int64_t ldq, int32_t pq_dtype,
+                                      int64_t num_nodes, const uint32_t* spos, int64_t num_edges, const float* extra,
+                                      const float* cvec, const float* w2, const float* b2, const float* w3, const float* b3,
+                                      int32_t D, const float* y, const float* pos_weight, int64_t denom,
+                                      const float* g_logits, float* logits, float* loss, uint32_t* rec, float* part_buf,
+                                      const int32_t* part_off, float* g_w2, float* g_w3, float* g_b3, float* g_cvec,
+                                      void* workspace, int64_t workspace_bytes, pangnn_stream_t stream);
 int pangnn_decoder_mlp_infer_mixed(const void* p, int64_t ldp, const void* q, int64_t ldq, int32_t pq_dtype,
                                    int64_t num_nodes, const int64_t* edge_index, int64_t ld, int64_t num_edges,
                                    const float* extra, const float* cvec, const float* w2, const float* b2,
@@ -801,6 +821,15 @@ int    pangnn_csr_plan(const int64_t* rowptr, int64_t n_rows, int64_t num_edges,
  *   tpos [E] uint32   perm[p] | closes_p << 31,  closes_p = (p + 1 == E  ||  (p + 1) % span == 0  ||  keys[p + 1] != keys[p])
  * i.e. bit 31 says that a part row ends behind position p.  One elementwise launch, plain stores; num_edges >= 1. */
 int    pangnn_csr_plan_tpos(const int32_t* perm, const int32_t* keys, int64_t num_edges, int32_t span, uint32_t* tpos,
+                            pangnn_stream_t stream);
+/* The position stream of a source-sorted edge list for pangnn_decoder_train_stream_*: edge_index [2, ld] int64 (row 0
+ * non-decreasing, every id in [0, 2^31)), span = 32 * pangnn_decoder_chunk_tiles_for(num_edges) ->
+ *   spos [2 * P] uint32, P = 32 * ceil(num_edges / 32) positions of two words each (8-byte aligned):
+ *   { src_k | closes_p << 31, dst_k } with k = min(p, num_edges - 1) — a position past the list repeats the last edge —
+ *   closes_p = (p + 1 == P  ||  (p + 1) % span == 0  ||  (p + 1 < num_edges && src[p + 1] != src[p]))
+ * i.e. bit 31 says that a part row ends behind position p: where the source changes, at the end of a chunk, and at the
+ * end of the last tile (whose padding adds zeros to the last run).  One elementwise launch, plain stores; num_edges >= 1. */
+int    pangnn_csr_plan_spos(const int64_t* edge_index, int64_t ld, int64_t num_edges, int32_t span, uint32_t* spos,
                             pangnn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------

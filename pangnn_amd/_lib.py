@@ -118,6 +118,12 @@ SIGNATURES = {
                                              _p, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "pangnn_decoder_mlp_infer_mixed": (C.c_int, [_p, _i64, _p, _i64, _i32, _i64, _p, _i64, _i64, _p, _p, _p, _p, _p, _p,
                                                  _i32, _p, _p]),
+    # the same pass on the plan's position stream: (p, ldp, q, ldq, [pq_dtype,] num_nodes, spos, num_edges, extra, ...,
+    # g_cvec, workspace, workspace_bytes, stream) — no ld, no live_edges
+    "pangnn_decoder_train_stream_f32": (C.c_int, [_p, _i64, _p, _i64, _i64, _p, _i64, _p, _p, _p, _p, _p, _p, _i32,
+                                                  _p, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _p]),
+    "pangnn_decoder_train_stream_mixed": (C.c_int, [_p, _i64, _p, _i64, _i32, _i64, _p, _i64, _p, _p, _p, _p, _p, _p, _i32,
+                                                    _p, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _p]),
     # T kernel: dL/dh1 run sums in a permuted (CSR) edge order from the records
     "pangnn_decoder_dgrad_workspace_bytes": (_sz, []),
     "pangnn_decoder_dgrad_f32": (C.c_int, [_p, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _p, _sz, _p]),
@@ -163,6 +169,8 @@ SIGNATURES = {
     "pangnn_csr_plan": (C.c_int, [_p, _i64, _i64, _i32, _p, _p, _p, _p, _p, _i64, _p]),
     # the T pass's position words of that order: (perm, keys, num_edges, span, tpos, stream)
     "pangnn_csr_plan_tpos": (C.c_int, [_p, _p, _i64, _i32, _p, _p]),
+    # the S pass's position stream of a source-sorted list: (edge_index, ld, num_edges, span, spos, stream)
+    "pangnn_csr_plan_spos": (C.c_int, [_p, _i64, _i64, _i32, _p, _p]),
     # the mask of the k smallest keys (csrc/mask_select.hip): (keys, n, k, keep, workspace, bytes, stream)
     "pangnn_mask_k_smallest_workspace_bytes": (_i64, [_i64]),
     "pangnn_mask_k_smallest_i64": (C.c_int, [_p, _i64, _i64, _p, _p, _i64, _p]),

@@ -22,6 +22,12 @@
 // keys above — tpos[p] = perm[p] | closes_p << 31, closes_p = [p + 1 == E  or  (p + 1) % span == 0  or  keys[p + 1] != keys[p]]:
 // the edge id at position p and "a part ends behind p", which the kernel otherwise re-derives from three loads per position in
 // every step.  One elementwise launch per graph, 4 bytes per edge kept.
+//
+// pangnn_csr_plan_spos: the same for the S kernel on a source-sorted list, which is its own by-source order — two words per
+// position, spos[p] = { src_p | closes_p << 31, dst_p }, for the positions of whole 32-edge tiles: a position past the list
+// repeats the last edge, and the last position of the last tile closes (so does every span-th position; the list's last
+// edge itself only where one of the two says so — a wave carries its run to the end of the tile, the padding adds zeros).
+// One elementwise launch per graph, 8 bytes per edge kept.
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>
@@ -142,10 +148,40 @@ __global__ __launch_bounds__(kBlock) void csr_plan_tpos_kernel(const int32_t* __
   }
 }
 
+// p runs over the padded positions [0, 32 * ceil(e / 32)); a position past the list looks at the last edge
+__global__ __launch_bounds__(kBlock) void csr_plan_spos_kernel(const int64_t* __restrict__ ei, int64_t ld, int64_t e, int64_t span,
+                                                              uint2* __restrict__ spos) {
+  const int64_t nthreads = (int64_t)gridDim.x * kBlock, padded = (e + 31) / 32 * 32;
+  for (int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x; p < padded; p += nthreads) {
+    const int64_t q = p + 1, k = p < e ? p : e - 1;
+    const int64_t src = ei[k];
+    const bool closes = q == padded || q % span == 0 || (q < e && ei[q] != src);
+    spos[p] = make_uint2(((uint32_t)src & 0x7fffffffu) | (closes ? 0x80000000u : 0u), (uint32_t)ei[ld + k]);
+  }
+}
+
 }  // namespace
 }  // namespace pangnn
 
 using namespace pangnn;
+
+extern "C" int pangnn_csr_plan_spos(const int64_t* edge_index, int64_t ld, int64_t num_edges, int32_t span, uint32_t* spos,
+                                    pangnn_stream_t stream) {
+  const char* name = "pangnn_csr_plan_spos";
+  const int64_t e = num_edges;
+  PG_CHECK_ARG(e >= 1 && ld >= e, PANGNN_E_BADARG, "%s: bad size (E=%lld, ld=%lld: at least one edge)", name, (long long)e,
+               (long long)ld);
+  PG_CHECK_ARG(e < ((int64_t)1 << 31) - 1, PANGNN_E_TOOLARGE, "%s: E must fit int32", name);
+  PG_CHECK_ARG(span >= 32 && span % 32 == 0, PANGNN_E_BADARG, "%s: span %d is not a positive multiple of 32", name, (int)span);
+  PG_CHECK_ARG(edge_index && spos, PANGNN_E_BADARG, "%s: null pointer", name);
+  PG_CHECK_ARG((((uintptr_t)edge_index | (uintptr_t)spos) & 7u) == 0, PANGNN_E_ALIGN, "%s: a pointer is not 8-byte aligned", name);
+  int64_t blocks = ((e + 31) / 32 * 32 + kBlock - 1) / kBlock;
+  if (blocks > kPlanMaxBlocks) blocks = kPlanMaxBlocks;
+  hipLaunchKernelGGL(csr_plan_spos_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, edge_index, ld, e,
+                     (int64_t)span, reinterpret_cast<uint2*>(spos));
+  PG_CHECK_LAUNCH(name);
+  return 0;
+}
 
 extern "C" int pangnn_csr_plan_tpos(const int32_t* perm, const int32_t* keys, int64_t num_edges, int32_t span, uint32_t* tpos,
                                     pangnn_stream_t stream) {

@@ -8,7 +8,8 @@
 // Two kernels replace the one-wave-per-SIMD kernel of round 1 (decoder_bwd_x3_kernel) and the 19 GB
 // dL/dh1 [E,64] round trip behind it:
 //
-//  S  decoder_train16_kernel   edges in the caller's order, 16-edge half tiles on v_mfma_f32_16x16x32_bf16:
+//  S  decoder_train16_kernel   edges in the caller's order (read as int64 ids, or as the run-sum plan's position stream: STREAM),
+//     16-edge half tiles on v_mfma_f32_16x16x32_bf16:
 //       P1  C[j][e] = sum_k W2[j][k] h1[e][k]            (three-way split operands, 6 partial products)
 //       loss, g_e = dL/dlogit_e, m2[j][e] = [h2 > 0], m1[e][k] = [h1 > 0]
 //       P2  dL/dh1[e][k] = m1 g_e sum_j m2[j][e] W2'[j][k],   W2' = diag(w3) W2   (A = m2 is EXACT in bf16,
@@ -212,6 +213,8 @@ __device__ __forceinline__ bf16x8 ld_b128(const char* lds_base, int off) {
 struct D16Params {
   const void* p; const void* q; uint32_t ldp_b; uint32_t ldq_b;     // row strides in bytes; rows are f32 or bf16 (PQ16)
   const int64_t* ei; int64_t ld; int64_t E;
+  // (the STREAM instances of S: `ei` is the position stream — 8 bytes per position, as an id is —, `ld` is unused and
+  // ldp_b / ldq_b hold log2 of the row strides in bytes; see load_half)
   const float* extra; const float* cvec;
   const float* w2; const float* b2; const float* w3; const float* b3;
   // e_live (nullable, device): the first *e_live edges of the list are real, the rest is padding (a fixed-shape batch whose
@@ -481,10 +484,31 @@ typedef HalfRowsT<false> HalfRows;
 // ids / label (or given gradient) / skip feature of the 16 edges of half `hx` of tile `tile`.  Addresses are a
 // wave-uniform tile base (scalar registers) plus a 32-bit lane offset; edges past the end of the list (the last
 // tile, and the prefetch of a tile the wave will not run) are clamped to the last edge.
-template <bool EXTRA>
+// STREAM: `a.ei` is the graph's position stream (csr_plan.hip, pangnn_csr_plan_spos: built once per graph), two words per
+// position of the source-sorted list, padded to whole tiles with the last edge — { src | closes << 31, dst }: ONE 8-byte
+// load per lane, row offsets by the shifts in a.ldp_b / a.ldq_b (which push the close bit out), no id of the next
+// position, no key compare; `key` carries the first word, whose sign is "a run closes behind this position".
+// Labels and the skip feature are per-call arrays of E entries and keep their clamped position.
+template <bool EXTRA, bool STREAM>
 __device__ __forceinline__ HalfIn load_half(const D16Params& a, const float* aux, int64_t tile, int64_t n_tiles, int hx,
                                             int c) {
   HalfIn h;
+  if (STREAM) {
+    // the uniform tile bookkeeping in 32 bits (E < 2^31; a prefetched tile number stays below n_tiles + 16 * the chunk stride):
+    // scalar compares, where the 64-bit signed ones of the ids form run on the vector unit
+    const int nt = (int)n_tiles, t32 = (int)tile;
+    const int e_tile = (t32 < nt ? t32 : nt - 1) * 32;
+    const int rest = (int)a.E - 1 - e_tile;
+    const uint32_t pos = (uint32_t)(16 * hx + c), k = min(pos, (uint32_t)(rest < 31 ? rest : 31));
+    const uint2 w = *reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(a.ei + e_tile) + 8u * pos);
+    h.key = (int)w.x;
+    h.key_nxt = 0;
+    h.poff = w.x << a.ldp_b;
+    h.qoff = w.y << a.ldq_b;
+    h.aux = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(aux + e_tile) + 4u * k);
+    h.w_e = EXTRA ? *reinterpret_cast<const float*>(reinterpret_cast<const char*>(a.extra + e_tile) + 4u * k) : 0.f;
+    return h;
+  }
   const int64_t tc = tile < n_tiles ? tile : n_tiles - 1;
   const int64_t e_tile = tc * 32;
   const int64_t rest = a.E - 1 - e_tile;
@@ -635,7 +659,8 @@ __device__ __forceinline__ void h1_frags(const HalfRowsT<PQ16>& rows, bool has_e
     for (int s = 0; s < 8; ++s) h[ks][s] = relu2x(h[ks][s]);       // 2 h1 (P1's images are W2 / 2)
 }
 
-template <bool FUSED_LOSS, bool RUNSUM, bool PQ16, bool EXTRA>
+// STREAM (with RUNSUM): ids and run ends from the graph's position stream (load_half); every edge is real (no e_live).
+template <bool FUSED_LOSS, bool RUNSUM, bool PQ16, bool EXTRA, bool STREAM>
 __global__ __launch_bounds__(S_WAVES * 64) void decoder_train16_kernel(
     D16Params a, const float* __restrict__ g_logits, D16Loss lp, float* __restrict__ logits, D16Run rs,
     uint32_t* __restrict__ rec, float* __restrict__ slabs, int64_t n_tiles) {
@@ -691,7 +716,7 @@ __global__ __launch_bounds__(S_WAVES * 64) void decoder_train16_kernel(
   const int64_t cstride = (int64_t)gridDim.x * S_WAVES;                // in chunks
   const int64_t n_chunks = (n_tiles + (1 << clog) - 1) >> clog;
   int64_t tile = ((int64_t)blockIdx.x * S_WAVES + wave) << clog;
-  HalfIn in_cur = load_half<EXTRA>(a, auxp, tile, n_tiles, 0, c);
+  HalfIn in_cur = load_half<EXTRA, STREAM>(a, auxp, tile, n_tiles, 0, c);
   HalfRowsT<PQ16> rows;
   issue_half_rows(a, in_cur, g, rows);
   int poff_cur = (RUNSUM && tile < n_tiles) ? rs.part_off[tile >> clog] : 0;
@@ -715,7 +740,7 @@ __global__ __launch_bounds__(S_WAVES * 64) void decoder_train16_kernel(
 #pragma unroll 1
     for (int hx = 0; hx < 2; ++hx) {
       // ids of the next half tile (this tile's second half, or the first half of the wave's next tile)
-      const HalfIn in_nxt = load_half<EXTRA>(a, auxp, hx == 0 ? tile : tile_nxt, n_tiles, hx ^ 1, c);    // one load site
+      const HalfIn in_nxt = load_half<EXTRA, STREAM>(a, auxp, hx == 0 ? tile : tile_nxt, n_tiles, hx ^ 1, c);    // one load site
       const int pos = 16 * hx + c;
       const bool live = pos <= live_lim;
 
@@ -859,7 +884,8 @@ __global__ __launch_bounds__(S_WAVES * 64) void decoder_train16_kernel(
             for (int i = 0; i < 4; ++i) gcv[kb] = fmaf(w4[i], pv[kb][i], gcv[kb]);
         }
         if (RUNSUM) {
-          const bool closes = in_cur.key != in_cur.key_nxt || (pos == 31 && last_tile);     // key change, or end of the chunk
+          // key change, or end of the chunk (STREAM: both are the sign of the position's first word)
+          const bool closes = STREAM ? in_cur.key < 0 : (in_cur.key != in_cur.key_nxt || (pos == 31 && last_tile));
           const unsigned long long bal = __ballot(closes);
           const unsigned m16 = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(bal & 0xffffull));
           run_sums(v, gm, m16, carry, rs.part, pidx, wv, lane, c, g, colp);
@@ -1266,19 +1292,21 @@ namespace pangnn {
 // ..._f16 in decoder16_f16.o.  `a` carries the row strides in bytes; y / part_buf / extra select the instance.
 int D16_TABLES16(launch_train16_tables)(const D16Params& a, const float* g_logits, const D16Loss& lp, float* logits,
                                         const D16Run& rs, uint32_t* rec, float* ws, int64_t n_tiles, unsigned grid,
-                                        hipStream_t s) {
+                                        bool stream, hipStream_t s) {
   const dim3 gd(grid), bd(S_WAVES * 64);
-#define PG_S16(F, R)                                                                                                  \
+#define PG_S16(F, R, S)                                                                                               \
   do {                                                                                                                \
     if (a.extra)                                                                                                      \
-      hipLaunchKernelGGL((decoder_train16_kernel<F, R, true, true>), gd, bd, 0, s, a, g_logits, lp, logits, rs, rec, ws, n_tiles);   \
+      hipLaunchKernelGGL((decoder_train16_kernel<F, R, true, true, S>), gd, bd, 0, s, a, g_logits, lp, logits, rs, rec, ws, n_tiles);   \
     else                                                                                                              \
-      hipLaunchKernelGGL((decoder_train16_kernel<F, R, true, false>), gd, bd, 0, s, a, g_logits, lp, logits, rs, rec, ws, n_tiles);  \
+      hipLaunchKernelGGL((decoder_train16_kernel<F, R, true, false, S>), gd, bd, 0, s, a, g_logits, lp, logits, rs, rec, ws, n_tiles);  \
   } while (0)
-  if (lp.y && rs.part) PG_S16(true, true);
-  else if (lp.y) PG_S16(true, false);
-  else if (rs.part) PG_S16(false, true);
-  else PG_S16(false, false);
+  if (stream && lp.y) PG_S16(true, true, true);            // the stream route comes with run sums (decoder_train_any)
+  else if (stream) PG_S16(false, true, true);
+  else if (lp.y && rs.part) PG_S16(true, true, false);
+  else if (lp.y) PG_S16(true, false, false);
+  else if (rs.part) PG_S16(false, true, false);
+  else PG_S16(false, false, false);
 #undef PG_S16
   return 0;
 }
@@ -1294,7 +1322,7 @@ int D16_TABLES16(launch_infer16_tables)(const D16Params& a, float* logits, int64
 #ifndef PANGNN_D16_TABLES_F16        // ---- everything below: decoder16.o only
 namespace pangnn {
 int launch_train16_tables_f16(const D16Params& a, const float* g_logits, const D16Loss& lp, float* logits, const D16Run& rs,
-                              uint32_t* rec, float* ws, int64_t n_tiles, unsigned grid, hipStream_t s);      // decoder16_f16.o
+                              uint32_t* rec, float* ws, int64_t n_tiles, unsigned grid, bool stream, hipStream_t s);      // decoder16_f16.o
 int launch_infer16_tables_f16(const D16Params& a, float* logits, int64_t n_tiles, unsigned grid, hipStream_t s);
 // decoder.hip: sums the per-workgroup slabs (layout SLAB16) in index order
 int launch_decoder_reduce(const float* slabs, int n_slabs, float* g_w2, float* g_b2, float* g_w3, float* g_cvec,
@@ -1375,16 +1403,14 @@ extern "C" int pangnn_decoder_mlp_infer_mixed(const void* p, int64_t ldp, const 
                             (hipStream_t)stream);
 }
 
-extern "C" int pangnn_decoder_train_mixed(const void* p, int64_t ldp, const void* q, int64_t ldq, int32_t pq_dtype,
-                                          int64_t num_nodes, const int64_t* edge_index, int64_t ld, int64_t num_edges,
-                                          const float* extra, const float* cvec, const float* w2, const float* b2,
-                                          const float* w3, const float* b3, int32_t D, const float* y,
-                                          const float* pos_weight, int64_t denom, const float* g_logits, float* logits,
-                                          float* loss, uint32_t* rec, float* part_buf, const int32_t* part_off,
-                                          float* g_w2, float* g_w3, float* g_b3, float* g_cvec,
-                                          const int64_t* live_edges, void* workspace, size_t workspace_bytes,
-                                          pangnn_stream_t stream) {
-  const char* who = "pangnn_decoder_train";
+// pangnn_decoder_train_mixed / _f32 (spos = NULL) and pangnn_decoder_train_stream_mixed / _f32 (edge_index = live_edges = NULL)
+static int decoder_train_any(const char* who, const void* p, int64_t ldp, const void* q, int64_t ldq, int32_t pq_dtype,
+                             int64_t num_nodes, const int64_t* edge_index, int64_t ld, const uint32_t* spos, int64_t num_edges,
+                             const float* extra, const float* cvec, const float* w2, const float* b2, const float* w3,
+                             const float* b3, int32_t D, const float* y, const float* pos_weight, int64_t denom,
+                             const float* g_logits, float* logits, float* loss, uint32_t* rec, float* part_buf,
+                             const int32_t* part_off, float* g_w2, float* g_w3, float* g_b3, float* g_cvec,
+                             const int64_t* live_edges, void* workspace, size_t workspace_bytes, pangnn_stream_t stream) {
   const bool pq16 = pq_dtype == PANGNN_DTYPE_BF16 || pq_dtype == PANGNN_DTYPE_F16;          // a 2-byte table format
   PG_CHECK_ARG(pq16 || pq_dtype == PANGNN_DTYPE_F32, PANGNN_E_BADARG, "%s: pq_dtype is PANGNN_DTYPE_F32 / _BF16 / _F16", who);
   PG_CHECK_ARG(D == D16, PANGNN_E_BADARG, "%s: built for node_dim 64, got %d", who, (int)D);
@@ -1416,40 +1442,69 @@ extern "C" int pangnn_decoder_train_mixed(const void* p, int64_t ldp, const void
     hipError_t e = hipMemsetAsync(workspace, 0, (size_t)grid * SLAB16 * sizeof(float), s);
     PG_CHECK_ARG(e == hipSuccess, (int)e, "%s: memset failed", who);
   } else {
-    PG_CHECK_ARG(p && q && edge_index && w2 && b2 && w3 && b3 && (!extra || cvec), PANGNN_E_BADARG, "%s: null pointer",
-                 who);
+    PG_CHECK_ARG(p && q && (edge_index || spos) && w2 && b2 && w3 && b3 && (!extra || cvec), PANGNN_E_BADARG,
+                 "%s: null pointer", who);
     PG_CHECK_ARG(aligned16(p) && aligned16(q) && aligned16(w2), PANGNN_E_ALIGN, "%s: p / q / w2 must be 16-byte aligned",
                  who);
     PG_CHECK_ARG(rec && aligned16(rec), PANGNN_E_ALIGN, "%s: rec is required and must be 16-byte aligned", who);
     const uint32_t esz = pq16 ? 2u : 4u;
     D16Params a{p, q, (uint32_t)ldp * esz, (uint32_t)ldq * esz, edge_index, ld, num_edges, extra, cvec, w2, b2, w3, b3,
                 live_edges};
+    if (spos) {
+      // the STREAM instances take the position stream in `ei` (8 bytes per position, as an int64 id) and the row strides as
+      // shifts: word << shift is the row's byte offset and drops the close bit (a stride is >= 128 bytes)
+      PG_CHECK_ARG(part_buf && ((uintptr_t)spos & 7u) == 0, PANGNN_E_BADARG,
+                   "%s: spos must be 8-byte aligned and comes with part_buf / part_off", who);
+      PG_CHECK_ARG((a.ldp_b & (a.ldp_b - 1)) == 0 && (a.ldq_b & (a.ldq_b - 1)) == 0, PANGNN_E_BADARG,
+                   "%s: row strides in bytes must be powers of two (take pangnn_decoder_train_mixed otherwise)", who);
+      a.ei = reinterpret_cast<const int64_t*>(spos);
+      a.ld = 0;
+      a.ldp_b = (uint32_t)__builtin_ctz(a.ldp_b);
+      a.ldq_b = (uint32_t)__builtin_ctz(a.ldq_b);
+    }
+    const bool st = spos != nullptr;
     const D16Loss lp{y, pos_weight, y ? 1.0f / (float)denom : 0.f};
     const D16Run rs{part_buf, part_off, clog};
     const dim3 gd((unsigned)grid), bd(S_WAVES * 64);
-#define PG_S2(F, R, H)                                                                                              \
+#define PG_S2(F, R, H, S)                                                                                           \
   do {                                                                                                              \
     if (extra)                                                                                                      \
-      hipLaunchKernelGGL((decoder_train16_kernel<F, R, H, true>), gd, bd, 0, s, a, g_logits, lp, logits, rs, rec, ws, n_tiles);  \
+      hipLaunchKernelGGL((decoder_train16_kernel<F, R, H, true, S>), gd, bd, 0, s, a, g_logits, lp, logits, rs, rec, ws, n_tiles);  \
     else                                                                                                            \
-      hipLaunchKernelGGL((decoder_train16_kernel<F, R, H, false>), gd, bd, 0, s, a, g_logits, lp, logits, rs, rec, ws, n_tiles); \
+      hipLaunchKernelGGL((decoder_train16_kernel<F, R, H, false, S>), gd, bd, 0, s, a, g_logits, lp, logits, rs, rec, ws, n_tiles); \
   } while (0)
-#define PG_S(F, R, H) PG_S2(F, R, H)
+#define PG_S(F, R, H, S) PG_S2(F, R, H, S)
     if (pq_dtype == PANGNN_DTYPE_F16) {
-      launch_train16_tables_f16(a, g_logits, lp, logits, rs, rec, ws, n_tiles, (unsigned)grid, s);
+      launch_train16_tables_f16(a, g_logits, lp, logits, rs, rec, ws, n_tiles, (unsigned)grid, st, s);
     } else if (pq16) {
-      launch_train16_tables_bf16(a, g_logits, lp, logits, rs, rec, ws, n_tiles, (unsigned)grid, s);
+      launch_train16_tables_bf16(a, g_logits, lp, logits, rs, rec, ws, n_tiles, (unsigned)grid, st, s);
     } else {
-      if (y && part_buf) PG_S(true, true, false);
-      else if (y) PG_S(true, false, false);
-      else if (part_buf) PG_S(false, true, false);
-      else PG_S(false, false, false);
+      if (st && y) PG_S(true, true, false, true);
+      else if (st) PG_S(false, true, false, true);
+      else if (y && part_buf) PG_S(true, true, false, false);
+      else if (y) PG_S(true, false, false, false);
+      else if (part_buf) PG_S(false, true, false, false);
+      else PG_S(false, false, false, false);
     }
 #undef PG_S2
 #undef PG_S
     PG_CHECK_LAUNCH(who);
   }
   return launch_decoder_reduce(ws, (int)grid, g_w2, nullptr, g_w3, g_cvec, g_b3, loss, s);
+}
+
+extern "C" int pangnn_decoder_train_mixed(const void* p, int64_t ldp, const void* q, int64_t ldq, int32_t pq_dtype,
+                                          int64_t num_nodes, const int64_t* edge_index, int64_t ld, int64_t num_edges,
+                                          const float* extra, const float* cvec, const float* w2, const float* b2,
+                                          const float* w3, const float* b3, int32_t D, const float* y,
+                                          const float* pos_weight, int64_t denom, const float* g_logits, float* logits,
+                                          float* loss, uint32_t* rec, float* part_buf, const int32_t* part_off,
+                                          float* g_w2, float* g_w3, float* g_b3, float* g_cvec,
+                                          const int64_t* live_edges, void* workspace, size_t workspace_bytes,
+                                          pangnn_stream_t stream) {
+  return decoder_train_any("pangnn_decoder_train", p, ldp, q, ldq, pq_dtype, num_nodes, edge_index, ld, nullptr, num_edges,
+                           extra, cvec, w2, b2, w3, b3, D, y, pos_weight, denom, g_logits, logits, loss, rec, part_buf,
+                           part_off, g_w2, g_w3, g_b3, g_cvec, live_edges, workspace, workspace_bytes, stream);
 }
 
 extern "C" int pangnn_decoder_train_f32(const float* p, int64_t ldp, const float* q, int64_t ldq, int64_t num_nodes,
@@ -1463,6 +1518,37 @@ extern "C" int pangnn_decoder_train_f32(const float* p, int64_t ldp, const float
   return pangnn_decoder_train_mixed(p, ldp, q, ldq, PANGNN_DTYPE_F32, num_nodes, edge_index, ld, num_edges, extra, cvec,
                                     w2, b2, w3, b3, D, y, pos_weight, denom, g_logits, logits, loss, rec, part_buf,
                                     part_off, g_w2, g_w3, g_b3, g_cvec, live_edges, workspace, workspace_bytes, stream);
+}
+
+extern "C" int pangnn_decoder_train_stream_mixed(const void* p, int64_t ldp, const void* q, int64_t ldq, int32_t pq_dtype,
+                                                 int64_t num_nodes, const uint32_t* spos, int64_t num_edges,
+                                                 const float* extra, const float* cvec, const float* w2, const float* b2,
+                                                 const float* w3, const float* b3, int32_t D, const float* y,
+                                                 const float* pos_weight, int64_t denom, const float* g_logits,
+                                                 float* logits, float* loss, uint32_t* rec, float* part_buf,
+                                                 const int32_t* part_off, float* g_w2, float* g_w3, float* g_b3,
+                                                 float* g_cvec, void* workspace, int64_t workspace_bytes,
+                                                 pangnn_stream_t stream) {
+  const char* who = "pangnn_decoder_train_stream";
+  PG_CHECK_ARG(num_edges <= 0 || (spos && part_buf && part_off), PANGNN_E_BADARG,
+               "%s: spos, part_buf and part_off are required", who);
+  PG_CHECK_ARG(workspace_bytes >= 0, PANGNN_E_BADARG, "%s: negative workspace size", who);
+  return decoder_train_any(who, p, ldp, q, ldq, pq_dtype, num_nodes, nullptr, num_edges, num_edges > 0 ? spos : nullptr,
+                           num_edges, extra, cvec, w2, b2, w3, b3, D, y, pos_weight, denom, g_logits, logits, loss, rec,
+                           part_buf, part_off, g_w2, g_w3, g_b3, g_cvec, nullptr, workspace, (size_t)workspace_bytes, stream);
+}
+
+extern "C" int pangnn_decoder_train_stream_f32(const float* p, int64_t ldp, const float* q, int64_t ldq, int64_t num_nodes,
+                                               const uint32_t* spos, int64_t num_edges, const float* extra,
+                                               const float* cvec, const float* w2, const float* b2, const float* w3,
+                                               const float* b3, int32_t D, const float* y, const float* pos_weight,
+                                               int64_t denom, const float* g_logits, float* logits, float* loss,
+                                               uint32_t* rec, float* part_buf, const int32_t* part_off, float* g_w2,
+                                               float* g_w3, float* g_b3, float* g_cvec, void* workspace,
+                                               int64_t workspace_bytes, pangnn_stream_t stream) {
+  return pangnn_decoder_train_stream_mixed(p, ldp, q, ldq, PANGNN_DTYPE_F32, num_nodes, spos, num_edges, extra, cvec, w2, b2,
+                                           w3, b3, D, y, pos_weight, denom, g_logits, logits, loss, rec, part_buf, part_off,
+                                           g_w2, g_w3, g_b3, g_cvec, workspace, workspace_bytes, stream);
 }
 
 extern "C" size_t pangnn_decoder_dgrad_workspace_bytes(void) { return (size_t)cu_count() * 64 * sizeof(float); }

@@ -34,7 +34,8 @@ enum Need : int64_t {          // bits of pangnn::_prepare_structure(..., need);
 };
 
 struct Csr { at::Tensor rowptr, other, perm, seg_ptr, parts_rowptr; };     // seg_ptr / parts_rowptr: long rows (graph.CSR.long_rows)
-// tpos (by-target plans of the D16 chunk size only, may be undefined): the T kernel's position words (pangnn_csr_plan_tpos)
+// tpos (plans of the D16 chunk size only, may be undefined): the position words of the plan's order — a CSR order's [E] words of
+// the T kernel (pangnn_csr_plan_tpos), the run-sum plan's (kind 0) [P, 2] word pairs of the S kernel (pangnn_csr_plan_spos)
 struct Plan { at::Tensor part_off, part_rowptr, keys; int64_t n_parts = 0; at::Tensor tpos; };
 
 struct Ident {                 // identity of a tensor: storage (weak), address, version
@@ -179,7 +180,9 @@ void register_plan(const at::Tensor& edge_index, int64_t n_dst, int64_t kind, in
   at::Tensor words;
   if (tpos.has_value() && tpos->defined()) {
     operand("_register_plan", "tpos", *tpos, edge_index, at::kInt);
-    TORCH_CHECK(kind != 0 && tpos->size(0) == e, "pangnn::_register_plan: tpos [E] goes with the plan of a CSR order");
+    TORCH_CHECK(kind != 0 ? (tpos->dim() == 1 && tpos->size(0) == e)
+                          : (tpos->dim() == 2 && tpos->size(0) == (e + 31) / 32 * 32 && tpos->size(1) == 2 && tpos->is_contiguous()),
+                "pangnn::_register_plan: tpos is [E] for the plan of a CSR order, [32 ceil(E / 32), 2] for the run-sum plan");
     words = *tpos;
   }
   std::lock_guard<std::mutex> lock(g_mu);
@@ -704,17 +707,34 @@ DecGrads decoder_train(const char* op, const DecIn& in, const at::Tensor& edge_i
   const auto yy = f32c(y), gl = f32c(g_logits);
   c10::optional<at::Tensor> pw;
   if (defined(pos_weight)) pw = f32c(*pos_weight).reshape({-1});
-  check_rc(pangnn_decoder_train_mixed(in.p(), in.pq.stride(0), in.q(), in.pq.stride(0), dtype_code(in.pq), n,
-                                      v.ei.data_ptr<int64_t>(), e, e, opt_ptr<float>(in.ex), opt_ptr<float>(in.cv),
-                                      in.w2.data_ptr<float>(), in.b2.data_ptr<float>(), in.w3.data_ptr<float>(), in.b3.data_ptr<float>(),
-                                      (int32_t)d, opt_ptr<float>(yy), opt_ptr<float>(pw), denom, opt_ptr<float>(gl),
-                                      fused ? r.logits.data_ptr<float>() : nullptr, fused ? r.loss.data_ptr<float>() : nullptr,
-                                      reinterpret_cast<uint32_t*>(rec.data_ptr<int32_t>()), runs ? parts.data_ptr<float>() : nullptr,
-                                      runs ? v.runsum.part_off.data_ptr<int32_t>() : nullptr, r.g_w2.data_ptr<float>(),
-                                      r.g_w3.data_ptr<float>(), r.g_b3.data_ptr<float>(),
-                                      defined(in.cv) ? r.g_cv.data_ptr<float>() : nullptr, opt_ptr<int64_t>(live), ws.data_ptr(), wsb,
-                                      stream_of(in.pq)),
-           "pangnn_decoder_train_mixed");
+  uint32_t* recp = reinterpret_cast<uint32_t*>(rec.data_ptr<int32_t>());
+  const int64_t ld_b = in.pq.stride(0) * in.pq.element_size();
+  if (runs && v.runsum.tpos.defined() && !defined(live) && (ld_b & (ld_b - 1)) == 0) {
+    // the run-sum plan carries the list as one word pair per position (built once per graph): the stream route of S
+    check_rc(pangnn_decoder_train_stream_mixed(in.p(), in.pq.stride(0), in.q(), in.pq.stride(0), dtype_code(in.pq), n,
+                                               reinterpret_cast<const uint32_t*>(v.runsum.tpos.data_ptr<int32_t>()), e,
+                                               opt_ptr<float>(in.ex), opt_ptr<float>(in.cv), in.w2.data_ptr<float>(),
+                                               in.b2.data_ptr<float>(), in.w3.data_ptr<float>(), in.b3.data_ptr<float>(), (int32_t)d,
+                                               opt_ptr<float>(yy), opt_ptr<float>(pw), denom, opt_ptr<float>(gl),
+                                               fused ? r.logits.data_ptr<float>() : nullptr, fused ? r.loss.data_ptr<float>() : nullptr,
+                                               recp, parts.data_ptr<float>(), v.runsum.part_off.data_ptr<int32_t>(),
+                                               r.g_w2.data_ptr<float>(), r.g_w3.data_ptr<float>(), r.g_b3.data_ptr<float>(),
+                                               defined(in.cv) ? r.g_cv.data_ptr<float>() : nullptr, ws.data_ptr(), (int64_t)wsb,
+                                               stream_of(in.pq)),
+             "pangnn_decoder_train_stream_mixed");
+  } else {
+    check_rc(pangnn_decoder_train_mixed(in.p(), in.pq.stride(0), in.q(), in.pq.stride(0), dtype_code(in.pq), n,
+                                        v.ei.data_ptr<int64_t>(), e, e, opt_ptr<float>(in.ex), opt_ptr<float>(in.cv),
+                                        in.w2.data_ptr<float>(), in.b2.data_ptr<float>(), in.w3.data_ptr<float>(), in.b3.data_ptr<float>(),
+                                        (int32_t)d, opt_ptr<float>(yy), opt_ptr<float>(pw), denom, opt_ptr<float>(gl),
+                                        fused ? r.logits.data_ptr<float>() : nullptr, fused ? r.loss.data_ptr<float>() : nullptr,
+                                        recp, runs ? parts.data_ptr<float>() : nullptr,
+                                        runs ? v.runsum.part_off.data_ptr<int32_t>() : nullptr, r.g_w2.data_ptr<float>(),
+                                        r.g_w3.data_ptr<float>(), r.g_b3.data_ptr<float>(),
+                                        defined(in.cv) ? r.g_cv.data_ptr<float>() : nullptr, opt_ptr<int64_t>(live), ws.data_ptr(), wsb,
+                                        stream_of(in.pq)),
+             "pangnn_decoder_train_mixed");
+  }
   if (layer) {
     r.g_z = at::empty({n, d}, fo);
     r.g_wpq = at::empty({2 * d, d}, fo);

@@ -679,13 +679,19 @@ def _decoder_train16(p, q, st: EdgeStructure, ex, cv, w2, b2, w3, b3, y=None, pw
     if p.dtype != q.dtype:
         raise ValueError("p and q must be stored alike (both float32, both bfloat16 or both float16)")
     ws, ws_bytes = _workspace(dev, "pangnn_decoder_train")
-    _launch(dev, "pangnn_decoder_train_mixed",
-            p.data_ptr(), p.stride(0), q.data_ptr(), q.stride(0), _dt(p), max(p.shape[0], q.shape[0]),
-            st.edge_index.data_ptr(), e, e, _lib.ptr(ex), _lib.ptr(cv), w2.data_ptr(), b2.data_ptr(), w3.data_ptr(),
-            b3.data_ptr(), d, _lib.ptr(y), _lib.ptr(pw), int(denom), _lib.ptr(g_logits), _lib.ptr(logits),
-            _lib.ptr(loss), rec.data_ptr(), _lib.ptr(parts), None if plan is None else plan.part_off.data_ptr(),
-            g_w2.data_ptr(), g_w3.data_ptr(), g_b3.data_ptr(), _lib.ptr(g_cv), _lib.ptr(live), ws.data_ptr(), ws_bytes,
-            tag="dec.bwd")
+    esz = p.element_size()
+    pow2 = all(n > 0 and n & (n - 1) == 0 for n in (p.stride(0) * esz, q.stride(0) * esz))
+    spos = None if (plan is None or live is not None or not pow2) else getattr(plan, "spos", None)
+    head = (p.data_ptr(), p.stride(0), q.data_ptr(), q.stride(0), _dt(p), max(p.shape[0], q.shape[0]))
+    tail = (_lib.ptr(ex), _lib.ptr(cv), w2.data_ptr(), b2.data_ptr(), w3.data_ptr(), b3.data_ptr(), d, _lib.ptr(y), _lib.ptr(pw),
+            int(denom), _lib.ptr(g_logits), _lib.ptr(logits), _lib.ptr(loss), rec.data_ptr(), _lib.ptr(parts),
+            None if plan is None else plan.part_off.data_ptr(), g_w2.data_ptr(), g_w3.data_ptr(), g_b3.data_ptr(), _lib.ptr(g_cv))
+    if spos is not None:          # the plan carries the list as one word pair per position: the stream route of S
+        _launch(dev, "pangnn_decoder_train_stream_mixed", *head, spos.data_ptr(), e, *tail, ws.data_ptr(), ws_bytes,
+                tag="dec.bwd")
+    else:
+        _launch(dev, "pangnn_decoder_train_mixed", *head, st.edge_index.data_ptr(), e, e, *tail, _lib.ptr(live),
+                ws.data_ptr(), ws_bytes, tag="dec.bwd")
     gp = gq = None
     b2_out = g_b2          # dL/db2 comes out of exactly one dgrad call
     if need_p:

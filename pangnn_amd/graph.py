@@ -416,6 +416,21 @@ class EdgeStructure:
         plan.n_parts_exact = lambda: int(plan._last) + 1
         return plan
 
+    @staticmethod
+    def _spos_of_sorted_list(edge_index: torch.Tensor, chunk_tiles: int) -> torch.Tensor:
+        """The S pass's position stream of a source-sorted device list (pangnn_csr_plan_spos): [P, 2] int32 (read as uint32)
+        for the P = 32 ceil(E / 32) positions of whole tiles, { src | closes << 31, dst } with closes = "a part ends behind
+        this position"; a position past the list repeats the last edge.  What pangnn_decoder_train_stream_* walks instead of
+        the int64 ids."""
+        lib = _lib.load()
+        e = edge_index.shape[1]
+        ei = edge_index if edge_index.stride(1) == 1 else edge_index.contiguous()
+        spos = torch.empty((e + 31) // 32 * 32, 2, dtype=torch.int32, device=ei.device)
+        with _lib.device_guard(ei.device):
+            _lib.check(lib.pangnn_csr_plan_spos(ei.data_ptr(), ei.stride(0), e, 32 * int(chunk_tiles), spos.data_ptr(),
+                                                _lib.stream_ptr()), "pangnn_csr_plan_spos")
+        return spos
+
     def csr_plan(self, by: str, chunk_tiles: int = 1):
         """run-sum plan of the CSR order `by` in {"dst", "src"} (pangnn_decoder_dgrad_f32: perm = that CSR's perm)"""
         cache = self.__dict__.setdefault("_csr_plans", {})
@@ -462,7 +477,14 @@ class EdgeStructure:
                 else:
                     src = self.edge_index[0]
                     rowptr = torch.searchsorted(src, torch.arange(self.num_src + 1, device=src.device, dtype=src.dtype))
-                self._runsum[ct] = self._plan_of_rowptr(rowptr, self.num_edges, ct)
+                plan = self._runsum[ct] = self._plan_of_rowptr(rowptr, self.num_edges, ct)
+                # a square structure's plan at the S kernel's chunk size also carries S's position stream (8 more bytes per
+                # edge kept); every other plan (a shard's rectangular structure, the strict-fp32 kernels' one-tile chunks of a
+                # long list, the small build, the index-op route, and a filtered child, whose list lives for one step: building
+                # its stream would cost more than S saves on it) has none and S reads the int64 ids
+                if self.num_src == self.num_nodes and getattr(self, "filter_state", None) is None and \
+                        ct == int(_lib.load().pangnn_decoder_chunk_tiles_for(self.num_edges)):
+                    plan.spos = self._spos_of_sorted_list(self.edge_index, ct)
             else:
                 self._runsum[ct] = self._plan_of_sorted_keys(self.edge_index[0], self.num_src, ct)
         return self._runsum[ct]
@@ -511,7 +533,8 @@ class EdgeStructure:
                 srt = 0 if plan is None else 1
             ops._register_structure(ei, n, self.num_src, self.edge_index, by_dst, by_src, band, srt)
             if plan is not None:
-                ops._register_plan(ei, n, 0, ct, plan.part_off, plan.part_rowptr, plan.keys, int(plan.n_parts))
+                ops._register_plan(ei, n, 0, ct, plan.part_off, plan.part_rowptr, plan.keys, int(plan.n_parts),
+                                   getattr(plan, "spos", None))
             have |= todo | NEED_ENTRY
         for bit, by, kind in ((NEED_PLAN_DST, "dst", 1), (NEED_PLAN_SRC, "src", 2)):
             if need & bit & ~have:
