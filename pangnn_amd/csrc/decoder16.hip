@@ -1288,34 +1288,46 @@ __global__ __launch_bounds__(I_WAVES * 64) void decoder_infer16_kernel(D16Params
 // host side
 // ------------------------------------------------------------------------------------------------------------------
 namespace pangnn {
-// launchers of the PQ16 instances (2-byte tables): launch_train16_tables_bf16 / launch_infer16_tables_bf16 in decoder16.o,
-// ..._f16 in decoder16_f16.o.  `a` carries the row strides in bytes; y / part_buf / extra select the instance.
+// The instance ladders, stated once for both table widths (PQ16: 2-byte tables).  `a` carries the row strides in bytes; the
+// fused loss (lp.y), the run sums (rs.part), the stream route — which comes with run sums (decoder_train_any) — and the skip
+// feature (a.extra) select the instance.  `static`: the two translation units' <true> launch differently named kernels.
+template <bool PQ16>
+static int launch_train16(const D16Params& a, const float* g_logits, const D16Loss& lp, float* logits, const D16Run& rs,
+                          uint32_t* rec, float* ws, int64_t n_tiles, unsigned grid, bool stream, hipStream_t s) {
+  const dim3 gd(grid), bd(S_WAVES * 64);
+#define PG_S(F, R, S)                                                                                                 \
+  do {                                                                                                                \
+    if (a.extra)                                                                                                      \
+      hipLaunchKernelGGL((decoder_train16_kernel<F, R, PQ16, true, S>), gd, bd, 0, s, a, g_logits, lp, logits, rs, rec, ws, n_tiles);   \
+    else                                                                                                              \
+      hipLaunchKernelGGL((decoder_train16_kernel<F, R, PQ16, false, S>), gd, bd, 0, s, a, g_logits, lp, logits, rs, rec, ws, n_tiles);  \
+  } while (0)
+  if (stream && lp.y) PG_S(true, true, true);
+  else if (stream) PG_S(false, true, true);
+  else if (lp.y && rs.part) PG_S(true, true, false);
+  else if (lp.y) PG_S(true, false, false);
+  else if (rs.part) PG_S(false, true, false);
+  else PG_S(false, false, false);
+#undef PG_S
+  return 0;
+}
+template <bool PQ16>
+static int launch_infer16(const D16Params& a, float* logits, int64_t n_tiles, unsigned grid, hipStream_t s) {
+  if (a.extra)
+    hipLaunchKernelGGL((decoder_infer16_kernel<PQ16, true>), dim3(grid), dim3(I_WAVES * 64), 0, s, a, logits, n_tiles);
+  else
+    hipLaunchKernelGGL((decoder_infer16_kernel<PQ16, false>), dim3(grid), dim3(I_WAVES * 64), 0, s, a, logits, n_tiles);
+  return 0;
+}
+// launchers of the PQ16 instances: launch_train16_tables_bf16 / launch_infer16_tables_bf16 in decoder16.o, ..._f16 in
+// decoder16_f16.o
 int D16_TABLES16(launch_train16_tables)(const D16Params& a, const float* g_logits, const D16Loss& lp, float* logits,
                                         const D16Run& rs, uint32_t* rec, float* ws, int64_t n_tiles, unsigned grid,
                                         bool stream, hipStream_t s) {
-  const dim3 gd(grid), bd(S_WAVES * 64);
-#define PG_S16(F, R, S)                                                                                               \
-  do {                                                                                                                \
-    if (a.extra)                                                                                                      \
-      hipLaunchKernelGGL((decoder_train16_kernel<F, R, true, true, S>), gd, bd, 0, s, a, g_logits, lp, logits, rs, rec, ws, n_tiles);   \
-    else                                                                                                              \
-      hipLaunchKernelGGL((decoder_train16_kernel<F, R, true, false, S>), gd, bd, 0, s, a, g_logits, lp, logits, rs, rec, ws, n_tiles);  \
-  } while (0)
-  if (stream && lp.y) PG_S16(true, true, true);            // the stream route comes with run sums (decoder_train_any)
-  else if (stream) PG_S16(false, true, true);
-  else if (lp.y && rs.part) PG_S16(true, true, false);
-  else if (lp.y) PG_S16(true, false, false);
-  else if (rs.part) PG_S16(false, true, false);
-  else PG_S16(false, false, false);
-#undef PG_S16
-  return 0;
+  return launch_train16<true>(a, g_logits, lp, logits, rs, rec, ws, n_tiles, grid, stream, s);
 }
 int D16_TABLES16(launch_infer16_tables)(const D16Params& a, float* logits, int64_t n_tiles, unsigned grid, hipStream_t s) {
-  if (a.extra)
-    hipLaunchKernelGGL((decoder_infer16_kernel<true, true>), dim3(grid), dim3(I_WAVES * 64), 0, s, a, logits, n_tiles);
-  else
-    hipLaunchKernelGGL((decoder_infer16_kernel<true, false>), dim3(grid), dim3(I_WAVES * 64), 0, s, a, logits, n_tiles);
-  return 0;
+  return launch_infer16<true>(a, logits, n_tiles, grid, s);
 }
 }  // namespace pangnn
 
@@ -1357,11 +1369,9 @@ static int launch_infer16_any(const void* p, int64_t ldp, const void* q, int64_t
   const uint32_t esz = pq_fmt ? 2u : 4u;                 // pq_fmt: PANGNN_DTYPE_F32 / _BF16 / _F16
   D16Params a{p, q, (uint32_t)ldp * esz, (uint32_t)ldq * esz, edge_index, ld, num_edges, extra, cvec, w2, b2, w3, b3,
               nullptr};
-#define PG_I(H, X) hipLaunchKernelGGL((decoder_infer16_kernel<H, X>), dim3((unsigned)grid), dim3(I_WAVES * 64), 0, s, a, logits, n_tiles)
   if (pq_fmt == PANGNN_DTYPE_F16) launch_infer16_tables_f16(a, logits, n_tiles, (unsigned)grid, s);
   else if (pq_fmt) launch_infer16_tables_bf16(a, logits, n_tiles, (unsigned)grid, s);
-  else { if (extra) PG_I(false, true); else PG_I(false, false); }
-#undef PG_I
+  else launch_infer16<false>(a, logits, n_tiles, (unsigned)grid, s);
   PG_CHECK_LAUNCH("pangnn_decoder_mlp_infer");
   return 0;
 }
@@ -1465,29 +1475,9 @@ static int decoder_train_any(const char* who, const void* p, int64_t ldp, const 
     const bool st = spos != nullptr;
     const D16Loss lp{y, pos_weight, y ? 1.0f / (float)denom : 0.f};
     const D16Run rs{part_buf, part_off, clog};
-    const dim3 gd((unsigned)grid), bd(S_WAVES * 64);
-#define PG_S2(F, R, H, S)                                                                                           \
-  do {                                                                                                              \
-    if (extra)                                                                                                      \
-      hipLaunchKernelGGL((decoder_train16_kernel<F, R, H, true, S>), gd, bd, 0, s, a, g_logits, lp, logits, rs, rec, ws, n_tiles);  \
-    else                                                                                                            \
-      hipLaunchKernelGGL((decoder_train16_kernel<F, R, H, false, S>), gd, bd, 0, s, a, g_logits, lp, logits, rs, rec, ws, n_tiles); \
-  } while (0)
-#define PG_S(F, R, H, S) PG_S2(F, R, H, S)
-    if (pq_dtype == PANGNN_DTYPE_F16) {
-      launch_train16_tables_f16(a, g_logits, lp, logits, rs, rec, ws, n_tiles, (unsigned)grid, st, s);
-    } else if (pq16) {
-      launch_train16_tables_bf16(a, g_logits, lp, logits, rs, rec, ws, n_tiles, (unsigned)grid, st, s);
-    } else {
-      if (st && y) PG_S(true, true, false, true);
-      else if (st) PG_S(false, true, false, true);
-      else if (y && part_buf) PG_S(true, true, false, false);
-      else if (y) PG_S(true, false, false, false);
-      else if (part_buf) PG_S(false, true, false, false);
-      else PG_S(false, false, false, false);
-    }
-#undef PG_S2
-#undef PG_S
+    if (pq_dtype == PANGNN_DTYPE_F16) launch_train16_tables_f16(a, g_logits, lp, logits, rs, rec, ws, n_tiles, (unsigned)grid, st, s);
+    else if (pq16) launch_train16_tables_bf16(a, g_logits, lp, logits, rs, rec, ws, n_tiles, (unsigned)grid, st, s);
+    else launch_train16<false>(a, g_logits, lp, logits, rs, rec, ws, n_tiles, (unsigned)grid, st, s);
     PG_CHECK_LAUNCH(who);
   }
   return launch_decoder_reduce(ws, (int)grid, g_w2, nullptr, g_w3, g_cvec, g_b3, loss, s);

@@ -34,9 +34,15 @@ enum Need : int64_t {          // bits of pangnn::_prepare_structure(..., need);
 };
 
 struct Csr { at::Tensor rowptr, other, perm, seg_ptr, parts_rowptr; };     // seg_ptr / parts_rowptr: long rows (graph.CSR.long_rows)
-// tpos (plans of the D16 chunk size only, may be undefined): the position words of the plan's order — a CSR order's [E] words of
-// the T kernel (pangnn_csr_plan_tpos), the run-sum plan's (kind 0) [P, 2] word pairs of the S kernel (pangnn_csr_plan_spos)
-struct Plan { at::Tensor part_off, part_rowptr, keys; int64_t n_parts = 0; at::Tensor tpos; };
+// graph.RunPlan; stream (may be undefined): the position words of the plan's order — a CSR order's [E] words of the T kernel
+// (pangnn_csr_plan_tpos), the run-sum plan's (kind 0) [P, 2] word pairs of the S kernel (pangnn_csr_plan_spos)
+struct Plan { at::Tensor part_off, part_rowptr, keys; int64_t n_parts = 0; at::Tensor stream; };
+// which calls walk the stream instead of the ids (functional._t_stream / _s_stream): the plan carries one and no `live` list is
+// given; S also takes the table's row stride in bytes as a shift, so it must be a power of two
+inline bool t_stream(const Plan* plan, const c10::optional<at::Tensor>& live) { return plan && plan->stream.defined() && !defined(live); }
+inline bool s_stream(const Plan* plan, const c10::optional<at::Tensor>& live, int64_t ld_bytes) {
+  return t_stream(plan, live) && (ld_bytes & (ld_bytes - 1)) == 0;
+}
 
 struct Ident {                 // identity of a tensor: storage (weak), address, version
   c10::optional<c10::weak_intrusive_ptr<c10::StorageImpl>> storage;
@@ -168,7 +174,7 @@ void register_structure(const at::Tensor& edge_index, int64_t n_dst, int64_t n_s
 
 void register_plan(const at::Tensor& edge_index, int64_t n_dst, int64_t kind, int64_t chunk_tiles, const at::Tensor& part_off,
                    const at::Tensor& part_rowptr, const at::Tensor& keys, int64_t n_parts,
-                   const c10::optional<at::Tensor>& tpos) {
+                   const c10::optional<at::Tensor>& stream) {
   check_edge_index("_register_plan", edge_index);
   TORCH_CHECK(kind >= 0 && kind <= 2 && chunk_tiles >= 1 && n_parts >= 0, "pangnn::_register_plan: bad kind / chunk size");
   operand("_register_plan", "part_off", part_off, edge_index, at::kInt);
@@ -178,12 +184,12 @@ void register_plan(const at::Tensor& edge_index, int64_t n_dst, int64_t kind, in
   TORCH_CHECK(keys.size(0) == e && part_off.size(0) >= (e + span - 1) / span, "pangnn::_register_plan: keys [E] and one part "
               "offset per chunk of ", span, " edges");
   at::Tensor words;
-  if (tpos.has_value() && tpos->defined()) {
-    operand("_register_plan", "tpos", *tpos, edge_index, at::kInt);
-    TORCH_CHECK(kind != 0 ? (tpos->dim() == 1 && tpos->size(0) == e)
-                          : (tpos->dim() == 2 && tpos->size(0) == (e + 31) / 32 * 32 && tpos->size(1) == 2 && tpos->is_contiguous()),
-                "pangnn::_register_plan: tpos is [E] for the plan of a CSR order, [32 ceil(E / 32), 2] for the run-sum plan");
-    words = *tpos;
+  if (stream.has_value() && stream->defined()) {
+    operand("_register_plan", "stream", *stream, edge_index, at::kInt);
+    TORCH_CHECK(kind != 0 ? (stream->dim() == 1 && stream->size(0) == e)
+                          : (stream->dim() == 2 && stream->size(0) == (e + 31) / 32 * 32 && stream->size(1) == 2 && stream->is_contiguous()),
+                "pangnn::_register_plan: stream is [E] for the plan of a CSR order, [32 ceil(E / 32), 2] for the run-sum plan");
+    words = *stream;
   }
   std::lock_guard<std::mutex> lock(g_mu);
   Entry* en = find_locked(edge_index, n_dst);
@@ -637,9 +643,9 @@ void dgrad_sum(const at::Tensor& rec, const View& v, int by /* 1 dst, 2 src, 0 n
     ws = bytes(wsb, in.w2);
   }
   const uint32_t* recp = reinterpret_cast<const uint32_t*>(rec.data_ptr<int32_t>());
-  if (plan && plan->tpos.defined() && !defined(live)) {
+  if (t_stream(plan, live)) {
     // the plan carries the order as one word per position (built once per graph): the stream route of T
-    check_rc(pangnn_decoder_dgrad_stream_f32(recp, reinterpret_cast<const uint32_t*>(plan->tpos.data_ptr<int32_t>()),
+    check_rc(pangnn_decoder_dgrad_stream_f32(recp, reinterpret_cast<const uint32_t*>(plan->stream.data_ptr<int32_t>()),
                                              in.w2.data_ptr<float>(), in.w3.data_ptr<float>(), v.num_edges, parts.data_ptr<float>(),
                                              plan->part_off.data_ptr<int32_t>(), g_b2 ? g_b2->data_ptr<float>() : nullptr,
                                              g_b2 ? ws.data_ptr() : nullptr, (int64_t)wsb, stream_of(rec)),
@@ -708,11 +714,10 @@ DecGrads decoder_train(const char* op, const DecIn& in, const at::Tensor& edge_i
   c10::optional<at::Tensor> pw;
   if (defined(pos_weight)) pw = f32c(*pos_weight).reshape({-1});
   uint32_t* recp = reinterpret_cast<uint32_t*>(rec.data_ptr<int32_t>());
-  const int64_t ld_b = in.pq.stride(0) * in.pq.element_size();
-  if (runs && v.runsum.tpos.defined() && !defined(live) && (ld_b & (ld_b - 1)) == 0) {
+  if (s_stream(runs ? &v.runsum : nullptr, live, in.pq.stride(0) * in.pq.element_size())) {
     // the run-sum plan carries the list as one word pair per position (built once per graph): the stream route of S
     check_rc(pangnn_decoder_train_stream_mixed(in.p(), in.pq.stride(0), in.q(), in.pq.stride(0), dtype_code(in.pq), n,
-                                               reinterpret_cast<const uint32_t*>(v.runsum.tpos.data_ptr<int32_t>()), e,
+                                               reinterpret_cast<const uint32_t*>(v.runsum.stream.data_ptr<int32_t>()), e,
                                                opt_ptr<float>(in.ex), opt_ptr<float>(in.cv), in.w2.data_ptr<float>(),
                                                in.b2.data_ptr<float>(), in.w3.data_ptr<float>(), in.b3.data_ptr<float>(), (int32_t)d,
                                                opt_ptr<float>(yy), opt_ptr<float>(pw), denom, opt_ptr<float>(gl),
@@ -1382,7 +1387,7 @@ TORCH_LIBRARY_FRAGMENT(pangnn, m) {
   m.def("_register_structure(Tensor edge_index, int n_dst, int n_src, Tensor ei_contig, Tensor[] by_dst, Tensor[] by_src, int band, "
         "int sorted_by_src) -> ()");
   m.def("_register_plan(Tensor edge_index, int n_dst, int kind, int chunk_tiles, Tensor part_off, Tensor part_rowptr, Tensor keys, "
-        "int n_parts, Tensor? tpos=None) -> ()");
+        "int n_parts, Tensor? stream=None) -> ()");
   m.def("_register_norm(Tensor edge_index, int n_dst, Tensor? weight, Tensor dis, Tensor by_dst, Tensor orig, Tensor? by_src) -> ()");
   m.def("_register_actions(Tensor edge_index, int n_dst, Tensor? weight, Tensor x, Tensor r, Tensor s) -> ()");
   m.def("_prepare_structure(Tensor edge_index, int n_dst, Tensor? edge_weight, Tensor? x, int need) -> ()");

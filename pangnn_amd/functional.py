@@ -611,6 +611,17 @@ def _sum_parts(plan, part_buf: torch.Tensor, n_rows: int, out: torch.Tensor, acc
     return out
 
 
+def _t_stream(plan, live):
+    """the words T walks instead of the order's perm and keys, or None: the plan carries a stream and no `live` list is given"""
+    return None if (plan is None or live is not None) else plan.stream
+
+
+def _s_stream(plan, live, p, q):
+    """the word pairs S walks instead of the int64 ids, or None: as T, and both row strides in bytes are powers of two"""
+    pow2 = all(n > 0 and n & (n - 1) == 0 for n in (p.stride(0) * p.element_size(), q.stride(0) * q.element_size()))
+    return _t_stream(plan, live) if pow2 else None
+
+
 def _dgrad_sum(rec, st: EdgeStructure, by: Optional[str], w2, w3, n_rows: int = 0, out=None, g_b2=None, live=None,
                accumulate: bool = False, raw_parts: bool = False):
     """dL/dh1 summed over the rows of CSR order `by` ("src" / "dst") from the per-edge records of the training
@@ -622,9 +633,9 @@ def _dgrad_sum(rec, st: EdgeStructure, by: Optional[str], w2, w3, n_rows: int = 
     csr = None if not by else (st.by_dst if by == "dst" else st.by_src)
     parts = None if plan is None else torch.empty(plan.n_parts, 64, dtype=torch.float32, device=dev)
     ws, ws_bytes = _workspace(dev, "pangnn_decoder_dgrad") if g_b2 is not None else (None, 0)
-    tpos = None if (plan is None or live is not None) else getattr(plan, "tpos", None)
-    if tpos is not None:          # the plan carries the order as one word per position: the stream route of T
-        _launch(dev, "pangnn_decoder_dgrad_stream_f32", rec.data_ptr(), tpos.data_ptr(), w2.data_ptr(), w3.data_ptr(),
+    words = _t_stream(plan, live)
+    if words is not None:         # the plan carries the order as one word per position: the stream route of T
+        _launch(dev, "pangnn_decoder_dgrad_stream_f32", rec.data_ptr(), words.data_ptr(), w2.data_ptr(), w3.data_ptr(),
                 st.num_edges, _lib.ptr(parts), plan.part_off.data_ptr(), _lib.ptr(g_b2), _lib.ptr(ws), ws_bytes, tag="dec.dgrad")
     else:
         _launch(dev, "pangnn_decoder_dgrad_f32", rec.data_ptr(), None if csr is None else _lib.ptr(csr.perm),
@@ -679,15 +690,13 @@ def _decoder_train16(p, q, st: EdgeStructure, ex, cv, w2, b2, w3, b3, y=None, pw
     if p.dtype != q.dtype:
         raise ValueError("p and q must be stored alike (both float32, both bfloat16 or both float16)")
     ws, ws_bytes = _workspace(dev, "pangnn_decoder_train")
-    esz = p.element_size()
-    pow2 = all(n > 0 and n & (n - 1) == 0 for n in (p.stride(0) * esz, q.stride(0) * esz))
-    spos = None if (plan is None or live is not None or not pow2) else getattr(plan, "spos", None)
+    words = _s_stream(plan, live, p, q)
     head = (p.data_ptr(), p.stride(0), q.data_ptr(), q.stride(0), _dt(p), max(p.shape[0], q.shape[0]))
     tail = (_lib.ptr(ex), _lib.ptr(cv), w2.data_ptr(), b2.data_ptr(), w3.data_ptr(), b3.data_ptr(), d, _lib.ptr(y), _lib.ptr(pw),
             int(denom), _lib.ptr(g_logits), _lib.ptr(logits), _lib.ptr(loss), rec.data_ptr(), _lib.ptr(parts),
             None if plan is None else plan.part_off.data_ptr(), g_w2.data_ptr(), g_w3.data_ptr(), g_b3.data_ptr(), _lib.ptr(g_cv))
-    if spos is not None:          # the plan carries the list as one word pair per position: the stream route of S
-        _launch(dev, "pangnn_decoder_train_stream_mixed", *head, spos.data_ptr(), e, *tail, ws.data_ptr(), ws_bytes,
+    if words is not None:         # the plan carries the list as one word pair per position: the stream route of S
+        _launch(dev, "pangnn_decoder_train_stream_mixed", *head, words.data_ptr(), e, *tail, ws.data_ptr(), ws_bytes,
                 tag="dec.bwd")
     else:
         _launch(dev, "pangnn_decoder_train_mixed", *head, st.edge_index.data_ptr(), e, e, *tail, _lib.ptr(live),

@@ -11,7 +11,8 @@ GPU (stable radix sort => deterministic per-row order) and memoises the GCN norm
 from __future__ import annotations
 
 import os
-from dataclasses import dataclass
+from dataclasses import dataclass, field
+from operator import attrgetter
 from typing import Dict, Optional, Tuple
 
 import torch
@@ -63,13 +64,19 @@ class CSR:
     rowptr: torch.Tensor   # int64 [N+1]
     other: torch.Tensor    # int32 [E]  opposite endpoint of each sorted edge
     perm: torch.Tensor     # int32 [E]  original edge id of each sorted edge
+    _long: object = field(default=None, repr=False, compare=False)      # long_rows' answer: None undecided, False short rows
+
+    def mark_short(self) -> "CSR":
+        """the producer vouches that no row exceeds LONG_ROW: long_rows() answers None without reading the rows"""
+        self._long = False
+        return self
 
     def long_rows(self, known_short: bool = False):
         """None, or (seg_ptr int64 [V + 1], parts_rowptr int64 [N + 1]) when the longest row exceeds LONG_ROW: segment v covers
         entries [seg_ptr[v], seg_ptr[v + 1]), the segments of row r are [parts_rowptr[r], parts_rowptr[r + 1]) (every row has
         at least one).  Decided once per CSR (one host read-back of the longest row, none for structures whose producer
         vouches for short rows: `known_short`)."""
-        hit = self.__dict__.get("_long")
+        hit = self._long
         if hit is None:
             hit = False
             n = self.rowptr.shape[0] - 1
@@ -85,8 +92,39 @@ class CSR:
                     j = torch.arange(row_of.shape[0], device=lens.device) - parts_rowptr[row_of]
                     seg_ptr = torch.cat([self.rowptr[row_of] + j * seg, self.rowptr[-1:]]).contiguous()
                     hit = (seg_ptr, parts_rowptr)
-            self.__dict__["_long"] = hit
+            self._long = hit
         return hit or None
+
+
+@dataclass
+class RunPlan:
+    """Layout of the per-(chunk, key) part rows of an edge order with non-decreasing keys; a chunk is `chunk_tiles` consecutive
+    32-edge tiles.  part_off[c] (int32): index of chunk c's first part; the parts of row r are [part_rowptr[r],
+    part_rowptr[r + 1]) (int64; consecutive: sorted); keys: the int32 [E] copy handed to the kernels; n_parts: an upper bound
+    (what the part buffer is sized by, no read-back); last: device int64[1], the index of the last part.
+    `stream` (where EdgeStructure._streams says so): the order as int32 words, read as uint32, that a decoder pass walks
+    instead of the ids; bit 31 of a position's first word = "a part ends behind this position".  A CSR-order plan: [E] words
+    perm[p] | closes << 31 (pangnn_csr_plan_tpos -> pangnn_decoder_dgrad_stream_f32).  The run-sum plan: [32 ceil(E / 32), 2]
+    pairs { src | closes << 31, dst }, a position past the list repeating the last edge (pangnn_csr_plan_spos ->
+    pangnn_decoder_train_stream_*)."""
+    n_parts: int
+    part_off: torch.Tensor
+    part_rowptr: torch.Tensor
+    keys: torch.Tensor
+    chunk_tiles: int
+    last: torch.Tensor
+    stream: Optional[torch.Tensor] = None
+
+    def n_parts_exact(self) -> int:           # the one device -> host read-back of a plan (bench accounting)
+        return int(self.last) + 1
+
+    # The names these fields had on the untyped plans (`spos` on a run-sum plan, `tpos` on a by-target plan, `_last`), kept
+    # for callers outside the package (the streams writable too); nothing inside it uses them.
+    def _set_stream(self, words: Optional[torch.Tensor]):
+        self.stream = words
+
+    spos = tpos = property(attrgetter("stream"), _set_stream)
+    _last = property(attrgetter("last"))
 
 
 def build_csr(edge_index: torch.Tensor, num_nodes: int, group_by: int, validate: bool = True,
@@ -144,9 +182,12 @@ class EdgeStructure:
         self._by_dst: Optional[CSR] = None
         self._by_src: Optional[CSR] = None
         self._norm: Dict[Tuple, Tuple["GcnNorm", Optional[torch.Tensor]]] = {}
-        self._runsum = None
+        self._sorted: Optional[bool] = None  # sorted_by_src's answer
+        # by ("run" | "dst" | "src", chunk_tiles): the run-sum plan of a source-sorted list, the plans of the CSR orders
+        self._plans: Dict[Tuple[str, int], Optional[RunPlan]] = {}
         self._band: Optional[int] = None
         self._small_built = False
+        self.filter_state, self._filter_claim = None, None   # set on the children `filtered` makes
         self._native = 0                     # NEED_* bits already pushed to the native registry (push_native)
 
     @classmethod
@@ -230,14 +271,14 @@ class EdgeStructure:
         child._by_dst, child._by_src = tabs[0], (tabs[1] if orders == 2 else None)
         for c, is_short in zip(tabs, short):
             if is_short:
-                c.__dict__["_long"] = False
+                c.mark_short()
         child.filter_state, child._filter_claim = state, (kept if known else None)
         return child, kept_id, outs
 
     def check_filter(self):
         """for a structure made by `filtered(..., num_kept=k)`: raise ValueError unless the mask had exactly k entries set
         (one device -> host read; the tables of a structure that fails this are not to be used)"""
-        if getattr(self, "_filter_claim", None) is not None:
+        if self._filter_claim is not None:
             count, status = self.filter_state.tolist()
             if status & 1:
                 raise ValueError(f"keep has {count} entries set, num_kept said {self._filter_claim}")
@@ -275,17 +316,22 @@ class EdgeStructure:
                 last_s.data_ptr(), bad.data_ptr(), _lib.stream_ptr()), "pangnn_structure_small")
             if not self.hints.get("valid_ids", False) and int(bad.item()) != 0:
                 raise ValueError(f"edge_index contains node ids outside [0, {n})")
-        self._by_dst, self._by_src = CSR(rp_d, other_d, perm_d), CSR(rp_s, other_s, perm_s)
-        self._by_dst.__dict__["_long"] = self._by_src.__dict__["_long"] = False      # <= 16384 edges in all: no split, no read-back
-        self._small_built = True
-        from types import SimpleNamespace
         n_bound = nc + min(n, e)
-        plans = self.__dict__.setdefault("_csr_plans", {})
-        for by, poff, prp, keys, last in (("dst", poff_d, prp_d, keys_d, last_d), ("src", poff_s, prp_s, keys_s, last_s)):
-            plan = SimpleNamespace(n_parts=n_bound, part_off=poff, part_rowptr=prp, keys=keys, chunk_tiles=ct, _last=last)
-            plan.n_parts_exact = (lambda pl: (lambda: int(pl._last) + 1))(plan)
-            plans[(by, ct)] = plan
+        self.adopt_tables(CSR(rp_d, other_d, perm_d), CSR(rp_s, other_s, perm_s),
+                          {("dst", ct): RunPlan(n_bound, poff_d, prp_d, keys_d, ct, last_d),
+                           ("src", ct): RunPlan(n_bound, poff_s, prp_s, keys_s, ct, last_s)})
         return True
+
+    def adopt_tables(self, by_dst: CSR, by_src: CSR, plans=None, short_rows: bool = True):
+        """Take over tables written in the small build's format (by it, or for a collated batch: SubGraphDataset.
+        _structures_of): both CSR orders and their stream-less plans {("dst" | "src", chunk_tiles): RunPlan}.  `short_rows`: no
+        row exceeds LONG_ROW (<= 16384 edges in all, a batch of small sub-graphs): no split, no read-back."""
+        self._by_dst, self._by_src, self._small_built = by_dst, by_src, True
+        if short_rows:
+            by_dst.mark_short(), by_src.mark_short()
+        if plans:
+            self._plans.update(plans)
+        return self
 
     @property
     def by_dst(self) -> CSR:
@@ -298,7 +344,7 @@ class EdgeStructure:
             if self.num_nodes < nmax and self.num_edges and int(self.edge_index[1].max()) >= self.num_nodes:
                 raise ValueError("target id outside the local row range")
             if self._vouched_short():                    # a producer-vouched list (a collated batch): built without any
-                self._by_dst.__dict__["_long"] = False   # read-back, so no read-back of the longest row either
+                self._by_dst.mark_short()                # read-back, so no read-back of the longest row either
         return self._by_dst
 
     @property
@@ -309,7 +355,7 @@ class EdgeStructure:
             nmax = max(self.num_nodes, self.num_src)
             self._by_src = build_csr(self.edge_index, nmax, 0, validate=False, num_rows=self.num_src)
             if self._vouched_short():
-                self._by_src.__dict__["_long"] = False
+                self._by_src.mark_short()
         return self._by_src
 
     def _vouched_short(self) -> bool:
@@ -319,15 +365,15 @@ class EdgeStructure:
 
     def sorted_by_src(self) -> bool:
         """the caller's edge order is sorted by source (decided once: the producer's hint, or one host read-back)"""
-        if self._runsum is None:
+        if self._sorted is None:
             src, e = self.edge_index[0], self.num_edges
             if e == 0:
-                self._runsum = False
+                self._sorted = False
             elif "sorted_by_src" in self.hints:
-                self._runsum = {} if self.hints["sorted_by_src"] else False
+                self._sorted = bool(self.hints["sorted_by_src"])
             else:
-                self._runsum = {} if bool((src[1:] >= src[:-1]).all()) else False
-        return self._runsum is not False
+                self._sorted = bool((src[1:] >= src[:-1]).all())
+        return self._sorted
 
     def band_width(self) -> int:
         """k > 0 if this edge list IS the positional-neighbour graph of a whole genome set as the reference builds it
@@ -352,14 +398,10 @@ class EdgeStructure:
         return self._band
 
     @staticmethod
-    def _plan_of_sorted_keys(keys: torch.Tensor, n_rows: int, chunk_tiles: int = 1):
-        """Layout of the per-(chunk, key) partial rows for an edge order whose `keys` are non-decreasing; a chunk is
-        `chunk_tiles` consecutive 32-edge tiles (1: the strict-fp32 kernels of decoder.hip; pangnn_decoder_chunk_tiles()
-        = 16: the S / T kernels of decoder16.hip, whose waves carry an open run from tile to tile inside a chunk):
-          part_off[c]    index of chunk c's first part
-          part_rowptr[r] parts of row r are [part_rowptr[r], part_rowptr[r+1])   (consecutive: sorted)
-          keys           int32 copy handed to the kernel"""
-        from types import SimpleNamespace
+    def _plan_of_sorted_keys(keys: torch.Tensor, n_rows: int, chunk_tiles: int = 1) -> RunPlan:
+        """The stream-less RunPlan of an edge order whose `keys` are non-decreasing, by index ops (the definition the plan
+        kernels are tested against); chunk_tiles 1: the strict-fp32 kernels of decoder.hip; pangnn_decoder_chunk_tiles()
+        = 16: the S / T kernels of decoder16.hip, whose waves carry an open run from tile to tile inside a chunk."""
         e = keys.shape[0]
         span = 32 * int(chunk_tiles)
         flags = (torch.arange(e, device=keys.device) % span) == 0
@@ -371,11 +413,8 @@ class EdgeStructure:
         n_bound = (e + span - 1) // span + min(int(n_rows), e)
         first = torch.searchsorted(keys, torch.arange(n_rows + 1, device=keys.device, dtype=keys.dtype))
         pid_ext = torch.cat([part_id, part_id[-1:] + 1])
-        plan = SimpleNamespace(n_parts=n_bound, part_off=part_id[::span].to(torch.int32).contiguous(),
-                               part_rowptr=pid_ext[first].contiguous(), keys=keys.to(torch.int32).contiguous(),
-                               chunk_tiles=int(chunk_tiles), _last=part_id[-1:])
-        plan.n_parts_exact = lambda: int(plan._last) + 1
-        return plan
+        return RunPlan(n_bound, part_id[::span].to(torch.int32).contiguous(), pid_ext[first].contiguous(),
+                       keys.to(torch.int32).contiguous(), int(chunk_tiles), part_id[-1:])
 
     @staticmethod
     def _plan_of_rowptr(rowptr: torch.Tensor, num_edges: int, chunk_tiles: int = 1, perm: Optional[torch.Tensor] = None):
@@ -383,10 +422,7 @@ class EdgeStructure:
         pangnn_csr_plan, csrc/csr_plan.hip): the keys are non-decreasing, so the key changes sit at rowptr[r] of the
         non-empty rows — one scan over the rows and one write of `keys`, no pass over a key array.  Same fields, dtypes and
         shapes, entry for entry (tests/test_csr_plan.py).
-        `perm` (that order's int32 edge ids): the plan also carries `tpos` — one word per position, perm[p] | closes_p << 31
-        with closes_p = "a part ends behind p" (pangnn_csr_plan_tpos; held as int32, read as uint32) — the stream the
-        decoder's T pass walks instead of perm and keys (pangnn_decoder_dgrad_stream_f32): 4 more bytes per edge kept."""
-        from types import SimpleNamespace
+        `perm` (that order's int32 edge ids): the plan also carries the CSR-order `stream` (4 more bytes per edge kept)."""
         lib = _lib.load()
         e, n_rows, ct = int(num_edges), rowptr.shape[0] - 1, int(chunk_tiles)
         span = 32 * ct
@@ -405,23 +441,17 @@ class EdgeStructure:
             _lib.check(lib.pangnn_csr_plan(rowptr.data_ptr(), n_rows, e, span, keys.data_ptr(), part_off.data_ptr(),
                                            part_rowptr.data_ptr(), last.data_ptr(), ws.data_ptr(), ws_bytes,
                                            _lib.stream_ptr()), "pangnn_csr_plan")
-            tpos = None
+            stream = None
             if perm is not None:
                 perm = perm if perm.is_contiguous() else perm.contiguous()
-                tpos = torch.empty(e, dtype=torch.int32, device=dev)
-                _lib.check(lib.pangnn_csr_plan_tpos(perm.data_ptr(), keys.data_ptr(), e, span, tpos.data_ptr(),
+                stream = torch.empty(e, dtype=torch.int32, device=dev)
+                _lib.check(lib.pangnn_csr_plan_tpos(perm.data_ptr(), keys.data_ptr(), e, span, stream.data_ptr(),
                                                     _lib.stream_ptr()), "pangnn_csr_plan_tpos")
-        plan = SimpleNamespace(n_parts=nc + min(n_rows, e), part_off=part_off, part_rowptr=part_rowptr, keys=keys,
-                               chunk_tiles=ct, _last=last, tpos=tpos)
-        plan.n_parts_exact = lambda: int(plan._last) + 1
-        return plan
+        return RunPlan(nc + min(n_rows, e), part_off, part_rowptr, keys, ct, last, stream)
 
     @staticmethod
     def _spos_of_sorted_list(edge_index: torch.Tensor, chunk_tiles: int) -> torch.Tensor:
-        """The S pass's position stream of a source-sorted device list (pangnn_csr_plan_spos): [P, 2] int32 (read as uint32)
-        for the P = 32 ceil(E / 32) positions of whole tiles, { src | closes << 31, dst } with closes = "a part ends behind
-        this position"; a position past the list repeats the last edge.  What pangnn_decoder_train_stream_* walks instead of
-        the int64 ids."""
+        """The run-sum plan's `stream` (RunPlan) of a source-sorted device list: pangnn_csr_plan_spos."""
         lib = _lib.load()
         e = edge_index.shape[1]
         ei = edge_index if edge_index.stride(1) == 1 else edge_index.contiguous()
@@ -431,44 +461,53 @@ class EdgeStructure:
                                                 _lib.stream_ptr()), "pangnn_csr_plan_spos")
         return spos
 
-    def csr_plan(self, by: str, chunk_tiles: int = 1):
+    def _streams(self, kind: str, ct: int) -> bool:
+        """Whether the plan (kind, ct), kind in {"run", "dst", "src"}, carries a `stream` (RunPlan).  All of: a square structure
+        (not a partitioned shard's rectangular one); ct is the S / T kernels' chunk size for this edge count (not the
+        strict-fp32 kernels' one-tile chunks of a long list); the plan kernel makes the plan (PLAN_KERNEL on device tensors: not
+        the index-op route, not the small build or a collated batch's tables); and the order is by target with int32 edge ids
+        (4 more bytes per edge kept) or the run-sum plan's of a list that is no filtered child (8 more bytes; a child's list
+        lives for one step: building its stream would cost more than S saves on it).  A pass over a plan without one reads
+        the ids: S the int64 list, T the order's perm and keys."""
+        if self.num_src != self.num_nodes or ct != int(_lib.load().pangnn_decoder_chunk_tiles_for(self.num_edges)) \
+                or not (PLAN_KERNEL and self.edge_index.is_cuda) or self._small_built:
+            return False
+        if kind == "dst":
+            return self._by_dst is not None and self._by_dst.perm.dtype == torch.int32    # (csr_plan has built the order)
+        return kind == "run" and self.filter_state is None
+
+    def csr_plan(self, by: str, chunk_tiles: int = 1) -> Optional[RunPlan]:
         """run-sum plan of the CSR order `by` in {"dst", "src"} (pangnn_decoder_dgrad_f32: perm = that CSR's perm)"""
-        cache = self.__dict__.setdefault("_csr_plans", {})
         key = (by, int(chunk_tiles))
-        if key not in cache:
+        if key not in self._plans:
             csr = self.by_dst if by == "dst" else self.by_src
-            if key in cache:                             # (the small build, just triggered, made the plans too)
-                return cache[key]
+            if key in self._plans:                       # (the small build, just triggered, made the plans too)
+                return self._plans[key]
             n_rows = self.num_nodes if by == "dst" else self.num_src
             if not self.num_edges:
-                cache[key] = None
+                self._plans[key] = None
             elif PLAN_KERNEL and csr.rowptr.is_cuda:
-                # the by-target plan of a square structure at the S / T kernels' chunk size also carries T's position words;
-                # every other plan (by source, a shard's rectangular structure, the strict-fp32 kernels' one-tile chunks of a
-                # long list, the small build, the index-op route) has none and T takes its keys route
-                stream = by == "dst" and self.num_src == self.num_nodes and csr.perm.dtype == torch.int32 and \
-                    int(chunk_tiles) == int(_lib.load().pangnn_decoder_chunk_tiles_for(self.num_edges))
-                cache[key] = self._plan_of_rowptr(csr.rowptr, self.num_edges, chunk_tiles, csr.perm if stream else None)
+                self._plans[key] = self._plan_of_rowptr(csr.rowptr, self.num_edges, chunk_tiles,
+                                                        csr.perm if self._streams(by, key[1]) else None)
             else:
                 keys = self.edge_index[1 if by == "dst" else 0][csr.perm.long()]
-                cache[key] = self._plan_of_sorted_keys(keys, n_rows, chunk_tiles)
-        return cache[key]
+                self._plans[key] = self._plan_of_sorted_keys(keys, n_rows, chunk_tiles)
+        return self._plans[key]
 
-    def runsum_plan(self, chunk_tiles: int = 1):
-        """If the caller's edge order is sorted by source: the layout of the per-(chunk, source) partial rows the decoder
-        training kernels can emit (include/pangnn_hip.h, `part_buf` / `part_off`), else None.
-          part_off[c]    index of chunk c's first part
-          part_rowptr[s] parts of source s are [part_rowptr[s], part_rowptr[s+1])   (consecutive: sorted)"""
+    def runsum_plan(self, chunk_tiles: int = 1) -> Optional[RunPlan]:
+        """If the caller's edge order is sorted by source: the plan of the per-(chunk, source) partial rows the decoder
+        training kernels can emit (include/pangnn_hip.h, `part_buf` / `part_off`), else None."""
         if not self.sorted_by_src():
             return None
         ct = int(chunk_tiles)
-        if ct not in self._runsum:
-            # a source-sorted list IS its by-source order (stable sort of a sorted list): the small build's plan of that
-            # order is this plan
+        key = ("run", ct)
+        if key not in self._plans:
+            # a source-sorted list IS its by-source order (stable sort of a sorted list): the small build's ("src", ct) plan
+            # is this plan
             self._small_build()              # no-op unless applicable and nothing is built yet
-            small = self.__dict__.get("_csr_plans", {}).get(("src", ct)) if self._small_built else None
+            small = self._plans.get(("src", ct)) if self._small_built else None
             if small is not None:
-                self._runsum[ct] = small
+                self._plans[key] = small
             elif PLAN_KERNEL and self.edge_index.is_cuda:
                 # the list is its own by-source order: that order's row pointer where it is held (a filtered child always
                 # holds it), else the first entry of every source by one N-sized search of the sorted sources — no sort
@@ -477,17 +516,12 @@ class EdgeStructure:
                 else:
                     src = self.edge_index[0]
                     rowptr = torch.searchsorted(src, torch.arange(self.num_src + 1, device=src.device, dtype=src.dtype))
-                plan = self._runsum[ct] = self._plan_of_rowptr(rowptr, self.num_edges, ct)
-                # a square structure's plan at the S kernel's chunk size also carries S's position stream (8 more bytes per
-                # edge kept); every other plan (a shard's rectangular structure, the strict-fp32 kernels' one-tile chunks of a
-                # long list, the small build, the index-op route, and a filtered child, whose list lives for one step: building
-                # its stream would cost more than S saves on it) has none and S reads the int64 ids
-                if self.num_src == self.num_nodes and getattr(self, "filter_state", None) is None and \
-                        ct == int(_lib.load().pangnn_decoder_chunk_tiles_for(self.num_edges)):
-                    plan.spos = self._spos_of_sorted_list(self.edge_index, ct)
+                plan = self._plans[key] = self._plan_of_rowptr(rowptr, self.num_edges, ct)
+                if self._streams("run", ct):
+                    plan.stream = self._spos_of_sorted_list(self.edge_index, ct)
             else:
-                self._runsum[ct] = self._plan_of_sorted_keys(self.edge_index[0], self.num_src, ct)
-        return self._runsum[ct]
+                self._plans[key] = self._plan_of_sorted_keys(self.edge_index[0], self.num_src, ct)
+        return self._plans[key]
 
     def native_has(self, need: int, norm=None, x=None) -> bool:
         """everything `need` names is in the native registry already (as far as this object knows: the registry may have
@@ -533,15 +567,13 @@ class EdgeStructure:
                 srt = 0 if plan is None else 1
             ops._register_structure(ei, n, self.num_src, self.edge_index, by_dst, by_src, band, srt)
             if plan is not None:
-                ops._register_plan(ei, n, 0, ct, plan.part_off, plan.part_rowptr, plan.keys, int(plan.n_parts),
-                                   getattr(plan, "spos", None))
+                ops._register_plan(ei, n, 0, ct, plan.part_off, plan.part_rowptr, plan.keys, int(plan.n_parts), plan.stream)
             have |= todo | NEED_ENTRY
         for bit, by, kind in ((NEED_PLAN_DST, "dst", 1), (NEED_PLAN_SRC, "src", 2)):
             if need & bit & ~have:
                 if e:
                     plan = self.csr_plan(by, ct)
-                    ops._register_plan(ei, n, kind, ct, plan.part_off, plan.part_rowptr, plan.keys, int(plan.n_parts),
-                                       getattr(plan, "tpos", None))
+                    ops._register_plan(ei, n, kind, ct, plan.part_off, plan.part_rowptr, plan.keys, int(plan.n_parts), plan.stream)
                 have |= bit
         self._native = have
         nb = need & _NORM_BITS

@@ -429,24 +429,18 @@ class SubGraphDataset:
 
     def _structures_of(self, buf):
         """graph.EdgeStructure objects of the batch's two edge lists over the order tables the collation wrote"""
-        from .graph import CSR, EdgeStructure
+        from .graph import CSR, EdgeStructure, RunPlan
         g, n, e, b = buf.spec
+        ct, nc = buf.orders.chunk_tiles, buf.orders.n_chunks
         out = {}
         for name, ei, m in (("sim", buf.edge_index, e), ("nb", buf.neighbour_edge_index, b)):
             td, ts = buf.orders.tables[name + "_dst"], buf.orders.tables[name + "_src"]
-            st = EdgeStructure(ei, n, hints=buf._pangnn_hints[name])
-            st._by_dst, st._by_src = CSR(td["rowptr"], td["other"], td["perm"]), CSR(ts["rowptr"], ts["other"], ts["perm"])
-            st._by_dst.__dict__["_long"] = st._by_src.__dict__["_long"] = False    # a collated batch of small sub-graphs
-            st._small_built = True
-            if name == "sim":
-                ct, nc = buf.orders.chunk_tiles, buf.orders.n_chunks
-                plans = st.__dict__.setdefault("_csr_plans", {})
-                for by, t in (("dst", td), ("src", ts)):
-                    plan = SimpleNamespace(n_parts=nc + min(n, m), part_off=t["part_off"], part_rowptr=t["part_rowptr"],
-                                           keys=t["keys"], chunk_tiles=ct, _last=t["last_part"])
-                    plan.n_parts_exact = (lambda pl: (lambda: int(pl._last) + 1))(plan)
-                    plans[(by, ct)] = plan
-            out[name] = st
+            plans = None if name != "sim" else {
+                (by, ct): RunPlan(nc + min(n, m), t["part_off"], t["part_rowptr"], t["keys"], ct, t["last_part"])
+                for by, t in (("dst", td), ("src", ts))}
+            # (a collated batch of small sub-graphs: short rows)
+            out[name] = EdgeStructure(ei, n, hints=buf._pangnn_hints[name]).adopt_tables(
+                CSR(td["rowptr"], td["other"], td["perm"]), CSR(ts["rowptr"], ts["other"], ts["perm"]), plans)
         return out
 
     def collate_padded(self, buf):

@@ -20,7 +20,7 @@ LAYOUTS = ["hub_alone", "hub_among_empty_rows", "one_entry_per_row", "rows_on_ch
 
 
 def plans_equal(got, want, what=""):
-    for f in ("keys", "part_off", "part_rowptr", "_last"):
+    for f in ("keys", "part_off", "part_rowptr", "last"):
         a, b = getattr(got, f), getattr(want, f)
         assert a.dtype == b.dtype and a.shape == b.shape and torch.equal(a, b), (what, f)
     assert got.n_parts == want.n_parts and got.chunk_tiles == want.chunk_tiles, what
@@ -162,4 +162,88 @@ def test_a_sub_sampled_step_needs_no_index_op_plan(skip, monkeypatch):
     assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
     assert len(got[2]) == len(want[2]) > 0
     for a, b in zip(got[2], want[2]):
+        assert torch.equal(a, b)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# which plans carry a stream (EdgeStructure._streams), producer by producer
+# ------------------------------------------------------------------------------------------------------------------
+N_NODES = 512
+
+
+def _sorted_list(e, seed=0):
+    gen = torch.Generator().manual_seed(seed)
+    src = torch.sort(torch.randint(0, N_NODES, (e,), generator=gen)).values
+    return torch.stack([src, torch.randint(0, N_NODES, (e,), generator=gen)]).to(DEV)
+
+
+def _whole(e):
+    return EdgeStructure(_sorted_list(e), N_NODES)
+
+
+def _filtered_child(e):
+    parent = _whole(e)
+    parent.by_src
+    keep = torch.rand(e, generator=torch.Generator().manual_seed(1)) < 0.8
+    child = EdgeStructure.filtered(parent, keep.to(DEV))[0]
+    assert child.filter_state is not None and child._by_src is not None and 0 < child.num_edges < e
+    return child
+
+
+def _adopted_without_plans(e):
+    """tables handed over without plans, as a collated batch's neighbour list has them: the plan kernel makes its plans"""
+    made = _whole(e)
+    return EdgeStructure(made.edge_index, N_NODES).adopt_tables(made.by_dst, made.by_src)
+
+
+def test_which_plans_carry_a_stream(monkeypatch):
+    """every producer EdgeStructure._streams names: (run-sum, by-target, by-source) plan with a stream or without; then one
+    decoder_loss step through the native registry, whose gradients are those of the same step on plans without streams"""
+    from pangnn_amd import functional as PF, torch_ops
+    big, more, small = 20000, 140000, 3000          # above the small build's 16384 edges; two-tile chunks; the small build
+    assert (PF.d16_chunk(big), PF.d16_chunk(more), PF.d16_chunk(small)) == (1, 2, 1)
+    d16 = None                                      # the S / T kernels' chunk size of the structure's own edge count
+    table = [("whole graph", lambda: _whole(big), d16, (True, True, False)),
+             ("whole graph, not the kernels' chunk size", lambda: _whole(big), 16, (False, False, False)),
+             ("whole graph, two-tile chunks", lambda: _whole(more), d16, (True, True, False)),
+             ("whole graph, one-tile chunks of a longer list", lambda: _whole(more), 1, (False, False, False)),
+             ("small build", lambda: _whole(small), d16, (False, False, False)),
+             ("adopted tables", lambda: _adopted_without_plans(big), d16, (False, False, False)),
+             ("rectangular", lambda: EdgeStructure(_sorted_list(big), N_NODES, num_src=2 * N_NODES), d16, (False, False, False)),
+             ("filtered child", lambda: _filtered_child(big), d16, (False, True, False)),
+             ("index-op route", lambda: _whole(big), d16, (False, False, False))]
+    for what, make, ct, want in table:
+        monkeypatch.setattr(G, "PLAN_KERNEL", what != "index-op route")
+        st = make()
+        e = st.num_edges
+        ct = PF.d16_chunk(e) if ct is None else ct
+        plans = st.runsum_plan(ct), st.csr_plan("dst", ct), st.csr_plan("src", ct)
+        assert st._small_built == (what in ("small build", "adopted tables")), what
+        assert tuple(p.stream is not None for p in plans) == want, what
+        assert [st._streams(kind, ct) for kind in ("run", "dst", "src")] == list(want), what
+        for p, shape in zip(plans, (((e + 31) // 32 * 32, 2), (e,), None)):
+            assert p.chunk_tiles == ct and (p.stream is None or (p.stream.dtype == torch.int32 and p.stream.shape == shape)), what
+    monkeypatch.setattr(G, "PLAN_KERNEL", True)
+
+    st = _whole(big)
+    ct = PF.d16_chunk(big)
+    gen = torch.Generator().manual_seed(2)
+    rnd = lambda *s: torch.randn(*s, generator=gen).to(DEV)          # noqa: E731
+    leaves = [rnd(N_NODES, 128) / 4, rnd(64, 64) / 8, rnd(64) / 8, rnd(64) / 8, rnd(1) / 8]
+    y, pw = (torch.rand(big, generator=gen) < 0.3).float().to(DEV), torch.tensor(2.5, device=DEV)
+    need = G.NEED_BY_DST | G.NEED_RUNSUM | G.NEED_PLAN_DST
+    res = []
+    for stream in (True, False):
+        plans = st.runsum_plan(ct), st.csr_plan("dst", ct)
+        if not stream:
+            for p in plans:
+                p.stream = None
+        assert all((p.stream is not None) == stream for p in plans)
+        st.push_native(need, force=True)
+        pq, w2, b2, w3, b3 = ws = [t.clone().requires_grad_(True) for t in leaves]
+        loss, logits = torch_ops.decoder_loss_pq(pq, st, None, None, w2, b2, w3, b3, y, pw, big)
+        loss.backward()
+        res.append([loss.detach(), logits.detach()] + [t.grad for t in ws])
+    assert bool(torch.isfinite(res[0][0]).all()) and all(bool(g.abs().sum() > 0) for g in res[0][2:])
+    for a, b in zip(*res):
         assert torch.equal(a, b)

@@ -123,7 +123,7 @@ def run_T(c, route, w2=None, want_b2=True):
     ws = torch.empty(lib.pangnn_decoder_dgrad_workspace_bytes(), dtype=torch.uint8, device=dev()) if want_b2 else None
     wsb = 0 if ws is None else ws.numel()
     if route == "stream":
-        L.check(lib.pangnn_decoder_dgrad_stream_f32(c.rec.data_ptr(), c.plan.tpos.data_ptr(), w2.data_ptr(), c.td["w3"].data_ptr(),
+        L.check(lib.pangnn_decoder_dgrad_stream_f32(c.rec.data_ptr(), c.plan.stream.data_ptr(), w2.data_ptr(), c.td["w3"].data_ptr(),
                                                     c.e, parts.data_ptr(), c.plan.part_off.data_ptr(), L.ptr(gb2), L.ptr(ws), wsb,
                                                     L.stream_ptr()), "pangnn_decoder_dgrad_stream_f32")
     else:
@@ -145,8 +145,8 @@ def both_routes(name):
 @pytest.mark.parametrize("name", GRAPHS)
 def test_tpos_is_perm_with_the_close_bit(name):
     c = case(name)
-    assert c.plan.tpos.dtype == torch.int32 and c.plan.tpos.shape == (c.e,)
-    got = c.plan.tpos.long() & 0xffffffff
+    assert c.plan.stream.dtype == torch.int32 and c.plan.stream.shape == (c.e,)
+    got = c.plan.stream.long() & 0xffffffff
     assert torch.equal(got, tpos_expected(c.perm, c.keys, 32 * c.ct))
     assert int((got >> 31).sum()) == c.lay.n_parts                            # one close bit per part row
 
@@ -218,16 +218,16 @@ def test_structures_route_by_what_their_plan_carries():
     c = case("E70000")
     st = EdgeStructure(c.ei, c.n)
     plan = st.csr_plan("dst", PF.d16_chunk(c.e))
-    assert plan.tpos is not None and torch.equal(plan.tpos, c.plan.tpos)
-    assert getattr(st.csr_plan("src", PF.d16_chunk(c.e)), "tpos", None) is None
+    assert plan.stream is not None and torch.equal(plan.stream, c.plan.stream)
+    assert st.csr_plan("src", PF.d16_chunk(c.e)).stream is None
     small = case("E3000")
-    assert getattr(EdgeStructure(small.ei, small.n).csr_plan("dst", PF.d16_chunk(small.e)), "tpos", None) is None
+    assert EdgeStructure(small.ei, small.n).csr_plan("dst", PF.d16_chunk(small.e)).stream is None
     w2, w3 = c.td["W2"], c.td["w3"]
     b_stream, b_keys, b_live = (torch.empty(D, device=dev()) for _ in range(3))
     got = PF._dgrad_sum(c.rec, st, "dst", w2, w3, c.n, g_b2=b_stream)
     live = torch.tensor([c.e], dtype=torch.int64, device=dev())
     got_live = PF._dgrad_sum(c.rec, st, "dst", w2, w3, c.n, g_b2=b_live, live=live)        # `live` given: keys route
-    plan.tpos = None
+    plan.stream = None
     got_keys = PF._dgrad_sum(c.rec, st, "dst", w2, w3, c.n, g_b2=b_keys)
     assert torch.equal(got, got_keys) and torch.equal(got, got_live)
     assert torch.equal(b_stream, b_keys) and torch.equal(b_stream, b_live)
@@ -246,7 +246,7 @@ def test_dispatcher_route_uses_the_registered_stream():
     b2 = c.td["b2"].clone().requires_grad_(True)
     out = torch_ops.decoder_mlp_pq(pq, st, None, None, c.td["W2"], b2, c.td["w3"], c.td["b3"])
     out.backward(c.g)
-    assert st.csr_plan("dst", c.ct).tpos is not None                          # what the backward registered and walked
+    assert st.csr_plan("dst", c.ct).stream is not None                          # what the backward registered and walked
     want_q = torch.zeros(c.n, D, dtype=torch.float64, device=dev()).index_add_(0, c.ei[1], c.ref["gh1"])
     assert torch.equal(out.detach(), _f32(c.ref["logits"]))
     assert torch.equal(pq.grad[:, D:], _f32(want_q)) and torch.equal(b2.grad, _f32(c.ref["a"].sum(0)))

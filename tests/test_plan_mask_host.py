@@ -85,7 +85,7 @@ def test_the_rowptr_formulas_are_the_plan_of_the_sorted_keys(span):
             assert keys.dtype == want.keys.dtype and torch.equal(keys, want.keys), what
             assert part_off.dtype == want.part_off.dtype and torch.equal(part_off, want.part_off), what
             assert part_rowptr.dtype == want.part_rowptr.dtype and torch.equal(part_rowptr, want.part_rowptr), what
-            assert last.dtype == want._last.dtype and torch.equal(last, want._last), what
+            assert last.dtype == want.last.dtype and torch.equal(last, want.last), what
             assert want.n_parts == (e + span - 1) // span + min(n_rows, e) >= int(last) + 1, what
 
 

@@ -120,10 +120,10 @@ def test_structures_route_by_what_their_plan_carries():
     c = case("ct2")
     st = EdgeStructure(c.ei, c.n)
     plan = st.runsum_plan(PF.d16_chunk(c.e))
-    assert plan.spos is not None and torch.equal(plan.spos, c.spos)
-    assert getattr(st.runsum_plan(1), "spos", None) is None                      # the strict-fp32 kernels' one-tile chunks
+    assert plan.stream is not None and torch.equal(plan.stream, c.spos)
+    assert st.runsum_plan(1).stream is None                      # the strict-fp32 kernels' one-tile chunks
     small = case("ct1")
-    assert getattr(EdgeStructure(small.ei, small.n).runsum_plan(PF.d16_chunk(small.e)), "spos", None) is None
+    assert EdgeStructure(small.ei, small.n).runsum_plan(PF.d16_chunk(small.e)).stream is None
     names = []
     orig = PF._launch
 
@@ -140,7 +140,7 @@ def test_structures_route_by_what_their_plan_carries():
     try:
         for kw, pp in ((dict(), p), (dict(live=live), p), (dict(), wide[:, :D])):
             outs.append(PF._decoder_train16(pp, q, st, None, None, w.W2, w.b2, w.w3, w.b3, y=c.y, pw=c.pw, denom=c.e, **kw))
-        plan.spos = None
+        plan.stream = None
         outs.append(PF._decoder_train16(p, q, st, None, None, w.W2, w.b2, w.w3, w.b3, y=c.y, pw=c.pw, denom=c.e))
     finally:
         PF._launch = orig
@@ -185,10 +185,10 @@ def test_train_step_is_bit_identical_without_the_stream(route, monkeypatch):
         if route == "ctypes":
             monkeypatch.setattr(PF, "KERNEL_TIMER", {"dec.bwd": [], "dec.dgrad": [], "dec.fwd": []})
         loss, logits = train_step(model, opt, g, g.y, pw)
-        sts = [st for _, st in g._pangnn_structs.values() if st.num_edges == g.edge_index.shape[1] and st._runsum]
+        sts = [st for _, st in g._pangnn_structs.values() if st.num_edges == g.edge_index.shape[1] and st._sorted and any(k[0] == "run" for k in st._plans)]
         assert sts, "the decoder's structure is held on the graph"
-        plans = [p for st in sts for p in st._runsum.values()]
-        assert plans and all((getattr(p, "spos", None) is not None) == stream for p in plans)
+        plans = [p for st in sts for k, p in st._plans.items() if k[0] == "run"]
+        assert plans and all((p.stream is not None) == stream for p in plans)
         res.append((loss.clone(), logits.clone(), {k: p.grad.clone() for k, p in model.named_parameters() if p.grad is not None}))
     a, b = res
     assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]) and bool(torch.isfinite(a[0]).all())

@@ -155,9 +155,7 @@ def main():
 
         def plan_fresh(which, kernel):
             G.PLAN_KERNEL = kernel
-            child.__dict__["_csr_plans"] = {}
-            if child._runsum is not None and child._runsum is not False:
-                child._runsum.clear()
+            child._plans.clear()
             try:
                 return child.runsum_plan(ct) if which == "runsum" else child.csr_plan(which, ct)
             finally:
@@ -171,7 +169,7 @@ def main():
         for wh in whichs:                    # the same tables?  (before any timing)
             pa, pb = plan_fresh(wh, True), plan_fresh(wh, False)
             same_plans &= all(torch.equal(getattr(pa, f), getattr(pb, f)) and getattr(pa, f).dtype == getattr(pb, f).dtype
-                              for f in ("keys", "part_off", "part_rowptr", "_last")) and pa.n_parts == pb.n_parts
+                              for f in ("keys", "part_off", "part_rowptr", "last")) and pa.n_parts == pb.n_parts
         emit(dict(what="agreement_plans", chunk_tiles=ct, orders=list(whichs), plans_equal=bool(same_plans)))
         if not same_plans:
             raise SystemExit("the kernel's plans differ from the index-op route's")
