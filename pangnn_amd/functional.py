@@ -8,7 +8,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from .graph import CSR, EdgeStructure, GcnNorm
+from .graph import CSR, EdgeStructure, GcnNorm, chunk_tiles_for
 
 
 ROWS16 = (torch.bfloat16, torch.float16)        # the two 2-byte row formats (PANGNN_DTYPE_BF16 / _F16)
@@ -594,8 +594,7 @@ def edge_conv(x, w1, b1, w2, b2, st: EdgeStructure, return_arg: bool = False):
 def d16_chunk(num_edges: Optional[int] = None) -> int:
     """tiles per run-sum chunk of the S / T kernels for a list of `num_edges` edges (pangnn_decoder_chunk_tiles_for: 16 for
     E >= 1e6, fewer for short lists so that a mini-batch still spreads over the chip); None: the maximum"""
-    lib = _lib.load()
-    return int(lib.pangnn_decoder_chunk_tiles() if num_edges is None else lib.pangnn_decoder_chunk_tiles_for(int(num_edges)))
+    return int(_lib.load().pangnn_decoder_chunk_tiles()) if num_edges is None else chunk_tiles_for(num_edges)
 
 
 def _sum_parts(plan, part_buf: torch.Tensor, n_rows: int, out: torch.Tensor, accumulate: bool = False,

@@ -96,6 +96,35 @@ class CSR:
         return hit or None
 
 
+def carve(dtype: torch.dtype, device, counts, align: int = 16):
+    """One allocation holding a table of counts[i] elements for every i: the 1-D views, in order, each starting on an
+    `align`-byte boundary of the allocation (a count of 0: an empty view).  Every packed table the kernels write through raw
+    pointers is laid out here."""
+    unit = align // dtype.itemsize
+    starts, end = [], 0
+    for k in counts:
+        starts.append(end)
+        end += -(-k // unit) * unit
+    buf = torch.empty(end, dtype=dtype, device=device)
+    return [buf[s:s + k] for s, k in zip(starts, counts)]
+
+
+def chunk_tiles_for(num_edges: int) -> int:
+    """tiles per run-sum chunk of the S / T kernels for a list of `num_edges` edges: the one place that asks the library"""
+    return int(_lib.load().pangnn_decoder_chunk_tiles_for(int(num_edges)))
+
+
+def n_chunks(num_edges: int, chunk_tiles: int) -> int:
+    """chunks of `chunk_tiles` 32-edge tiles that an edge list has (the entries of a plan's part_off)"""
+    return (num_edges + 32 * chunk_tiles - 1) // (32 * chunk_tiles)
+
+
+def part_bound(rows: int, num_edges: int, chunk_tiles: int) -> int:
+    """upper bound of a plan's part count — one part per chunk start plus one per key change — that every S / T part buffer
+    is sized by (RunPlan.n_parts)"""
+    return n_chunks(num_edges, chunk_tiles) + min(rows, num_edges)
+
+
 @dataclass
 class RunPlan:
     """Layout of the per-(chunk, key) part rows of an edge order with non-decreasing keys; a chunk is `chunk_tiles` consecutive
@@ -235,12 +264,9 @@ class EdgeStructure:
         kept_id = torch.empty(kept, dtype=torch.int32, device=dev)
         outs = [torch.empty(kept, dtype=torch.float32, device=dev) for _ in arrays]
         orders = 2 if s is not None else 1
-        ka, na = -(-kept // 4) * 4, -(-(n + 1) // 2) * 2                            # 16-byte aligned segments
-        i32 = torch.empty(2 * orders * ka + 4, dtype=torch.int32, device=dev)
-        i64 = torch.empty(orders * na, dtype=torch.int64, device=dev)
-        tabs = [CSR(i64[o * na:o * na + n + 1], i32[2 * o * ka:2 * o * ka + kept], i32[(2 * o + 1) * ka:(2 * o + 1) * ka + kept])
-                for o in range(orders)]
-        state = i32[2 * orders * ka:2 * orders * ka + 2]
+        *seg32, state = carve(torch.int32, dev, [kept] * (2 * orders) + [2])       # (other, perm) per order, then the state
+        rowptrs = carve(torch.int64, dev, [n + 1] * orders)
+        tabs = [CSR(rowptrs[o], seg32[2 * o], seg32[2 * o + 1]) for o in range(orders)]
         a_in, a_out = list(arrays) + [None, None], outs + [None, None]
         with _lib.device_guard(dev):
             ws_bytes = lib.pangnn_structure_filter_workspace_bytes(e)
@@ -296,27 +322,21 @@ class EdgeStructure:
         e, n = self.num_edges, self.num_nodes
         if not lib.pangnn_structure_small_supported(e, n):
             return False
-        ct = int(lib.pangnn_decoder_chunk_tiles_for(e))
-        span = 32 * ct
-        nc = (e + span - 1) // span
+        ct = chunk_tiles_for(e)
+        nc = n_chunks(e, ct)
         dev = self.edge_index.device
-        ea, na, ca = -(-e // 4) * 4, -(-(n + 1) // 2) * 2, -(-nc // 4) * 4             # 16-byte aligned segments
-        i32 = torch.empty(2 * (3 * ea + ca) + 4, dtype=torch.int32, device=dev)
-        i64 = torch.empty(2 * (2 * na + 2), dtype=torch.int64, device=dev)
-        seg32 = [i32[k * ea:k * ea + e] for k in range(6)] + [i32[6 * ea + k * ca:6 * ea + k * ca + nc] for k in range(2)]
-        other_d, perm_d, keys_d, other_s, perm_s, keys_s, poff_d, poff_s = seg32
-        bad = i32[6 * ea + 2 * ca:6 * ea + 2 * ca + 1]
-        rp_d, prp_d, rp_s, prp_s = (i64[k * na:k * na + n + 1] for k in range(4))
-        last_d, last_s = i64[4 * na:4 * na + 1], i64[4 * na + 2:4 * na + 3]
+        other_d, perm_d, keys_d, other_s, perm_s, keys_s, poff_d, poff_s, bad = carve(
+            torch.int32, dev, [e] * 6 + [nc] * 2 + [1])
+        rp_d, prp_d, rp_s, prp_s, last_d, last_s = carve(torch.int64, dev, [n + 1] * 4 + [1] * 2)    # (a 16-byte slot per `last`)
         with _lib.device_guard(dev):
             _lib.check(lib.pangnn_structure_small(
-                self.edge_index.data_ptr(), e, e, n, span, rp_d.data_ptr(), other_d.data_ptr(), perm_d.data_ptr(),
+                self.edge_index.data_ptr(), e, e, n, 32 * ct, rp_d.data_ptr(), other_d.data_ptr(), perm_d.data_ptr(),
                 keys_d.data_ptr(), poff_d.data_ptr(), prp_d.data_ptr(), last_d.data_ptr(), rp_s.data_ptr(),
                 other_s.data_ptr(), perm_s.data_ptr(), keys_s.data_ptr(), poff_s.data_ptr(), prp_s.data_ptr(),
                 last_s.data_ptr(), bad.data_ptr(), _lib.stream_ptr()), "pangnn_structure_small")
             if not self.hints.get("valid_ids", False) and int(bad.item()) != 0:
                 raise ValueError(f"edge_index contains node ids outside [0, {n})")
-        n_bound = nc + min(n, e)
+        n_bound = part_bound(n, e, ct)
         self.adopt_tables(CSR(rp_d, other_d, perm_d), CSR(rp_s, other_s, perm_s),
                           {("dst", ct): RunPlan(n_bound, poff_d, prp_d, keys_d, ct, last_d),
                            ("src", ct): RunPlan(n_bound, poff_s, prp_s, keys_s, ct, last_s)})
@@ -410,7 +430,7 @@ class EdgeStructure:
         # Everything stays on the device (no host read-back): the part buffer is sized by an upper bound — one part per
         # chunk start plus one per key change — and a row's first part is the part of its first entry (a key change
         # always starts a part).  `n_parts_exact()` reads the true count when somebody needs it (bench accounting).
-        n_bound = (e + span - 1) // span + min(int(n_rows), e)
+        n_bound = part_bound(int(n_rows), e, int(chunk_tiles))
         first = torch.searchsorted(keys, torch.arange(n_rows + 1, device=keys.device, dtype=keys.dtype))
         pid_ext = torch.cat([part_id, part_id[-1:] + 1])
         return RunPlan(n_bound, part_id[::span].to(torch.int32).contiguous(), pid_ext[first].contiguous(),
@@ -426,13 +446,11 @@ class EdgeStructure:
         lib = _lib.load()
         e, n_rows, ct = int(num_edges), rowptr.shape[0] - 1, int(chunk_tiles)
         span = 32 * ct
-        nc = (e + span - 1) // span
         dev = rowptr.device
         rowptr = rowptr if rowptr.is_contiguous() else rowptr.contiguous()
         keys = torch.empty(e, dtype=torch.int32, device=dev)
-        part_off = torch.empty(nc, dtype=torch.int32, device=dev)
-        i64 = torch.empty(n_rows + 2, dtype=torch.int64, device=dev)
-        part_rowptr, last = i64[:n_rows + 1], i64[n_rows + 1:]
+        part_off = torch.empty(n_chunks(e, ct), dtype=torch.int32, device=dev)
+        part_rowptr, last = carve(torch.int64, dev, [n_rows + 1, 1])
         with _lib.device_guard(dev):
             ws_bytes = lib.pangnn_csr_plan_workspace_bytes(n_rows)
             if ws_bytes == 0:
@@ -447,7 +465,7 @@ class EdgeStructure:
                 stream = torch.empty(e, dtype=torch.int32, device=dev)
                 _lib.check(lib.pangnn_csr_plan_tpos(perm.data_ptr(), keys.data_ptr(), e, span, stream.data_ptr(),
                                                     _lib.stream_ptr()), "pangnn_csr_plan_tpos")
-        return RunPlan(nc + min(n_rows, e), part_off, part_rowptr, keys, ct, last, stream)
+        return RunPlan(part_bound(n_rows, e, ct), part_off, part_rowptr, keys, ct, last, stream)
 
     @staticmethod
     def _spos_of_sorted_list(edge_index: torch.Tensor, chunk_tiles: int) -> torch.Tensor:
@@ -469,7 +487,7 @@ class EdgeStructure:
         (4 more bytes per edge kept) or the run-sum plan's of a list that is no filtered child (8 more bytes; a child's list
         lives for one step: building its stream would cost more than S saves on it).  A pass over a plan without one reads
         the ids: S the int64 list, T the order's perm and keys."""
-        if self.num_src != self.num_nodes or ct != int(_lib.load().pangnn_decoder_chunk_tiles_for(self.num_edges)) \
+        if self.num_src != self.num_nodes or ct != chunk_tiles_for(self.num_edges) \
                 or not (PLAN_KERNEL and self.edge_index.is_cuda) or self._small_built:
             return False
         if kind == "dst":
@@ -549,7 +567,7 @@ class EdgeStructure:
         from .torch_ops import ops
         ei, n, e = self._key_tensor, self.num_nodes, self.num_edges
         have = 0 if force else self._native
-        ct = int(_lib.load().pangnn_decoder_chunk_tiles_for(e))
+        ct = chunk_tiles_for(e)
         todo = need & _STRUCT_BITS & ~have
         if todo or not (have & NEED_ENTRY):
             by_dst, by_src, band, srt, plan = [], [], -1, -1, None
@@ -628,13 +646,10 @@ class GcnNorm:
             edge_weight = edge_weight.detach().to(torch.float32).contiguous()
         self.weight = edge_weight               # the fp32 contiguous weights that were normalised (functional.propagate_w's backward)
         d = st.by_dst
-        ea, na = -(-e // 4) * 4, -(-n // 4) * 4                          # one allocation, 16-byte aligned segments
         small = e <= (1 << 20)                  # small graphs: the by-source table too (a launch-bound step counts allocations)
-        buf = torch.empty(na + (3 if small else 2) * ea, dtype=torch.float32, device=dev)
-        self.deg_inv_sqrt = buf[:n]
-        self.by_dst = buf[na:na + e]                                     # CSR(dst) order
-        self.orig = buf[na + ea:na + ea + e]                             # caller's edge order
-        self._by_src_buf = buf[na + 2 * ea:na + 2 * ea + e] if small else None      # CSR(src) order, filled on first use
+        # one allocation: deg^-1/2, the norm in CSR(dst) order, in the caller's edge order, in CSR(src) order (filled on first use)
+        self.deg_inv_sqrt, self.by_dst, self.orig, *rest = carve(torch.float32, dev, [n] + [e] * (3 if small else 2))
+        self._by_src_buf = rest[0] if small else None
         with _lib.device_guard(dev):
             if gather_dis is None:
                 if st.num_src != st.num_nodes:
@@ -690,8 +705,7 @@ def structure_of(edge_index: torch.Tensor, num_nodes: int, holder=None, name: st
     kept on it (`holder._pangnn_structs[name]`), otherwise in a small identity-keyed cache."""
     if torch.compiler.is_compiling():
         return TracedStructure(edge_index, num_nodes)
-    key = (edge_index.data_ptr(), edge_index._version, tuple(edge_index.shape), int(num_nodes),
-           edge_index.device.index)
+    key = structure_key(edge_index, num_nodes)
     if holder is not None:
         d = getattr(holder, "_pangnn_structs", None)
         if d is None:
@@ -745,8 +759,7 @@ def register(st, key=None):
     if getattr(st, "traced", False):
         return
     if key is None:
-        ei = st._key_tensor
-        key = (ei.data_ptr(), ei._version, tuple(ei.shape), int(st.num_nodes), ei.device.index)
+        key = structure_key(st._key_tensor, st.num_nodes)
     if _CACHE.get(key) is not st:
         if len(_CACHE) >= _CACHE_MAX:
             _CACHE.pop(next(iter(_CACHE)))

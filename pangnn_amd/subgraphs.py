@@ -27,10 +27,35 @@ slices and one subtraction — no per-step collation on the host.
 """
 from __future__ import annotations
 
+import ctypes
 from types import SimpleNamespace
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
+
+from . import _lib
+from .graph import (CSR, EdgeStructure, RunPlan, carve, chunk_tiles_for, forget, n_chunks, part_bound, register,
+                    structure_key)
+
+
+class PaddedSpec(NamedTuple):
+    """the fixed shapes of a padded batch (SubGraphDataset.padded_spec)"""
+    graphs: int
+    nodes: int        # one more than the real nodes: the padding's endpoint
+    edges: int
+    nb_edges: int
+
+
+# pangnn_batch_order / pangnn_batch_orders of include/pangnn_hip.h, field for field: `rank` is read, the rest written by
+# pangnn_collate_subgraphs_padded (part_off / part_rowptr / last_part NULL: no plan for that order)
+class BatchOrder(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in ("rank", "rowptr", "other", "perm", "keys", "part_off", "part_rowptr",
+                                               "last_part")]
+
+
+class BatchOrders(ctypes.Structure):
+    _fields_ = [("chunk_edges", ctypes.c_int32), ("sim_dst", BatchOrder), ("sim_src", BatchOrder), ("nb_dst", BatchOrder),
+                ("nb_src", BatchOrder)]
 
 
 def _unique_sorted(keys: torch.Tensor) -> torch.Tensor:
@@ -262,7 +287,6 @@ class SubGraphDataset:
         hints = {"sim": {"valid_ids": True, "sorted_by_src": h.sorted_by_src}, "nb": {"valid_ids": True}}
         if dev.type == "cuda" and COLLATE_KERNEL:
             # one launch (pangnn_collate_subgraphs) instead of seven index ops: the step around it is launch-bound
-            from . import _lib
             lib = _lib.load()
             n, e, b, g = n1 - n0, e1 - e0, b1 - b0, i1 - i0
             buf = torch.empty(2 * e + 2 * b + (g + 1) + n, dtype=torch.int64, device=dev)
@@ -294,7 +318,7 @@ class SubGraphDataset:
 
     # ---- fixed-shape batches (train.ReplayedFreshStep): one set of buffers, one captured HIP graph, every mini-batch
     def padded_spec(self, batch_size: int = 32, graphs=None, slack: Optional[float] = None):
-        """(max_graphs, max_nodes, max_edges, max_nb): shapes that hold the disjoint union of ANY `batch_size` sub-graphs out
+        """PaddedSpec (max_graphs, max_nodes, max_edges, max_nb): shapes that hold the disjoint union of ANY `batch_size` sub-graphs out
         of `graphs` (default: all) — the sums of the `batch_size` largest counts, plus the one node that is never real
         (the padding's endpoint).  `slack`: instead `slack` times the MEAN batch (capped by the worst case) — what a
         shuffled batch needs in practice (the sum of 32 draws concentrates around its mean); a batch that does not fit is
@@ -310,14 +334,18 @@ class SubGraphDataset:
             if slack is None or not sizes:
                 return worst
             return min(worst, int(float(slack) * bs * sum(sizes) / len(sizes)) + 1)
-        return bs, cap(h.node) + 1, max(cap(h.edge), 1), max(cap(h.nb), 1)
+        return PaddedSpec(bs, cap(h.node) + 1, max(cap(h.edge), 1), max(cap(h.nb), 1))
+
+    def _counts(self, ids):
+        """(nodes, edges, neighbour edges) of the disjoint union of the sub-graphs `ids` (host arithmetic)"""
+        h = self._host()
+        return tuple(sum(off[i + 1] - off[i] for i in ids) for off in (h.node, h.edge, h.nb))
 
     def fits(self, spec, ids) -> bool:
         """whether the disjoint union of the sub-graphs `ids` fits the padded shapes `spec` (host arithmetic)"""
-        h = self._host()
-        ids = [int(i) for i in ids]
-        return len(ids) <= spec[0] and sum(h.node[i + 1] - h.node[i] for i in ids) < spec[1] \
-            and sum(h.edge[i + 1] - h.edge[i] for i in ids) <= spec[2] and sum(h.nb[i + 1] - h.nb[i] for i in ids) <= spec[3]
+        spec, ids = PaddedSpec(*spec), [int(i) for i in ids]
+        n, e, b = self._counts(ids)
+        return len(ids) <= spec.graphs and n < spec.nodes and e <= spec.edges and b <= spec.nb_edges
 
     def structure_index(self):
         """per flat edge of both lists: its position inside its own sub-graph in the by-target and in the by-source order
@@ -351,103 +379,69 @@ class SubGraphDataset:
         buffers of both CSR orders (and the decoder's run-sum plans) of both edge lists, written by the collation itself —
         no per-batch sort (`structure_index`); False, or shapes beyond the small-structure limits: built per batch by
         graph.EdgeStructure as for any other batch.
-        Layout facts a consumer of the PyG-like fields needs: `ptr` has spec[0] + 1 entries (entries past the real graphs
+        Layout facts a consumer of the PyG-like fields needs: `ptr` has spec.graphs + 1 entries (entries past the real graphs
         repeat the real node count); `batch` gives a PADDED node the id of a dedicated padding segment — the number of real
-        graphs of the current batch, which for a full batch equals spec[0] — so per-graph pooling over `batch` must be sized
-        `num_graphs` = spec[0] + 1 (what this buffer reports), and its last used row is the padding's."""
+        graphs of the current batch, which for a full batch equals spec.graphs — so per-graph pooling over `batch` must be sized
+        `num_graphs` = spec.graphs + 1 (what this buffer reports), and its last used row is the padding's."""
+        spec = PaddedSpec(*spec)
         g, n, e, b = spec
         dev = self.edge_index.device
-        i64 = torch.empty(2 * e + 2 * b + (g + 1) + n + 8 + g + 16, dtype=torch.int64, device=dev)
-        f32 = torch.empty(2 * e + n + 16, dtype=torch.float32, device=dev)
-        o = [0]
-
-        def take(buf, k):                       # segments start on 16-byte boundaries
-            v = buf[o[0]:o[0] + k]
-            o[0] += -(-k * buf.element_size() // 16) * 16 // buf.element_size()
-            return v
-        ei, nb = take(i64, 2 * e).view(2, e), take(i64, 2 * b).view(2, b)
-        ptr, bid, live, ids = take(i64, g + 1), take(i64, n), take(i64, 8), take(i64, g)
+        ei, nb, ptr, bid, live, ids = carve(torch.int64, dev, [2 * e, 2 * b, g + 1, n, 8, g])
         ids.fill_(-1)
         live.zero_()
-        o[0] = 0
-        w, y, x = take(f32, e), take(f32, e), take(f32, n).view(n, 1)
+        w, y, x = carve(torch.float32, dev, [e, e, n])
         hints = {"sim": {"valid_ids": True, "sorted_by_src": self._host().sorted_by_src, "band_width": 0},
                  "nb": {"valid_ids": True, "band_width": 0}}
-        buf = SimpleNamespace(_pangnn_hints=hints, x=x, edge_index=ei, edge_attr=w, y=y, neighbour_edge_index=nb, ptr=ptr,
-                              batch=bid, live=live, live_edges=live[:1], graph_ids=ids, spec=tuple(spec), num_graphs=g + 1,
-                              orders=None)
-        from . import _lib
+        buf = SimpleNamespace(_pangnn_hints=hints, x=x.view(n, 1), edge_index=ei.view(2, e), edge_attr=w, y=y,
+                              neighbour_edge_index=nb.view(2, b), ptr=ptr, batch=bid, live=live, live_edges=live[:1],
+                              graph_ids=ids, spec=spec, num_graphs=g + 1, orders=None)
         lib = _lib.load()
         if orders and dev.type == "cuda" and lib.pangnn_structure_small_supported(e, n) \
                 and lib.pangnn_structure_small_supported(b, n):
-            buf.orders = self._order_buffers(lib, n, e, b, dev)
+            buf.orders = self._order_buffers(n, e, b, dev)
         return buf
 
-    def _order_buffers(self, lib, n, e, b, dev):
+    def _order_buffers(self, n, e, b, dev):
         """device tables of the four CSR orders of a padded batch + the ctypes descriptor the collation takes"""
-        import ctypes
-
-        class Order(ctypes.Structure):
-            _fields_ = [(k, ctypes.c_void_p) for k in ("rank", "rowptr", "other", "perm", "keys", "part_off", "part_rowptr",
-                                                       "last_part")]
-
-        class Orders(ctypes.Structure):
-            _fields_ = [("chunk_edges", ctypes.c_int32), ("sim_dst", Order), ("sim_src", Order), ("nb_dst", Order),
-                        ("nb_src", Order)]
-        ct = int(lib.pangnn_decoder_chunk_tiles_for(e))
-        span = 32 * ct
-        nc = (e + span - 1) // span
+        ct = chunk_tiles_for(e)
+        nc = n_chunks(e, ct)
         rk = self.structure_index()
-        al = lambda k, m: -(-k // m) * m                                        # noqa: E731
-        ea, ba, na, ca = al(e, 4), al(b, 4), al(n + 1, 2), al(nc, 4)
-        i32 = torch.empty(6 * ea + 6 * ba + 2 * ca, dtype=torch.int32, device=dev)
-        i64 = torch.empty(6 * na + 4, dtype=torch.int64, device=dev)
+        # order after order: other, perm, keys (+ part_off: the similarity list's plans) | rowptr (+ part_rowptr); behind
+        # them each plan's last_part, in a 16-byte slot of its own
+        i32 = iter(carve(torch.int32, dev, [e, e, e, nc] * 2 + [b] * 6))
+        i64 = iter(carve(torch.int64, dev, [n + 1] * 6 + [1, 1]))
         seg = {}
-        o32 = o64 = 0
-        for name, m, ma in (("sim_dst", e, ea), ("sim_src", e, ea), ("nb_dst", b, ba), ("nb_src", b, ba)):
-            t = {}
-            for f in ("other", "perm", "keys"):
-                t[f] = i32[o32:o32 + m]
-                o32 += ma
-            t["rowptr"] = i64[o64:o64 + n + 1]
-            o64 += na
-            if name.startswith("sim"):
-                t["part_off"] = i32[o32:o32 + nc]
-                o32 += ca
-                t["part_rowptr"] = i64[o64:o64 + n + 1]
-                o64 += na
-                t["last_part"] = i64[6 * na + (0 if name == "sim_dst" else 2):][:1]
-            seg[name] = t
-        desc = Orders()
-        desc.chunk_edges = span
         for name in ("sim_dst", "sim_src", "nb_dst", "nb_src"):
+            t = seg[name] = {"other": next(i32), "perm": next(i32), "keys": next(i32), "rowptr": next(i64)}
+            if name.startswith("sim"):
+                t["part_off"], t["part_rowptr"] = next(i32), next(i64)
+        seg["sim_dst"]["last_part"], seg["sim_src"]["last_part"] = i64
+        desc = BatchOrders(chunk_edges=32 * ct)
+        for name, t in seg.items():
             o = getattr(desc, name)
             o.rank = getattr(rk, name).data_ptr()
-            for f in ("rowptr", "other", "perm", "keys", "part_off", "part_rowptr", "last_part"):
-                setattr(o, f, seg[name][f].data_ptr() if f in seg[name] else None)
-        return SimpleNamespace(desc=desc, tables=seg, chunk_tiles=ct, n_chunks=nc, _keep=(i32, i64, rk))
+            for f, table in t.items():
+                setattr(o, f, table.data_ptr())
+        return SimpleNamespace(desc=desc, tables=seg, chunk_tiles=ct, n_chunks=nc, _keep=rk)
 
     def _structures_of(self, buf):
         """graph.EdgeStructure objects of the batch's two edge lists over the order tables the collation wrote"""
-        from .graph import CSR, EdgeStructure, RunPlan
-        g, n, e, b = buf.spec
-        ct, nc = buf.orders.chunk_tiles, buf.orders.n_chunks
+        spec, ct = buf.spec, buf.orders.chunk_tiles
+        n_bound = part_bound(spec.nodes, spec.edges, ct)
         out = {}
-        for name, ei, m in (("sim", buf.edge_index, e), ("nb", buf.neighbour_edge_index, b)):
+        for name, ei in (("sim", buf.edge_index), ("nb", buf.neighbour_edge_index)):
             td, ts = buf.orders.tables[name + "_dst"], buf.orders.tables[name + "_src"]
             plans = None if name != "sim" else {
-                (by, ct): RunPlan(nc + min(n, m), t["part_off"], t["part_rowptr"], t["keys"], ct, t["last_part"])
+                (by, ct): RunPlan(n_bound, t["part_off"], t["part_rowptr"], t["keys"], ct, t["last_part"])
                 for by, t in (("dst", td), ("src", ts))}
             # (a collated batch of small sub-graphs: short rows)
-            out[name] = EdgeStructure(ei, n, hints=buf._pangnn_hints[name]).adopt_tables(
+            out[name] = EdgeStructure(ei, spec.nodes, hints=buf._pangnn_hints[name]).adopt_tables(
                 CSR(td["rowptr"], td["other"], td["perm"]), CSR(ts["rowptr"], ts["other"], ts["perm"]), plans)
         return out
 
     def collate_padded(self, buf):
         """(re)fill the padded batch `buf` from the sub-graph ids in buf.graph_ids (device): ONE launch, no host read-back;
         capturable — a replay collates whatever ids the list holds at that moment"""
-        import ctypes
-        from . import _lib
         lib = _lib.load()
         g, n, e, b = buf.spec
         src_ei, src_nb = self.edge_index, self.neighbour_edge_index
@@ -468,13 +462,11 @@ class SubGraphDataset:
                 "pangnn_collate_subgraphs_padded")
         # what is cached on the batch object belongs to the previous content of the buffers (same addresses): replace it
         # by the structures over the tables this collation wrote, or drop it (built on first use as for any batch)
-        from .graph import forget, structure_key
         for ei in (buf.edge_index, buf.neighbour_edge_index):        # only THIS batch's entries of the identity-keyed cache
             forget(structure_key(ei, n), ei)
         if buf.orders is None:
             buf.__dict__.pop("_pangnn_structs", None)
         else:
-            from .graph import register
             sts = self._structures_of(buf)
             buf._pangnn_structs = {name: (structure_key(st.edge_index, st.num_nodes), st) for name, st in sts.items()}
             for st in sts.values():
@@ -482,23 +474,18 @@ class SubGraphDataset:
         return buf
 
     def set_graph_ids(self, buf, ids):
-        """hand the next batch's sub-graph ids (host ints, at most buf.spec[0] and 64) to the device list: one tiny launch whose
-        arguments carry the values (no staging buffer that a later call could overwrite before it is read); returns the
+        """hand the next batch's sub-graph ids (host ints, at most buf.spec.graphs and 64) to the device list: one tiny launch
+        whose arguments carry the values (no staging buffer that a later call could overwrite before it is read); returns the
         batch's real (nodes, edges, neighbour edges) — host arithmetic"""
-        import ctypes
-        from . import _lib
-        g = buf.spec[0]
+        spec, g = buf.spec, buf.spec.graphs
         ids = [int(i) for i in ids]
         if not 0 < len(ids) <= min(g, 64) or g > 64:
             raise ValueError(f"a padded batch takes 1..{min(g, 64)} sub-graph ids")
         if min(ids) < 0 or max(ids) >= self.num_graphs:
             raise ValueError("sub-graph id out of range")
-        h = self._host()
-        n = sum(h.node[i + 1] - h.node[i] for i in ids)
-        e = sum(h.edge[i + 1] - h.edge[i] for i in ids)
-        b = sum(h.nb[i + 1] - h.nb[i] for i in ids)
-        if n >= buf.spec[1] or e > buf.spec[2] or b > buf.spec[3]:
-            raise ValueError(f"batch ({n} nodes, {e} edges, {b} neighbour edges) does not fit the padded shapes {buf.spec}")
+        n, e, b = self._counts(ids)
+        if n >= spec.nodes or e > spec.edges or b > spec.nb_edges:
+            raise ValueError(f"batch ({n} nodes, {e} edges, {b} neighbour edges) does not fit the padded shapes {tuple(spec)}")
         vals = (ctypes.c_int64 * g)(*(ids + [-1] * (g - len(ids))))
         with _lib.device_guard(buf.graph_ids.device):
             _lib.check(_lib.load().pangnn_set_i64(buf.graph_ids.data_ptr(), ctypes.cast(vals, ctypes.c_void_p), g,

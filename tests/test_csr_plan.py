@@ -134,6 +134,117 @@ def test_a_rectangular_structure(monkeypatch):
         assert sts[0][0].part_rowptr.shape[0] == n_dst + 1 and sts[0][1].part_rowptr.shape[0] == n_src + 1
 
 
+# ------------------------------------------------------------------------------------------------------------------
+# the packed sites (graph.carve): every table aligned, disjoint from its neighbours, and the general route's table
+# ------------------------------------------------------------------------------------------------------------------
+def _general_tables(ei, n, ct):
+    """{"dst" | "src": (CSR, plan)} of a device list by the general route: build_csr and _plan_of_sorted_keys"""
+    out = {}
+    for by, row in (("dst", 1), ("src", 0)):
+        csr = G.build_csr(ei, n, row)
+        out[by] = csr, EdgeStructure._plan_of_sorted_keys(ei[row][csr.perm.long()], n, ct)
+    return out
+
+
+def _csr_equal(got, want, what):
+    for f in ("rowptr", "other", "perm"):
+        a, b = getattr(got, f), getattr(want, f)
+        assert a.dtype == b.dtype and a.shape == b.shape and torch.equal(a, b), (what, f)
+
+
+def _aligned_and_disjoint(tables, what):
+    """the tensors of one packed site: each starts on 16 bytes, no two share a byte"""
+    spans = sorted((t.data_ptr(), t.data_ptr() + t.numel() * t.element_size()) for t in tables if t.numel())
+    assert len(spans) == len(tables) and all(lo % 16 == 0 for lo, _ in spans), what
+    assert all(a[1] <= b[0] for a, b in zip(spans, spans[1:])), what
+
+
+def _plan_tables(plan):
+    return [plan.part_off, plan.part_rowptr, plan.keys, plan.last]
+
+
+def _two_sub_graphs(ei, n):
+    """sub-graphs of n and n + 1 nodes (so the batch's row pointers have an odd length) over the list and its front part"""
+    from types import SimpleNamespace
+    from pangnn_amd.subgraphs import SubGraphDataset
+    e = ei.shape[1]
+    subs = []
+    for nodes, edges, nb in ((n, ei, ei.flip(0)[:, :(e + 1) // 2]), (n + 1, ei[:, :max(e - 1, 1)], ei.flip(0))):
+        k = edges.shape[1]
+        subs.append(SimpleNamespace(x=torch.ones(nodes, 1), edge_index=edges, neighbour_edge_index=nb,
+                                    edge_attr=torch.arange(1, k + 1, dtype=torch.float32), y=torch.zeros(k)))
+    return SubGraphDataset.from_data_list(subs, device=DEV)
+
+
+@pytest.mark.parametrize("n,e", [(1, 1), (2, 3), (7, 5), (6, 33), (97, 1000)])
+def test_every_packed_site_hands_out_aligned_disjoint_tables_of_the_general_route(n, e, monkeypatch):
+    """segment lengths that are no multiple of their alignment unit (N + 1 odd, E below and just past one tile), through the
+    small build, `filtered` with both orders held, gcn_norm with and without weights and a padded batch's order tables"""
+    host_ei, host_w = random_graph(n, e, seed=n + e)
+    ei, w = host_ei.to(DEV), host_w.to(DEV)
+    ct = G.chunk_tiles_for(e)
+    monkeypatch.setattr(G, "SMALL_STRUCTURE", False)
+    monkeypatch.setattr(G, "PLAN_KERNEL", False)
+    want = _general_tables(ei, n, ct)
+    general = EdgeStructure(ei.clone(), n)
+    assert general.by_dst is not None and not general._small_built
+
+    monkeypatch.setattr(G, "SMALL_STRUCTURE", True)              # the small build
+    st = EdgeStructure(ei, n)
+    got = {"dst": (st.by_dst, st.csr_plan("dst", ct)), "src": (st.by_src, st.csr_plan("src", ct))}
+    assert st._small_built
+    for by in ("dst", "src"):
+        _csr_equal(got[by][0], want[by][0], ("small", by))
+        plans_equal(got[by][1], want[by][1], ("small", by))
+    _aligned_and_disjoint([t for c, p in got.values() for t in [c.rowptr, c.other, c.perm] + _plan_tables(p)], "small")
+
+    keep = (torch.arange(e) % 3 != 1).to(DEV)                    # filtered, both orders held by the parent
+    child, kept_id, _ = EdgeStructure.filtered(st, keep)
+    k = child.num_edges
+    assert k == int(keep.sum()) > 0 and child._by_src is not None and child.filter_state.tolist() == [k, 0]
+    assert torch.equal(child.edge_index, ei[:, keep]) and torch.equal(kept_id.long(), torch.nonzero(keep).view(-1))
+    of_child = _general_tables(child.edge_index, n, 1)
+    _csr_equal(child._by_dst, of_child["dst"][0], "filtered dst")
+    _csr_equal(child._by_src, of_child["src"][0], "filtered src")
+    _aligned_and_disjoint([t for c in (child._by_dst, child._by_src) for t in (c.rowptr, c.other, c.perm)]
+                          + [child.filter_state], "filtered")
+
+    for weight in (None, w):                                      # gcn_norm
+        a, b = st.gcn_norm(weight), general.gcn_norm(weight)
+        tables = [(x.deg_inv_sqrt, x.by_dst, x.orig, x.by_src) for x in (a, b)]
+        assert a._by_src_buf is not None and a.by_src is a._by_src_buf
+        for f, ta, tb in zip(("deg_inv_sqrt", "by_dst", "orig", "by_src"), *tables):
+            assert ta.dtype == tb.dtype == torch.float32 and ta.shape == tb.shape and torch.equal(ta, tb), ("norm", f)
+        assert bool(torch.isfinite(torch.cat(tables[0])).all())
+        _aligned_and_disjoint(tables[0], "norm")
+
+    ds = _two_sub_graphs(host_ei, n)                             # a padded batch's order tables
+    spec = ds.padded_spec(2)
+    assert spec.nodes == 2 * n + 2 and spec.edges == e + max(e - 1, 1)
+    buf = ds.padded_buffers(spec)
+    assert buf.orders is not None
+    ds.set_graph_ids(buf, [1, 0])
+    ds.collate_padded(buf)
+    pct = buf.orders.chunk_tiles
+    assert pct == G.chunk_tiles_for(spec.edges) and buf.orders.n_chunks == G.n_chunks(spec.edges, pct)
+    packed = [buf.edge_index, buf.neighbour_edge_index, buf.ptr, buf.batch, buf.live, buf.graph_ids, buf.edge_attr, buf.y, buf.x]
+    for name, lst in (("sim", buf.edge_index), ("nb", buf.neighbour_edge_index)):
+        of_batch = _general_tables(lst.clone(), spec.nodes, pct)
+        made = buf._pangnn_structs[name][1]
+        for by in ("dst", "src"):
+            t = buf.orders.tables[f"{name}_{by}"]
+            csr = made.by_dst if by == "dst" else made.by_src
+            assert csr.rowptr is t["rowptr"] and csr.other is t["other"] and csr.perm is t["perm"]
+            _csr_equal(csr, of_batch[by][0], (name, by))
+            assert t["keys"].dtype == torch.int32 and torch.equal(t["keys"], of_batch[by][1].keys), (name, by)
+            assert ("part_off" in t) == ("part_rowptr" in t) == ("last_part" in t) == (name == "sim")
+            if name == "sim":
+                plans_equal(made.csr_plan(by, pct), of_batch[by][1], (name, by))
+                assert made.csr_plan(by, pct).last is t["last_part"]
+            packed += list(t.values())
+    _aligned_and_disjoint(packed, "padded batch")
+
+
 def _sub_sampled_step(skip, kernel, monkeypatch):
     G.clear_cache()
     monkeypatch.setattr(G, "PLAN_KERNEL", kernel)
