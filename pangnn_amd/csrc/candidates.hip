@@ -23,13 +23,6 @@ __device__ __forceinline__ float neg_inf<float>() { return -INFINITY; }
 template <>
 __device__ __forceinline__ double neg_inf<double>() { return -(double)INFINITY; }
 
-template <typename T>
-__device__ __forceinline__ T wave_max(T v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v = fmax(v, __shfl_xor(v, off));
-  return v;
-}
-
 // c[k] (valid in every lane) += number of lanes whose (label, prediction) pair is k, for the lanes with `on` set
 __device__ __forceinline__ void count_lanes(bool on, bool lab, bool pred, unsigned int c[4]) {
   const unsigned long long l1 = __ballot(on && lab), p1 = __ballot(on && pred), all = __ballot(on);

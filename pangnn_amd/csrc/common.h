@@ -32,6 +32,33 @@ constexpr int kWave = 64;          // CDNA4 wavefront
 constexpr int kBlock = 256;        // 4 waves per workgroup
 constexpr int kWavesPerBlock = kBlock / kWave;
 
+// ---- host side: launch geometry, workspace carving and the argument checks that several entry points share
+// compute units of the current device; 256 (an MI355X) where the query fails
+inline int cu_count() {
+  int dev = 0, v = 0;
+  if (hipGetDevice(&dev) == hipSuccess &&
+      hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
+    return v;
+  return 256;
+}
+inline int64_t blocks_for(int64_t items, int per_block) { return (items + per_block - 1) / per_block; }
+// workgroups of kBlock threads for `work` items of a grid-stride kernel: at least one, at most `cap` (each file states its own)
+inline unsigned capped_grid(int64_t work, int64_t cap) {
+  const int64_t b = blocks_for(work, kBlock);
+  return (unsigned)(b < 1 ? 1 : b > cap ? cap : b);
+}
+// v >= 0 rounded up to a multiple of a
+template <typename T>
+constexpr T align_up(T v, int a) { return (v + (a - 1)) / a * a; }
+// the row widths of the gather kernels: G = F / 4 lanes per row, G a power of two that divides the wave
+inline bool row_width_ok(int32_t f) { return f == 16 || f == 32 || f == 64 || f == 128 || f == 256; }
+inline bool row_dtype_ok(int32_t t) { return t == PANGNN_DTYPE_F32 || t == PANGNN_DTYPE_BF16 || t == PANGNN_DTYPE_F16; }
+// every row starts on a lane's load width: 16 bytes (f32) / 8 bytes (2-byte rows), ld a multiple of 4 elements
+inline bool rows_aligned(const void* p, int32_t dtype, int64_t ld) {
+  const uintptr_t a = reinterpret_cast<uintptr_t>(p);
+  return ld % 4 == 0 && (dtype == PANGNN_DTYPE_F32 ? (a & 15u) == 0 : (a & 7u) == 0);
+}
+
 // Second stage of the two-stage reductions (per-workgroup partial rows -> one row), reproducible and short:
 // a 1024-thread block owns 64 consecutive elements; wave g adds parts g, g+16, g+32, ... in that order, then the
 // 16 wave sums are added in wave order.  (One thread walking all parts serially took 60-240 us per call.)
@@ -69,6 +96,63 @@ __device__ __forceinline__ uint2 f32_to_rows16(float v0, float v1, float v2, flo
   const __bf16 o[4] = {(__bf16)v0, (__bf16)v1, (__bf16)v2, (__bf16)v3};
   return *reinterpret_cast<const uint2*>(o);
 }
+
+// A lane's piece of a gathered row as stored: four consecutive elements (16 bytes of f32, 8 bytes of bf16 / f16; xf is the
+// PANGNN_DTYPE_* code) -> f32, exact.  PIN, for the kernels that multiply two gathered pieces (edge_score.hip,
+// edge_weight_grad.hip): half rows are f32 values first, so that no conversion is folded into a mixed / packed-dot instruction
+// (v_dot2_f32_f16, v_fma_mix_f32) that rounds differently from the f32 call on the up-converted rows.  The propagate of
+// spmm.hip deliberately has no pin: a piece meets nothing there but an fp32 weight in one fmaf.
+template <bool PIN>
+__device__ __forceinline__ float4 row_piece(const char* p, int xf) {
+  if (!xf) return *reinterpret_cast<const float4*>(p);
+  float4 r = rows16_to_f32(*reinterpret_cast<const uint2*>(p), xf);
+  if (PIN && xf == 2) asm volatile("" : "+v"(r.x), "+v"(r.y), "+v"(r.z), "+v"(r.w));
+  return r;
+}
+
+// the four products of two pieces in a fixed order
+__device__ __forceinline__ float dot4(float4 a, float4 b) {
+  return fmaf(a.w, b.w, fmaf(a.z, b.z, fmaf(a.y, b.y, a.x * b.x)));
+}
+
+// sum / maximum over every aligned group of G lanes by an xor butterfly (offsets G / 2 ... 1): a fixed order, and every lane
+// of a group ends with the same bits.  group_max is fmax's: a NaN operand is ignored.
+template <int G, typename T>
+__device__ __forceinline__ T group_sum(T v) {
+#pragma unroll
+  for (int off = G / 2; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+template <int G, typename T>
+__device__ __forceinline__ T group_max(T v) {
+#pragma unroll
+  for (int off = G / 2; off >= 1; off >>= 1) v = fmax(v, __shfl_xor(v, off));
+  return v;
+}
+template <typename T> __device__ __forceinline__ T wave_sum(T v) { return group_sum<kWave>(v); }
+template <typename T> __device__ __forceinline__ T wave_max(T v) { return group_max<kWave>(v); }
+
+// The row of a CSR that holds entry k (0 <= k < rowptr[n_rows]): the last r in [0, n_rows) with rowptr[r] <= k, hence
+// rowptr[r + 1] > k — among equal row pointers the non-empty row, empty rows are stepped over.  Always inside
+// [0, n_rows - 1], whatever rowptr holds.
+__device__ __forceinline__ int64_t row_of_entry(const int64_t* __restrict__ rowptr, int64_t n_rows, int64_t k) {
+  int64_t lo = 0, hi = n_rows;                 // invariant: rowptr[lo] <= k < rowptr[hi]
+  while (hi - lo > 1) {
+    const int64_t mid = lo + ((hi - lo) >> 1);
+    if (rowptr[mid] <= k) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+__device__ __forceinline__ void wave_lds_sync() {
+  // LDS operations of one wave execute in issue order; this only pins the compiler's ordering.
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// row of the 32x32 MFMA accumulator held in register r by a lane of half hh
+__device__ __forceinline__ constexpr int acc_row(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }
 
 __device__ __forceinline__ float ordered_parts_sum(const float* __restrict__ part, int n_parts, int64_t stride, int i,
                                                    int len) {

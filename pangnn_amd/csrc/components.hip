@@ -136,12 +136,6 @@ __global__ __launch_bounds__(kBlock) void components_compress_kernel(int32_t n, 
   }
 }
 
-unsigned grid_for(int64_t work) {
-  int64_t blocks = (work + kBlock - 1) / kBlock;
-  if (blocks > kCompMaxBlocks) blocks = kCompMaxBlocks;
-  return (unsigned)(blocks < 1 ? 1 : blocks);
-}
-
 }  // namespace
 }  // namespace pangnn
 
@@ -162,12 +156,13 @@ extern "C" int pangnn_components_i32(const int64_t* src, const int64_t* dst, con
   PG_CHECK_ARG((src != nullptr && dst != nullptr) || num_edges == 0, PANGNN_E_BADARG, "%s: null edge list", name);
   hipStream_t s = (hipStream_t)stream;
   const int32_t n = (int32_t)num_nodes;
-  hipLaunchKernelGGL(components_init_kernel, dim3(grid_for(num_nodes)), dim3(kBlock), 0, s, n, labels, touched, status);
+  hipLaunchKernelGGL(components_init_kernel, dim3(capped_grid(num_nodes, kCompMaxBlocks)), dim3(kBlock), 0, s, n, labels,
+                     touched, status);
   PG_CHECK_LAUNCH(name);
   if (num_edges == 0) return 0;
   const int vec = keep_itemsize != 0 && aligned16(keep);
   const int64_t work = keep_itemsize && vec ? (num_edges + 16 / keep_itemsize - 1) / (16 / keep_itemsize) : num_edges;
-  const dim3 grid(grid_for(work));
+  const dim3 grid(capped_grid(work, kCompMaxBlocks));
   if (keep_itemsize == 0)
     hipLaunchKernelGGL(components_hook_kernel<0>, grid, dim3(kBlock), 0, s, src, dst, nullptr, 0, num_edges, n, labels,
                        touched, status);
@@ -179,7 +174,7 @@ extern "C" int pangnn_components_i32(const int64_t* src, const int64_t* dst, con
                        touched, status);
   PG_CHECK_LAUNCH(name);
   if (num_nodes == 0) return 0;
-  hipLaunchKernelGGL(components_compress_kernel, dim3(grid_for(num_nodes)), dim3(kBlock), 0, s, n, labels);
+  hipLaunchKernelGGL(components_compress_kernel, dim3(capped_grid(num_nodes, kCompMaxBlocks)), dim3(kBlock), 0, s, n, labels);
   PG_CHECK_LAUNCH(name);
   return 0;
 }

@@ -39,8 +39,6 @@ namespace {
 constexpr int kPlanTile = 4 * kBlock;           // entries per workgroup step: four consecutive ones per thread
 constexpr int kPlanMaxBlocks = 2048;            // a memory-bound stream: 8 workgroups per CU, grid-stride the rest
 
-size_t plan_align256(size_t v) { return (v + 255) / 256 * 256; }
-
 // item r of the scan: row r starts a part inside a chunk
 struct StartsInsideChunk {
   const int64_t* rowptr;
@@ -62,18 +60,6 @@ size_t plan_scan_temp_bytes(int64_t items) {
   return b;
 }
 
-// the row that holds entry q: the last r in [0, n) with rowptr[r] <= q (rowptr[r + 1] > q: among equal row pointers the
-// non-empty row).  Always inside [0, n - 1], whatever rowptr holds.
-__device__ __forceinline__ int32_t row_of_entry(const int64_t* __restrict__ rowptr, int64_t n, int64_t q) {
-  int64_t lo = 0, hi = n;                       // first r in [1, n] with rowptr[r] > q is in (lo, hi]
-  while (hi - lo > 1) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (rowptr[mid] <= q) lo = mid;
-    else hi = mid;
-  }
-  return (int32_t)lo;
-}
-
 __global__ __launch_bounds__(kBlock) void csr_plan_kernel(
     const int64_t* __restrict__ rowptr, const int32_t* __restrict__ cin, int64_t e, int64_t n, int64_t span,
     int32_t* __restrict__ keys, int32_t* __restrict__ part_off, int64_t* __restrict__ part_rowptr,
@@ -86,7 +72,7 @@ __global__ __launch_bounds__(kBlock) void csr_plan_kernel(
   for (int64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
     const int64_t q0 = t * kPlanTile;
     const int len = (int)(e - q0 < kPlanTile ? e - q0 : kPlanTile);
-    if (tid < 2) ends[tid] = row_of_entry(rowptr, n, tid == 0 ? q0 : q0 + len - 1);
+    if (tid < 2) ends[tid] = (int32_t)row_of_entry(rowptr, n, tid == 0 ? q0 : q0 + len - 1);   // n < 2^31
     reinterpret_cast<int4*>(mark)[tid] = make_int4(0, 0, 0, 0);
     __syncthreads();
     const int32_t lo = ends[0], hi = ends[1];
@@ -206,7 +192,7 @@ extern "C" int64_t pangnn_csr_plan_workspace_bytes(int64_t n_rows) {
   if (n_rows < 1 || n_rows >= ((int64_t)1 << 31)) return 0;
   const size_t t = plan_scan_temp_bytes(n_rows);
   if (t == (size_t)-1) return 0;
-  return (int64_t)(plan_align256((size_t)n_rows * 4) + plan_align256(t));
+  return (int64_t)(align_up((size_t)n_rows * 4, 256) + align_up(t, 256));
 }
 
 extern "C" int pangnn_csr_plan(const int64_t* rowptr, int64_t n_rows, int64_t num_edges, int32_t span, int32_t* keys,
@@ -227,13 +213,13 @@ extern "C" int pangnn_csr_plan(const int64_t* rowptr, int64_t n_rows, int64_t nu
   PG_CHECK_ARG((p8 & 7u) == 0 && (p4 & 3u) == 0, PANGNN_E_ALIGN, "%s: a pointer is not aligned to its element size", name);
   const size_t temp = plan_scan_temp_bytes(n);
   PG_CHECK_ARG(temp != (size_t)-1, PANGNN_E_BADARG, "%s: rocPRIM size query failed", name);
-  const size_t seg = plan_align256((size_t)n * 4);
-  PG_CHECK_ARG(workspace_bytes >= 0 && (size_t)workspace_bytes >= seg + plan_align256(temp), PANGNN_E_WORKSPACE,
-               "%s: workspace too small (%lld < %zu)", name, (long long)workspace_bytes, seg + plan_align256(temp));
+  const size_t seg = align_up((size_t)n * 4, 256);
+  PG_CHECK_ARG(workspace_bytes >= 0 && (size_t)workspace_bytes >= seg + align_up(temp, 256), PANGNN_E_WORKSPACE,
+               "%s: workspace too small (%lld < %zu)", name, (long long)workspace_bytes, seg + align_up(temp, 256));
   char* ws = static_cast<char*>(workspace);
   int32_t* cin = reinterpret_cast<int32_t*>(ws);
   hipStream_t s = (hipStream_t)stream;
-  size_t tb = plan_align256(temp);
+  size_t tb = align_up(temp, 256);
   const hipError_t err = scan_starts(ws + seg, tb, StartsInsideChunk{rowptr, span}, cin, n, s);
   PG_CHECK_ARG(err == hipSuccess, (int)err, "%s: scan failed: %s", name, hipGetErrorString(err));
   const int64_t n_tiles = (e + kPlanTile - 1) / kPlanTile, row_blocks = (n + kBlock) / kBlock;

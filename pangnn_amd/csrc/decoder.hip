@@ -63,16 +63,6 @@ struct Shape {
   static_assert(SLAB <= WAVES * PER_WAVE, "the slab is reduced in the tile area");
 };
 
-__device__ __forceinline__ void wave_lds_sync() {
-  // LDS operations of one wave execute in issue order; this only pins the compiler's ordering.
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// row of the 32x32 MFMA accumulator held in register r by a lane of half hh
-__device__ __forceinline__ constexpr int jr(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }
-
 struct DecParams {
   const float* p; const float* q; uint32_t ldp4; uint32_t ldq4;   // row strides in float4 units
   const int64_t* ei; int64_t ld; int64_t E;
@@ -169,7 +159,7 @@ __device__ __forceinline__ void gather_tile(const DecParams& a, int64_t ebase, i
   }
 }
 
-// ---- C[j][e] = sum_k W2[j][k] h1[e][k]; lane (e = lane&31, hh = lane>>5) gets rows jr(i,hh) + 32b in acc[b][i].
+// ---- C[j][e] = sum_k W2[j][k] h1[e][k]; lane (e = lane&31, hh = lane>>5) gets rows acc_row(i,hh) + 32b in acc[b][i].
 // Half hh of the wave feeds k = (D/2) hh + 0 .. D/2 - 1, one k of each half per instruction.
 template <int D>
 __device__ __forceinline__ void gemm1(const float* Wl, const float* Ht, int lane, f32x16 (&acc)[Shape<D>::NB]) {
@@ -361,7 +351,7 @@ __global__ __launch_bounds__(Shape<D>::WAVES * 64) void decoder_bwd_kernel(
   __syncthreads();
   const int hh = lane >> 5, r = lane & 31;
 
-  f32x16 acc3[NJ][NB];   // gW2[j = jr(i,hh) + 32 (COOP ? wave : bj)][k = r + 32bk]
+  f32x16 acc3[NJ][NB];   // gW2[j = acc_row(i,hh) + 32 (COOP ? wave : bj)][k = r + 32bk]
 #pragma unroll
   for (int bj = 0; bj < NJ; ++bj)
 #pragma unroll
@@ -383,7 +373,7 @@ __global__ __launch_bounds__(Shape<D>::WAVES * 64) void decoder_bwd_kernel(
   const float pw = (FUSED_LOSS && lp.pos_weight) ? lp.pos_weight[0] : 1.f;
 
   // what a tile carries from its front half (forward recomputation) to its back half (dL/dh1)
-  f32x16 acc[NB];      // h2[j][e], lane (e = r, hh), rows jr(i,hh) + 32b
+  f32x16 acc[NB];      // h2[j][e], lane (e = r, hh), rows acc_row(i,hh) + 32b
   float g_e = 0.f;
   int id = 0;
 
@@ -493,20 +483,20 @@ __global__ __launch_bounds__(Shape<D>::WAVES * 64) void decoder_bwd_kernel(
       for (int b = 0; b < NB; ++b)
 #pragma unroll
         for (int i = 0; i < 16; ++i)
-          acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(acc[b][i], Wl[(32 * b + jr(i, hh)) * RS + r + 32 * bp], acc2, 0, 0, 0);
+          acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(acc[b][i], Wl[(32 * b + acc_row(i, hh)) * RS + r + 32 * bp], acc2, 0, 0, 0);
       // mask by h1 > 0, write dL/dh1pre (full tiles store through one lane base pointer + compile-time offsets: no
       // per-element bounds test or address arithmetic), accumulate gcvec
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
-        const int e = jr(i, hh);
+        const int e = acc_row(i, hh);
         const float hval = Ht[e * RS + r + 32 * bp];
         const float v = hval <= 0.f ? 0.f : acc2[i];
-        if (full || ebase + e < a.E) __builtin_nontemporal_store(v, &gout[jr(i, 0) * D + 32 * bp]);   // written once
+        if (full || ebase + e < a.E) __builtin_nontemporal_store(v, &gout[acc_row(i, 0) * D + 32 * bp]);   // written once
         acc2[i] = v;
       }
       if (has_extra) {
 #pragma unroll
-        for (int i = 0; i < 16; ++i) gcv[bp] = fmaf(wl[jr(i, hh)], acc2[i], gcv[bp]);
+        for (int i = 0; i < 16; ++i) gcv[bp] = fmaf(wl[acc_row(i, hh)], acc2[i], gcv[bp]);
       }
       if (RUNSUM) {
         if (one_run) {
@@ -521,7 +511,7 @@ __global__ __launch_bounds__(Shape<D>::WAVES * 64) void decoder_bwd_kernel(
           float s0 = 0.f, s1 = 0.f;
 #pragma unroll
           for (int i = 0; i < 16; ++i) {
-            const bool first = jr(i, hh) <= bnd;
+            const bool first = acc_row(i, hh) <= bnd;
             s0 += first ? acc2[i] : 0.f;
             s1 += first ? 0.f : acc2[i];
           }
@@ -535,7 +525,7 @@ __global__ __launch_bounds__(Shape<D>::WAVES * 64) void decoder_bwd_kernel(
           // three or more runs: the block's dL/dh1 values replace the h1 values they were masked with (same lane, same
           // address; the other blocks' columns stay)
 #pragma unroll
-          for (int i = 0; i < 16; ++i) Ht[jr(i, hh) * RS + r + 32 * bp] = acc2[i];
+          for (int i = 0; i < 16; ++i) Ht[acc_row(i, hh) * RS + r + 32 * bp] = acc2[i];
         }
       }
       if (D == 128) __builtin_amdgcn_sched_barrier(0);     // one block's loads in flight at a time: registers
@@ -575,7 +565,7 @@ __global__ __launch_bounds__(Shape<D>::WAVES * 64) void decoder_bwd_kernel(
 #pragma unroll
       for (int b = 0; b < NB; ++b) {
 #pragma unroll
-        for (int i = 0; i < 16; ++i) Gt[jr(i, hh) * GS + r] = acc[b][i];
+        for (int i = 0; i < 16; ++i) Gt[acc_row(i, hh) * GS + r] = acc[b][i];
         wave_lds_sync();
         wgrad_block(Ht, Gt, gl, b);
         wave_lds_sync();   // the next block overwrites Gt
@@ -608,7 +598,7 @@ __global__ __launch_bounds__(Shape<D>::WAVES * 64) void decoder_bwd_kernel(
             float v = acc[0][i];
 #pragma unroll
             for (int b = 1; b < NB; ++b) v = pb == b ? acc[b][i] : v;
-            Gt[jr(i, hh) * GS + r] = v;
+            Gt[acc_row(i, hh) * GS + r] = v;
           }
         }
         __syncthreads();
@@ -646,7 +636,7 @@ __global__ __launch_bounds__(Shape<D>::WAVES * 64) void decoder_bwd_kernel(
 #pragma unroll
     for (int bk = 0; bk < NB; ++bk)
 #pragma unroll
-      for (int i = 0; i < 16; ++i) red[(32 * wave + jr(i, hh)) * D + r + 32 * bk] = acc3[0][bk][i];
+      for (int i = 0; i < 16; ++i) red[(32 * wave + acc_row(i, hh)) * D + r + 32 * bk] = acc3[0][bk][i];
     if (hh == 0) {
       red[D * D + 32 * wave + r] = gb2p[0];
       red[D * D + D + 32 * wave + r] = gw3p[0];
@@ -662,7 +652,7 @@ __global__ __launch_bounds__(Shape<D>::WAVES * 64) void decoder_bwd_kernel(
           for (int bk = 0; bk < NB; ++bk)
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
-              const int idx = (32 * bj + jr(i, hh)) * D + r + 32 * bk;
+              const int idx = (32 * bj + acc_row(i, hh)) * D + r + 32 * bk;
               red[idx] = (first ? 0.f : red[idx]) + acc3[bj][bk][i];
             }
       }

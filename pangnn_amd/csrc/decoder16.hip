@@ -190,12 +190,6 @@ __device__ __forceinline__ uint32_t nz16x2(uint32_t x, uint32_t one2) {
   return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_bit_cast(u16x2, x), __builtin_bit_cast(u16x2, one2)));
 }
 
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 typedef __attribute__((address_space(3))) short4v lds_s4;
 __device__ __forceinline__ short4v ld_tr4(const char* lds_base, int off) {
   return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(lds_base + off));
@@ -443,14 +437,14 @@ __device__ __forceinline__ void run_sums(const f32x4 (&v)[4], const f32x4 (&gm)[
   } else {
     // three or more runs: the tile goes through LDS (the tile images are free at this point) as [16][64] floats,
     // the carried sum as row 16; lane = column walks the rows
-    wave_sync();
+    wave_lds_sync();
     float* tile = reinterpret_cast<float*>(wv);
 #pragma unroll
     for (int kb = 0; kb < 4; ++kb)
 #pragma unroll
       for (int i = 0; i < 4; ++i) tile[(4 * g + i) * 64 + 16 * kb + c] = v[kb][i] * gm[kb][i];
     tile[16 * 64 + colp] = carry;
-    wave_sync();
+    wave_lds_sync();
     float sum = tile[16 * 64 + lane];
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
@@ -461,11 +455,11 @@ __device__ __forceinline__ void run_sums(const f32x4 (&v)[4], const f32x4 (&gm)[
         ++pidx;
       }
     }
-    wave_sync();
+    wave_lds_sync();
     tile[lane] = sum;                  // the open remainder back into the carry layout
-    wave_sync();
+    wave_lds_sync();
     carry = tile[colp];
-    wave_sync();
+    wave_lds_sync();
   }
 }
 
@@ -693,7 +687,7 @@ __global__ __launch_bounds__(S_WAVES * 64) void decoder_train16_kernel(
     }
   }
 
-  f32x16 acc3[2][2];                       // sum_e m2[j][e] g_e h1[e][k]:  j = 32 mb + jr(i, h), k = 32 nb + (lane & 31)
+  f32x16 acc3[2][2];                       // sum_e m2[j][e] g_e h1[e][k]:  j = 32 mb + acc_row(i, h), k = 32 nb + (lane & 31)
 #pragma unroll
   for (int x = 0; x < 2; ++x)
 #pragma unroll
@@ -843,7 +837,7 @@ __global__ __launch_bounds__(S_WAVES * 64) void decoder_train16_kernel(
         }
       };
       write_hg(0);
-      wave_sync();
+      wave_lds_sync();
 #pragma unroll
       for (int mb = 0; mb < 2; ++mb) am[mb] = ld_tr8(wv + WV_M2, tr3h[0] ^ (mb << 6), tr3h[1] ^ (mb << 6));
       __builtin_amdgcn_s_setprio(1);
@@ -862,7 +856,7 @@ __global__ __launch_bounds__(S_WAVES * 64) void decoder_train16_kernel(
         *reinterpret_cast<uint32_t*>(r) = recw;
         *reinterpret_cast<uint32_t*>(r + 16) = __builtin_bit_cast(uint32_t, g_raw);
       }
-      wave_sync();
+      wave_lds_sync();
       p3_block(1);
       __builtin_amdgcn_s_setprio(0);
 
@@ -891,7 +885,7 @@ __global__ __launch_bounds__(S_WAVES * 64) void decoder_train16_kernel(
           run_sums(v, gm, m16, carry, rs.part, pidx, wv, lane, c, g, colp);
         }
       }
-      wave_sync();          // the next half tile overwrites the images / recl / gl
+      wave_lds_sync();          // the next half tile overwrites the images / recl / gl
       in_cur = in_nxt;
     }
     poff_cur = last_tile ? poff_nxt : poff_cur;
@@ -941,7 +935,7 @@ __global__ __launch_bounds__(S_WAVES * 64) void decoder_train16_kernel(
 #pragma unroll
   for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
-    for (int i = 0; i < 16; ++i) w3r[mb][i] = w3l[32 * mb + (i & 3) + 8 * (i >> 2) + 4 * hh];
+    for (int i = 0; i < 16; ++i) w3r[mb][i] = w3l[32 * mb + acc_row(i, hh)];
   __syncthreads();                                           // every wave is done with the weight / tile images
   float* buf = reinterpret_cast<float*>(lds);                // [4 writers][NV][64 lanes] = 88 KB of the 116 KB
   static_assert(4 * NV * 64 * 4 <= S_LDS, "tree buffers");
@@ -973,7 +967,7 @@ __global__ __launch_bounds__(S_WAVES * 64) void decoder_train16_kernel(
       for (int nb = 0; nb < 2; ++nb)
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-          const int j = 32 * mb + (i & 3) + 8 * (i >> 2) + 4 * hh;
+          const int j = 32 * mb + acc_row(i, hh);
           img[j * 64 + r + 32 * nb] = w3r[mb][i] * val[32 * mb + 16 * nb + i];
         }
     if (c == 0) {
@@ -1165,7 +1159,7 @@ __global__ __launch_bounds__(T_WAVES * 64) void decoder_dgrad16_kernel(
         }
       }
     }
-    wave_sync();
+    wave_lds_sync();
     if (RUN) {
       f32x4 v[2][4];
       dgrad_tile2(lds, a2, wfrag0, wfrag1, v);
@@ -1186,7 +1180,7 @@ __global__ __launch_bounds__(T_WAVES * 64) void decoder_dgrad16_kernel(
         run_sums(v[h], gm, m16, carry, rs.part, pidx, wv, lane, c, g, colp);
       }
     }
-    wave_sync();          // the next tile overwrites recl / gl
+    wave_lds_sync();          // the next tile overwrites recl / gl
 #pragma unroll
     for (int h = 0; h < 2; ++h) cur[h] = nxt[h];
     poff_cur = last_tile ? poff_nxt : poff_cur;
@@ -1345,15 +1339,6 @@ __global__ __launch_bounds__(kSumThreads) void gcv_reduce_kernel(const float* __
   const int i = threadIdx.x & (kWave - 1);
   const float s = ordered_parts_sum(slabs, n_slabs, 64, i, 64);
   if (threadIdx.x < kWave) g_cvec[i] = s;
-}
-
-static int cu_count() {
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) {
-    int v = 0;
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-  }
-  return cus;
 }
 }  // namespace pangnn
 

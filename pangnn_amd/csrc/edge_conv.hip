@@ -42,16 +42,6 @@ template <int OUT> struct Cfg {
   static constexpr int BWD_WAVES = OUT == 64 ? 4 : 2;      // W2 + two tiles per wave within 160 KiB of LDS
 };
 
-__device__ __forceinline__ void wave_lds_sync() {
-  // LDS operations of one wave execute in issue order; this only pins the compiler's ordering.
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// row of the 32x32 MFMA accumulator held in register r by a lane of half hh
-__device__ __forceinline__ constexpr int acc_row(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }
-
 // relu as torch computes it: a NaN stays a NaN (fmed3f / fmaxf would return 0), so that the max-aggregation sees it
 __device__ __forceinline__ float relu1(float x) { return x < 0.f ? 0.f : x; }
 
@@ -458,8 +448,6 @@ __global__ __launch_bounds__(kSumThreads) void edge_conv_slab_sum_kernel(const f
   if (threadIdx.x < kWave && i < len) gw2[i] = s;
 }
 
-int64_t round16(int64_t b) { return (b + 15) & ~(int64_t)15; }
-
 // scratch layout shared by the query and the launchers
 struct Scratch { int64_t head_row, head_val, head_arg, tail_val, tail_arg, win, slabs, total; };
 Scratch scratch_layout(int64_t num_edges, int out_dim, bool backward) {
@@ -467,14 +455,14 @@ Scratch scratch_layout(int64_t num_edges, int out_dim, bool backward) {
   const int64_t nc = cp.n_chunks > 0 ? cp.n_chunks : 1;
   Scratch s;
   int64_t off = 0;
-  s.head_row = off; off += round16(nc * 4);
-  s.head_val = off; off += round16(nc * out_dim * 4);
-  s.head_arg = off; off += backward ? 0 : round16(nc * out_dim * 4);
-  s.tail_val = off; off += round16(nc * out_dim * 4);
-  s.tail_arg = off; off += backward ? 0 : round16(nc * out_dim * 4);
-  s.win = off; off += backward ? round16(num_edges > 0 ? num_edges : 1) : 0;
+  s.head_row = off; off += align_up(nc * 4, 16);
+  s.head_val = off; off += align_up(nc * out_dim * 4, 16);
+  s.head_arg = off; off += backward ? 0 : align_up(nc * out_dim * 4, 16);
+  s.tail_val = off; off += align_up(nc * out_dim * 4, 16);
+  s.tail_arg = off; off += backward ? 0 : align_up(nc * out_dim * 4, 16);
+  s.win = off; off += backward ? align_up(num_edges > 0 ? num_edges : 1, 16) : 0;
   const int waves = out_dim == 64 ? Cfg<64>::BWD_WAVES : Cfg<128>::BWD_WAVES;
-  s.slabs = off; off += backward ? round16(((nc + waves - 1) / waves) * (int64_t)out_dim * out_dim * 4) : 0;
+  s.slabs = off; off += backward ? align_up(((nc + waves - 1) / waves) * (int64_t)out_dim * out_dim * 4, 16) : 0;
   s.total = off;
   return s;
 }

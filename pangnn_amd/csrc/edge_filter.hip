@@ -29,14 +29,6 @@ namespace {
 
 constexpr int kFilterMaxBlocks = 2048;          // memory-bound streams: 8 workgroups per CU, grid-stride the rest
 
-unsigned filter_grid(int64_t work) {
-  int64_t b = (work + kBlock - 1) / kBlock;
-  if (b > kFilterMaxBlocks) b = kFilterMaxBlocks;
-  return (unsigned)(b < 1 ? 1 : b);
-}
-
-size_t align256(size_t v) { return (v + 255) / 256 * 256; }
-
 template <int ITEM>
 __host__ __device__ __forceinline__ int32_t keep_at(const void* keep, int64_t i) {
   if constexpr (ITEM == 4) return static_cast<const uint32_t*>(keep)[i] != 0u ? 1 : 0;
@@ -153,8 +145,8 @@ int run_filter(const char* name, const int64_t* edge_index, int64_t ld, int64_t 
   PG_CHECK_ARG(err == hipSuccess, (int)err, "%s: scan failed: %s", name, hipGetErrorString(err));
   const int64_t* dst = edge_index ? edge_index + ld : nullptr;            // (both may be null for an empty list)
   int64_t* c_dst = c_edge_index ? c_edge_index + c_ld : nullptr;
-  hipLaunchKernelGGL(filter_edges_kernel, dim3(filter_grid(e > num_kept ? e : num_kept)), dim3(kBlock), 0, s, edge_index,
-                     dst, a0, a1, new_id, e, num_kept, c_edge_index, c_dst, c_a0, c_a1, kept_id, count, status);
+  hipLaunchKernelGGL(filter_edges_kernel, dim3(capped_grid(e > num_kept ? e : num_kept, kFilterMaxBlocks)), dim3(kBlock), 0, s,
+                     edge_index, dst, a0, a1, new_id, e, num_kept, c_edge_index, c_dst, c_a0, c_a1, kept_id, count, status);
   PG_CHECK_LAUNCH(name);
   for (int o = 0; o < 2; ++o) {
     if (!rowptr[o]) continue;
@@ -162,8 +154,8 @@ int run_filter(const char* name, const int64_t* edge_index, int64_t ld, int64_t 
     err = scan_flags(temp, tb, KeepFlagOfSorted<ITEM>{keep, perm[o], e}, pos, e + 1, s);
     PG_CHECK_ARG(err == hipSuccess, (int)err, "%s: scan failed: %s", name, hipGetErrorString(err));
     const int64_t work = e > n + 1 ? e : n + 1;
-    hipLaunchKernelGGL(filter_order_kernel, dim3(filter_grid(work)), dim3(kBlock), 0, s, rowptr[o], other[o], perm[o],
-                       new_id, pos, e, n, num_kept, c_rowptr[o], c_other[o], c_perm[o], status);
+    hipLaunchKernelGGL(filter_order_kernel, dim3(capped_grid(work, kFilterMaxBlocks)), dim3(kBlock), 0, s, rowptr[o], other[o],
+                       perm[o], new_id, pos, e, n, num_kept, c_rowptr[o], c_other[o], c_perm[o], status);
     PG_CHECK_LAUNCH(name);
   }
   return 0;
@@ -180,7 +172,7 @@ extern "C" int64_t pangnn_structure_filter_workspace_bytes(int64_t num_edges) {
   // (the size depends on the number and the type of the items, int32 for every scan of this file, not on the functor)
   const size_t t = scan_temp_bytes<KeepFlagOfSorted<4>>(num_edges + 1);
   if (t == (size_t)-1) return 0;
-  return (int64_t)(2 * align256((size_t)(num_edges + 1) * 4) + align256(t));
+  return (int64_t)(2 * align_up((size_t)(num_edges + 1) * 4, 256) + align_up(t, 256));
 }
 
 extern "C" int pangnn_structure_filter(
@@ -226,12 +218,12 @@ extern "C" int pangnn_structure_filter(
                        (uintptr_t)child_other_src | (uintptr_t)child_perm_src | (uintptr_t)count | (uintptr_t)status |
                        (keep_itemsize == 4 ? (uintptr_t)keep : 0);
   PG_CHECK_ARG((p8 & 7u) == 0 && (p4 & 3u) == 0, PANGNN_E_ALIGN, "%s: a pointer is not aligned to its element size", name);
-  const size_t seg = align256((size_t)(e + 1) * 4);
+  const size_t seg = align_up((size_t)(e + 1) * 4, 256);
   const size_t temp = keep_itemsize == 1 ? scan_temp_bytes<KeepFlagOfSorted<1>>(e + 1)
                                          : scan_temp_bytes<KeepFlagOfSorted<4>>(e + 1);
   PG_CHECK_ARG(temp != (size_t)-1, PANGNN_E_BADARG, "%s: rocPRIM size query failed", name);
-  PG_CHECK_ARG(workspace_bytes >= 0 && (size_t)workspace_bytes >= 2 * seg + align256(temp), PANGNN_E_WORKSPACE,
-               "%s: workspace too small (%lld < %zu)", name, (long long)workspace_bytes, 2 * seg + align256(temp));
+  PG_CHECK_ARG(workspace_bytes >= 0 && (size_t)workspace_bytes >= 2 * seg + align_up(temp, 256), PANGNN_E_WORKSPACE,
+               "%s: workspace too small (%lld < %zu)", name, (long long)workspace_bytes, 2 * seg + align_up(temp, 256));
   char* ws = static_cast<char*>(workspace);
   int32_t* new_id = reinterpret_cast<int32_t*>(ws);
   int32_t* pos = reinterpret_cast<int32_t*>(ws + seg);
@@ -246,8 +238,8 @@ extern "C" int pangnn_structure_filter(
   if (keep_itemsize == 1)
     return run_filter<1>(name, edge_index, ld, e, n, keep, num_kept, rowptr, other, perm, attr0, attr1, child_edge_index,
                          child_ld, kept_id, child_attr0, child_attr1, c_rowptr, c_other, c_perm, count, status, new_id, pos,
-                         tmp, align256(temp), s);
+                         tmp, align_up(temp, 256), s);
   return run_filter<4>(name, edge_index, ld, e, n, keep, num_kept, rowptr, other, perm, attr0, attr1, child_edge_index,
                        child_ld, kept_id, child_attr0, child_attr1, c_rowptr, c_other, c_perm, count, status, new_id, pos,
-                       tmp, align256(temp), s);
+                       tmp, align_up(temp, 256), s);
 }

@@ -12,12 +12,6 @@ void set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
 // deg[i] = sum_{in-edges} w ; dis = deg^-1/2 (0 when deg == 0).  One wave per target row; lanes
 // stride the row (fixed order => reproducible).
 __global__ __launch_bounds__(kBlock) void degree_kernel(const int64_t* __restrict__ rowptr,
@@ -221,6 +215,7 @@ __global__ __launch_bounds__(kBlock) void confusion_kernel(const float* __restri
   }
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
+    // wave_sum written out: through the shared helper the compiler schedules the four butterflies differently
     unsigned int v = c[k];
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
@@ -422,13 +417,7 @@ __global__ __launch_bounds__(kBlock) void embed_conv_in_param_grads_kernel(const
     for (int h = threadIdx.x; h < H; h += kBlock) g_b_in[h] = sums[2 * H + h];
 }
 
-static inline unsigned grid_for(int64_t total) {
-  int64_t b = (total + kBlock - 1) / kBlock;
-  const int64_t cap = 256 * 16;  // 256 CUs x 16 blocks, grid-stride the rest
-  if (b > cap) b = cap;
-  if (b < 1) b = 1;
-  return (unsigned)b;
-}
+constexpr int kEdgeMaxBlocks = 256 * 16;  // 256 CUs x 16 blocks, grid-stride the rest
 
 // ------------------------------------------------------------------------------------------------------------------
 // normalize_sim_scores (src/preprocessing.py:454-548) as ONE segmented pass over the (source, candidate genome)-sorted
@@ -453,12 +442,10 @@ __global__ __launch_bounds__(kBlock) void softmax_qscore_kernel(const int64_t* _
   // reference's logsumexp and the host leg's scatter_reduce(amax) do — tests/test_nonfinite.py)
   double mx = -INFINITY;
   for (int64_t i = beg + lane; i < end; i += kWave) mx = fmax(mx, score[i] / t);     // divide like the reference (t = 0.8 is not a binary fraction)
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) mx = fmax(mx, __shfl_xor(mx, off));
+  mx = wave_max(mx);
   double sm = 0.0;
   for (int64_t i = beg + lane; i < end; i += kWave) sm += exp(score[i] / t - mx);
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) sm += __shfl_xor(sm, off);
+  sm = wave_sum(sm);
   const double lse = log(sm) + mx;                                      // scipy.special.logsumexp
   for (int64_t i = beg + lane; i < end; i += kWave) {
     const double p = exp(score[i] / t - lse);
@@ -669,7 +656,7 @@ extern "C" int pangnn_permute_f32(const float* in, const int32_t* perm, float* o
   PG_CHECK_ARG(n >= 0, PANGNN_E_BADARG, "pangnn_permute_f32: negative size");
   if (n == 0) return 0;
   PG_CHECK_ARG(in && perm && out, PANGNN_E_BADARG, "pangnn_permute_f32: null pointer");
-  hipLaunchKernelGGL(permute_kernel, dim3(grid_for(n)), dim3(kBlock), 0, (hipStream_t)stream, in,
+  hipLaunchKernelGGL(permute_kernel, dim3(capped_grid(n, kEdgeMaxBlocks)), dim3(kBlock), 0, (hipStream_t)stream, in,
                      perm, out, n);
   PG_CHECK_LAUNCH("pangnn_permute_f32");
   return 0;
@@ -691,10 +678,10 @@ extern "C" int pangnn_edge_gather_concat_f32(const float* z, int64_t ldz, int64_
   const bool vec = !extra && D % 4 == 0 && ldz % 4 == 0 && ldo % 4 == 0 && aligned16(z) && aligned16(out);
   hipStream_t s = (hipStream_t)stream;
   if (vec)
-    hipLaunchKernelGGL((gather_concat_kernel<true>), dim3(grid_for(n_edges * (2 * D / 4))), dim3(kBlock),
+    hipLaunchKernelGGL((gather_concat_kernel<true>), dim3(capped_grid(n_edges * (2 * D / 4), kEdgeMaxBlocks)), dim3(kBlock),
                        0, s, z, ldz, edge_index, ld, e_begin, n_edges, extra, out, ldo, (int)D);
   else
-    hipLaunchKernelGGL((gather_concat_kernel<false>), dim3(grid_for(n_edges * 2 * D)), dim3(kBlock), 0,
+    hipLaunchKernelGGL((gather_concat_kernel<false>), dim3(capped_grid(n_edges * 2 * D, kEdgeMaxBlocks)), dim3(kBlock), 0,
                        s, z, ldz, edge_index, ld, e_begin, n_edges, extra, out, ldo, (int)D);
   PG_CHECK_LAUNCH("pangnn_edge_gather_concat_f32");
   return 0;
@@ -715,7 +702,7 @@ extern "C" int pangnn_edge_pair_add_f32(const float* p, const float* q, int64_t 
                "pangnn_edge_pair_add_f32: D / leading dimensions must be multiples of 4");
   PG_CHECK_ARG(aligned16(p) && aligned16(q) && aligned16(out) && (!cvec || aligned16(cvec)),
                PANGNN_E_ALIGN, "pangnn_edge_pair_add_f32: pointers must be 16-byte aligned");
-  hipLaunchKernelGGL(pair_add_kernel, dim3(grid_for(n_edges * (D / 4))), dim3(kBlock), 0,
+  hipLaunchKernelGGL(pair_add_kernel, dim3(capped_grid(n_edges * (D / 4), kEdgeMaxBlocks)), dim3(kBlock), 0,
                      (hipStream_t)stream, p, q, ldpq, edge_index, ld, e_begin, n_edges, extra, cvec,
                      out, ldo, (int)D);
   PG_CHECK_LAUNCH("pangnn_edge_pair_add_f32");
@@ -744,7 +731,7 @@ extern "C" int pangnn_segment_max_bwd_f32(const float* g, const int32_t* arg, co
   PG_CHECK_ARG(n_rows >= 0 && F > 0, PANGNN_E_BADARG, "pangnn_segment_max_bwd_f32: bad size");
   if (n_rows == 0) return 0;
   PG_CHECK_ARG(g && arg && gm, PANGNN_E_BADARG, "pangnn_segment_max_bwd_f32: null pointer");
-  hipLaunchKernelGGL(segment_max_bwd_kernel, dim3(grid_for(n_rows * F)), dim3(kBlock), 0,
+  hipLaunchKernelGGL(segment_max_bwd_kernel, dim3(capped_grid(n_rows * F, kEdgeMaxBlocks)), dim3(kBlock), 0,
                      (hipStream_t)stream, g, arg, gm, ldm, ldo, n_rows, (int)F);
   PG_CHECK_LAUNCH("pangnn_segment_max_bwd_f32");
   return 0;

@@ -15,26 +15,6 @@ namespace {
 
 constexpr float kScoreEps = 1e-8f;   // F.cosine_similarity's default
 
-__device__ __forceinline__ float4 score_piece(const char* p, int xf) {
-  if (!xf) return *reinterpret_cast<const float4*>(p);
-  float4 r = rows16_to_f32(*reinterpret_cast<const uint2*>(p), xf);
-  // half rows: f32 values first, so that no conversion is folded into a mixed / packed-dot instruction (v_dot2_f32_f16,
-  // v_fma_mix_f32) that rounds differently from the f32 call on the up-converted rows
-  if (xf == 2) asm volatile("" : "+v"(r.x), "+v"(r.y), "+v"(r.z), "+v"(r.w));
-  return r;
-}
-
-template <int G>
-__device__ __forceinline__ float group_sum(float v) {
-#pragma unroll
-  for (int off = G / 2; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
-__device__ __forceinline__ float dot4(float4 a, float4 b) {
-  return fmaf(a.w, b.w, fmaf(a.z, b.z, fmaf(a.y, b.y, a.x * b.x)));
-}
-
 // one group of G = D / 4 lanes per node
 template <int D, int XF>
 __global__ __launch_bounds__(kBlock) void score_norm_kernel(const char* __restrict__ z, int64_t ldz, int64_t n,
@@ -43,7 +23,7 @@ __global__ __launch_bounds__(kBlock) void score_norm_kernel(const char* __restri
   const int lane = threadIdx.x & (kWave - 1), fl = lane % G;
   const int64_t node = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / G;
   if (node >= n) return;                                   // a whole group leaves together
-  const float4 v = score_piece(z + ((uint64_t)node * ldz + fl * 4) * ES, XF);
+  const float4 v = row_piece<true>(z + ((uint64_t)node * ldz + fl * 4) * ES, XF);
   const float s = group_sum<G>(dot4(v, v));
   if (fl == 0) {
     const float nrm = sqrtf(s);
@@ -81,8 +61,8 @@ __global__ __launch_bounds__(kBlock) void edge_score_kernel(const char* __restri
     float4 a[U], b[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-      a[u] = score_piece(zb + (uint64_t)s[u] * ldb, XF);
-      b[u] = score_piece(zb + (uint64_t)d[u] * ldb, XF);
+      a[u] = row_piece<true>(zb + (uint64_t)s[u] * ldb, XF);
+      b[u] = row_piece<true>(zb + (uint64_t)d[u] * ldb, XF);
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -106,6 +86,7 @@ __global__ __launch_bounds__(kBlock) void edge_score_kernel(const char* __restri
   }
   if (LOSS) {
     __shared__ float red[kWavesPerBlock];
+    // wave_sum written out: through the shared helper the compiler schedules this tail differently (same sums, other bytes)
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off);
     if (lane == 0) red[threadIdx.x >> 6] = acc;
@@ -123,8 +104,7 @@ __global__ void score_loss_finish_kernel(const float* __restrict__ partial, int 
   const int lane = threadIdx.x;
   float s = 0.f;
   for (int i = lane; i < n; i += kWave) s += partial[i];
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
+  s = wave_sum(s);
   if (lane == 0) loss[0] = s;
 }
 
@@ -141,8 +121,8 @@ __device__ __forceinline__ void score_walk(const char* zb, uint64_t ldb, const i
     const bool ok1 = k1 < hi;
     const int32_t e0 = perm[k], m0 = other[k];
     const int32_t e1 = ok1 ? perm[k1] : e0, m1 = ok1 ? other[k1] : m0;
-    const float4 r0 = score_piece(zb + (uint64_t)m0 * ldb, XF);
-    const float4 r1 = score_piece(zb + (uint64_t)m1 * ldb, XF);
+    const float4 r0 = row_piece<true>(zb + (uint64_t)m0 * ldb, XF);
+    const float4 r1 = row_piece<true>(zb + (uint64_t)m1 * ldb, XF);
     float c0 = g[e0], c1 = ok1 ? g[e1] : 0.f;
     if (MODE == PANGNN_SCORE_COSINE) {
       ds = fmaf(c0, logits[e0], ds);
@@ -236,7 +216,7 @@ __global__ __launch_bounds__(kBlock) void score_grad_kernel(const char* __restri
   if (MODE == PANGNN_SCORE_COSINE &&
       (src.rowptr[node + 1] > src.rowptr[node] || dst.rowptr[node + 1] > dst.rowptr[node])) {
     const float inv = norms[2 * node], k = norms[2 * node + 1] * ds;
-    const float4 zn = score_piece(zb + (uint64_t)node * ldb, XF);
+    const float4 zn = row_piece<true>(zb + (uint64_t)node * ldb, XF);
     out = make_float4(inv * acc.x - k * zn.x, inv * acc.y - k * zn.y, inv * acc.z - k * zn.z, inv * acc.w - k * zn.w);
   }
   if (g_scale) {
@@ -248,8 +228,6 @@ __global__ __launch_bounds__(kBlock) void score_grad_kernel(const char* __restri
 
 // ---- launchers
 constexpr int kScoreMaxBlocks = 4096;
-
-inline int64_t blocks_for(int64_t items, int per_block) { return (items + per_block - 1) / per_block; }
 
 template <int D, int XF>
 int launch_norms(const void* z, int64_t ldz, int64_t n, float* norms, hipStream_t s) {
@@ -345,21 +323,17 @@ struct BwdFn {
   }
 };
 
-bool score_width(int32_t d) { return d == 16 || d == 32 || d == 64 || d == 128 || d == 256; }
-
 // shared argument checks of the three entry points (z, its layout, sizes, mode)
 int check_rows(const char* fn, const void* z, int32_t z_dtype, int64_t ldz, int64_t n, int64_t e, int32_t d, int32_t mode) {
   PG_CHECK_ARG(mode == PANGNN_SCORE_DOT || mode == PANGNN_SCORE_COSINE, PANGNN_E_BADARG, "%s: mode must be 0 (dot) or 1 (cosine)",
                fn);
-  PG_CHECK_ARG(score_width(d), PANGNN_E_BADARG, "%s: d must be 16, 32, 64, 128 or 256 (got %d)", fn, (int)d);
-  PG_CHECK_ARG(z_dtype == PANGNN_DTYPE_F32 || z_dtype == PANGNN_DTYPE_BF16 || z_dtype == PANGNN_DTYPE_F16, PANGNN_E_BADARG,
-               "%s: z_dtype must be 0, 1 or 2", fn);
+  PG_CHECK_ARG(row_width_ok(d), PANGNN_E_BADARG, "%s: d must be 16, 32, 64, 128 or 256 (got %d)", fn, (int)d);
+  PG_CHECK_ARG(row_dtype_ok(z_dtype), PANGNN_E_BADARG, "%s: z_dtype must be 0, 1 or 2", fn);
   PG_CHECK_ARG(n >= 0 && e >= 0 && ldz >= d, PANGNN_E_BADARG, "%s: bad size", fn);
   PG_CHECK_ARG(n > 0 || e == 0, PANGNN_E_BADARG, "%s: edges without nodes", fn);
   PG_CHECK_ARG(e < ((int64_t)1 << 31) && n < ((int64_t)1 << 31), PANGNN_E_TOOLARGE, "%s: sizes exceed the int32 index range", fn);
   PG_CHECK_ARG(n == 0 || z, PANGNN_E_BADARG, "%s: null pointer", fn);
-  const uintptr_t a = reinterpret_cast<uintptr_t>(z);
-  PG_CHECK_ARG(ldz % 4 == 0 && (z_dtype == PANGNN_DTYPE_F32 ? (a & 15u) == 0 : (a & 7u) == 0), PANGNN_E_ALIGN,
+  PG_CHECK_ARG(rows_aligned(z, z_dtype, ldz), PANGNN_E_ALIGN,
                "%s: z rows must start on 16 bytes (f32) / 8 bytes (2-byte rows): ldz a multiple of 4", fn);
   return 0;
 }
@@ -369,7 +343,7 @@ int check_rows(const char* fn, const void* z, int32_t z_dtype, int64_t ldz, int6
 
 using namespace pangnn;
 
-extern "C" int pangnn_edge_score_supported(int32_t d) { return score_width(d) ? 1 : 0; }
+extern "C" int pangnn_edge_score_supported(int32_t d) { return row_width_ok(d) ? 1 : 0; }
 
 extern "C" int pangnn_edge_score_mixed(const void* z, int32_t z_dtype, int64_t ldz, int64_t num_nodes, const int64_t* edge_index,
                                        int64_t ld, int64_t num_edges, int32_t d, int32_t mode, float* norms, float* logits,

@@ -12,36 +12,6 @@
 namespace pangnn {
 namespace {
 
-__device__ __forceinline__ float4 dot_piece(const char* p, int xf) {
-  if (!xf) return *reinterpret_cast<const float4*>(p);
-  float4 r = rows16_to_f32(*reinterpret_cast<const uint2*>(p), xf);
-  // half rows: f32 values first, so that no conversion is folded into a mixed / packed-dot instruction (v_dot2_f32_f16,
-  // v_fma_mix_f32) that rounds differently from the f32 call on the up-converted rows (edge_score.hip, score_piece)
-  if (xf == 2) asm volatile("" : "+v"(r.x), "+v"(r.y), "+v"(r.z), "+v"(r.w));
-  return r;
-}
-
-template <int G>
-__device__ __forceinline__ float group_sum(float v) {
-#pragma unroll
-  for (int off = G / 2; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
-__device__ __forceinline__ float dot4(float4 a, float4 b) {
-  return fmaf(a.w, b.w, fmaf(a.z, b.z, fmaf(a.y, b.y, a.x * b.x)));
-}
-
-// the row r of a CSR that holds entry k: rowptr[r] <= k < rowptr[r + 1] (k < rowptr[n_rows]; empty rows are stepped over)
-__device__ __forceinline__ int64_t row_of_entry(const int64_t* __restrict__ rowptr, int64_t n_rows, int64_t k) {
-  int64_t lo = 0, hi = n_rows;                 // invariant: rowptr[lo] <= k < rowptr[hi]
-  while (hi - lo > 1) {
-    const int64_t mid = lo + ((hi - lo) >> 1);
-    if (rowptr[mid] <= k) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
 // One wave owns `chunk` consecutive entries of the CSR (a multiple of 64), whatever rows they belong to: the work is balanced
 // by entries, a hub row is shared by as many waves as it has chunks, and since every output is one entry's own dot product no
 // part sums exist.  A group of G = F / 4 lanes takes one entry at a time (EPS = 64 / G entries per wave step, U steps in
@@ -72,7 +42,7 @@ __global__ __launch_bounds__(kBlock) void edge_dot_kernel(const int64_t* __restr
   if (beg + sub < end) {
     row = row_of_entry(rowptr, n_rows, beg + sub);
     row_end = rowptr[row + 1];
-    gv = dot_piece(gb + (uint64_t)row * ldgb, XG);
+    gv = row_piece<true>(gb + (uint64_t)row * ldgb, XG);
   }
 
   int c_nxt = 0, p_nxt = 0;
@@ -108,9 +78,9 @@ __global__ __launch_bounds__(kBlock) void edge_dot_kernel(const int64_t* __restr
               ++row;
               row_end = rowptr[row + 1];
             }
-            gv = dot_piece(gb + (uint64_t)row * ldgb, XG);
+            gv = row_piece<true>(gb + (uint64_t)row * ldgb, XG);
           }
-          xv[u] = dot_piece(xb + (uint64_t)(uint32_t)c * ldxb, XX);
+          xv[u] = row_piece<true>(xb + (uint64_t)(uint32_t)c * ldxb, XX);
         } else {
           xv[u] = make_float4(0.f, 0.f, 0.f, 0.f);
         }
@@ -228,16 +198,6 @@ __global__ __launch_bounds__(kBlock) void norm_edge_kernel(const int64_t* __rest
   }
 }
 
-inline int64_t blocks_for(int64_t items, int per_block) { return (items + per_block - 1) / per_block; }
-inline size_t align4f(int64_t n) { return (size_t)((n + 3) / 4 * 4); }       // floats, a multiple of 16 bytes
-
-bool dot_width(int32_t f) { return f == 16 || f == 32 || f == 64 || f == 128 || f == 256; }
-bool row_dtype(int32_t t) { return t == PANGNN_DTYPE_F32 || t == PANGNN_DTYPE_BF16 || t == PANGNN_DTYPE_F16; }
-bool rows_aligned(const void* p, int32_t dtype, int64_t ld) {
-  const uintptr_t a = reinterpret_cast<uintptr_t>(p);
-  return ld % 4 == 0 && (dtype == PANGNN_DTYPE_F32 ? (a & 15u) == 0 : (a & 7u) == 0);
-}
-
 }  // namespace
 }  // namespace pangnn
 
@@ -248,8 +208,8 @@ extern "C" int pangnn_edge_dot_mixed(const int64_t* rowptr, const int32_t* idx, 
                                      int64_t x_rows, int64_t n_rows, int64_t nnz, int32_t F, float* out_sorted, float* out_orig,
                                      pangnn_stream_t stream) {
   const char* fn = "pangnn_edge_dot_mixed";
-  PG_CHECK_ARG(dot_width(F), PANGNN_E_BADARG, "%s: F must be 16, 32, 64, 128 or 256 (got %d)", fn, (int)F);
-  PG_CHECK_ARG(row_dtype(g_dtype) && row_dtype(x_dtype), PANGNN_E_BADARG, "%s: g_dtype and x_dtype must be 0, 1 or 2", fn);
+  PG_CHECK_ARG(row_width_ok(F), PANGNN_E_BADARG, "%s: F must be 16, 32, 64, 128 or 256 (got %d)", fn, (int)F);
+  PG_CHECK_ARG(row_dtype_ok(g_dtype) && row_dtype_ok(x_dtype), PANGNN_E_BADARG, "%s: g_dtype and x_dtype must be 0, 1 or 2", fn);
   PG_CHECK_ARG(g_dtype == PANGNN_DTYPE_F32 || x_dtype == PANGNN_DTYPE_F32 || g_dtype == x_dtype, PANGNN_E_BADARG,
                "%s: the 2-byte rows of one call are all bfloat16 or all float16", fn);
   PG_CHECK_ARG(F >= 32 || (g_dtype == PANGNN_DTYPE_F32 && x_dtype == PANGNN_DTYPE_F32), PANGNN_E_BADARG,
@@ -278,9 +238,10 @@ extern "C" int pangnn_edge_dot_mixed(const int64_t* rowptr, const int32_t* idx, 
   return PANGNN_E_BADARG;
 }
 
+// workspace: gdeg | parts_dst | parts_src, each a whole number of 16 bytes (float counts rounded up to 4)
 extern "C" int64_t pangnn_gcn_norm_bwd_workspace_bytes(int64_t num_nodes, int64_t num_seg_dst, int64_t num_seg_src) {
   if (num_nodes < 0 || num_seg_dst < 0 || num_seg_src < 0) return 0;
-  return (int64_t)((align4f(num_nodes) + align4f(num_seg_dst) + align4f(num_seg_src) + 4) * sizeof(float));
+  return (int64_t)((align_up(num_nodes, 4) + align_up(num_seg_dst, 4) + align_up(num_seg_src, 4) + 4) * sizeof(float));
 }
 
 extern "C" int pangnn_gcn_norm_bwd_f32(const int64_t* edge_index, int64_t ld, int64_t num_edges, int64_t num_nodes,
@@ -309,8 +270,8 @@ extern "C" int pangnn_gcn_norm_bwd_f32(const int64_t* edge_index, int64_t ld, in
   PG_CHECK_ARG(aligned16(workspace), PANGNN_E_ALIGN, "%s: workspace must be 16-byte aligned", fn);
   hipStream_t s = (hipStream_t)stream;
   float* gdeg = static_cast<float*>(workspace);
-  float* parts_dst = gdeg + align4f(num_nodes);
-  float* parts_src = parts_dst + align4f(nsd);
+  float* parts_dst = gdeg + align_up(num_nodes, 4);
+  float* parts_src = parts_dst + align_up(nsd, 4);
   const NormOrder dst{rowptr_dst, other_dst, perm_dst, seg_ptr_dst, parts_rowptr_dst, nsd, parts_dst};
   const NormOrder src{rowptr_src, other_src, perm_src, seg_ptr_src, parts_rowptr_src, nss, parts_src};
   for (const NormOrder* o : {&dst, &src}) {

@@ -49,14 +49,7 @@ __global__ __launch_bounds__(kBlock) void rowptr_kernel(const int32_t* __restric
   }
 }
 
-static inline unsigned grid_for(int64_t total) {
-  int64_t b = (total + kBlock - 1) / kBlock;
-  if (b > 4096) b = 4096;
-  if (b < 1) b = 1;
-  return (unsigned)b;
-}
-
-static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+constexpr int kBuildMaxBlocks = 4096;           // the elementwise kernels grid-stride the rest
 
 static int key_bits(int64_t n) {
   int b = 1;
@@ -122,17 +115,17 @@ extern "C" int pangnn_csr_build(const int64_t* edge_index, int64_t ld, int64_t n
   const int64_t* other_row = edge_index + (group_by ? 0 : ld);
   hipError_t e = hipMemsetAsync(bad, 0, 256, s);
   PG_CHECK_ARG(e == hipSuccess, (int)e, "pangnn_csr_build: memset failed: %s", hipGetErrorString(e));
-  hipLaunchKernelGGL(make_keys_kernel, dim3(grid_for(num_edges)), dim3(kBlock), 0, s, key_row, keys_in,
+  hipLaunchKernelGGL(make_keys_kernel, dim3(capped_grid(num_edges, kBuildMaxBlocks)), dim3(kBlock), 0, s, key_row, keys_in,
                      ids_in, num_edges, num_nodes, bad);
   PG_CHECK_LAUNCH("pangnn_csr_build(keys)");
   size_t tb = temp;
   e = rocprim::radix_sort_pairs(tmp, tb, keys_in, keys_out, ids_in, perm, (size_t)num_edges, 0u,
                                 (unsigned)key_bits(num_nodes), s);
   PG_CHECK_ARG(e == hipSuccess, (int)e, "pangnn_csr_build: radix sort failed: %s", hipGetErrorString(e));
-  hipLaunchKernelGGL(other_end_kernel, dim3(grid_for(num_edges)), dim3(kBlock), 0, s, other_row, perm,
+  hipLaunchKernelGGL(other_end_kernel, dim3(capped_grid(num_edges, kBuildMaxBlocks)), dim3(kBlock), 0, s, other_row, perm,
                      other, num_edges, num_nodes, bad);
   PG_CHECK_LAUNCH("pangnn_csr_build(other)");
-  hipLaunchKernelGGL(rowptr_kernel, dim3(grid_for(num_nodes + 1)), dim3(kBlock), 0, s, keys_out, rowptr,
+  hipLaunchKernelGGL(rowptr_kernel, dim3(capped_grid(num_nodes + 1, kBuildMaxBlocks)), dim3(kBlock), 0, s, keys_out, rowptr,
                      num_edges, num_nodes);
   PG_CHECK_LAUNCH("pangnn_csr_build(rowptr)");
   return 0;
@@ -383,9 +376,9 @@ extern "C" int pangnn_collate_subgraphs(const int64_t* edge_index, int64_t ld_e,
                    (num_nb == 0 || (nb_index && out_nb_index)) && (num_nodes == 0 || (out_batch && out_x)),
                PANGNN_E_BADARG, "pangnn_collate_subgraphs: null pointer");
   const int64_t total = 2 * num_edges + 2 * num_nb + (num_graphs + 1) + num_nodes;
-  hipLaunchKernelGGL(collate_kernel, dim3(grid_for(total)), dim3(kBlock), 0, (hipStream_t)stream, edge_index, ld_e, e0,
-                     num_edges, nb_index, ld_b, b0, num_nb, node_off, (int)num_graphs, n0, num_nodes, out_edge_index,
-                     out_nb_index, out_ptr, out_batch, out_x);
+  hipLaunchKernelGGL(collate_kernel, dim3(capped_grid(total, kBuildMaxBlocks)), dim3(kBlock), 0, (hipStream_t)stream,
+                     edge_index, ld_e, e0, num_edges, nb_index, ld_b, b0, num_nb, node_off, (int)num_graphs, n0, num_nodes,
+                     out_edge_index, out_nb_index, out_ptr, out_batch, out_x);
   PG_CHECK_LAUNCH("pangnn_collate_subgraphs");
   return 0;
 }
@@ -646,10 +639,10 @@ extern "C" int pangnn_collate_subgraphs_padded(const int64_t* edge_index, int64_
     bo.enabled = 1;
   }
   const int64_t total = 2 * max_edges + 2 * max_nb + (max_graphs + 1) + max_nodes;
-  hipLaunchKernelGGL(collate_padded_kernel, dim3(grid_for(total)), dim3(kBlock), 0, (hipStream_t)stream, edge_index, ld_e,
-                     nb_index, ld_b, edge_attr, y, node_off, edge_off, nb_off, graph_ids, (int)max_graphs, num_graphs_total,
-                     max_edges, max_nb, max_nodes, out_edge_index, out_nb_index, out_edge_attr, out_y, out_ptr, out_batch,
-                     out_x, out_live, bo);
+  hipLaunchKernelGGL(collate_padded_kernel, dim3(capped_grid(total, kBuildMaxBlocks)), dim3(kBlock), 0,
+                     (hipStream_t)stream, edge_index, ld_e, nb_index, ld_b, edge_attr, y, node_off, edge_off, nb_off, graph_ids,
+                     (int)max_graphs, num_graphs_total, max_edges, max_nb, max_nodes, out_edge_index, out_nb_index,
+                     out_edge_attr, out_y, out_ptr, out_batch, out_x, out_live, bo);
   PG_CHECK_LAUNCH(who);
   if (orders != nullptr) {
     WalkOrders w{};

@@ -13,14 +13,6 @@ namespace pangnn {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-__device__ __forceinline__ constexpr int jrow(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }
-
-__device__ __forceinline__ void wave_sync_lds() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // wave-uniform base pointer + 32-bit per-lane byte offset: the form that maps to `global_* v_off, v_data, s[base]`
 // (scalar address arithmetic per tile, no 64-bit vector pointer per access).  The compiler only selects it when
 // the base is known to sit in SGPRs and the offset's zero-extension is in the same basic block, hence `pin()`
@@ -346,7 +338,7 @@ __global__ __launch_bounds__((FwdGeo<K, M>::WAVES * 64)) void linear_fwd_kernel(
     load_rows_full<K, TX>(x, ldx, tile * 32, lane, rg);
     store_rows<K, ACT, TX>(rg, lane, Xt);
     load_rows_full<K, TX>(x, ldx, (tile + stride < last ? tile + stride : last) * 32, lane, rg);
-    wave_sync_lds();
+    wave_lds_sync();
     for (; tile < n_full; tile += stride) {
       // GATE: the tile's gate values are fetched before the product so that they land behind the MFMAs (fetched
       // in the epilogue, one load-and-use at a time, the 128-wide variant took 0.98 ms instead of 0.17)
@@ -357,19 +349,19 @@ __global__ __launch_bounds__((FwdGeo<K, M>::WAVES * 64)) void linear_fwd_kernel(
         pin(gbase, goff);
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-          const TG* gr = gate + (gbase + (i & 3) + 8 * (i >> 2)) * ldgate;
+          const TG* gr = gate + (gbase + acc_row(i, 0)) * ldgate;
 #pragma unroll
           for (int b = 0; b < M / 32; ++b) gv[b][i] = Elem<TG>::ld1(gr + 32 * b, goff);
         }
       }
       tile_product<K, M>(Xt, Wl, r, hh, acc);
-      // C[row = jrow(i,hh)][m = r + 32b]: 128-byte row segments
+      // C[row = acc_row(i,hh)][m = r + 32b]: 128-byte row segments
       uint32_t loff = (4u * hh * (uint32_t)ldy + r) * (uint32_t)sizeof(TY);
       int64_t sbase = tile * 32;
       pin(sbase, loff);
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
-        TY* yr = y + (sbase + (i & 3) + 8 * (i >> 2)) * ldy;              // scalar
+        TY* yr = y + (sbase + acc_row(i, 0)) * ldy;              // scalar
 #pragma unroll
         for (int b = 0; b < M / 32; ++b) {
           float v = acc[b][i] + bv[b];
@@ -380,21 +372,21 @@ __global__ __launch_bounds__((FwdGeo<K, M>::WAVES * 64)) void linear_fwd_kernel(
       store_rows<K, ACT, TX>(rg, lane, Xt);           // tile + stride (see the pipeline note)
       const int64_t nxt = tile + 2 * stride;
       load_rows_full<K, TX>(x, ldx, (nxt < last ? nxt : last) * 32, lane, rg);
-      wave_sync_lds();
+      wave_lds_sync();
     }
   }
   if (tile == n_full && n_full < n_tiles) {            // the partial tile, rows [32 n_full, n)
     const int64_t base = n_full * 32;
     load_rows<K, TX>(x, ldx, n, base, lane, rg);
-    wave_sync_lds();
+    wave_lds_sync();
     store_rows<K, ACT, TX>(rg, lane, Xt);
-    wave_sync_lds();
+    wave_lds_sync();
     tile_product<K, M>(Xt, Wl, r, hh, acc);
 #pragma unroll
     for (int b = 0; b < M / 32; ++b)
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
-        const int64_t row = base + jrow(i, hh);
+        const int64_t row = base + acc_row(i, hh);
         if (row < n) {
           float v = acc[b][i] + bv[b];
           if (GATE) v *= elu1_grad(Elem<TG>::ld1(gate + row * ldgate + r + 32 * b, 0u));
@@ -511,7 +503,7 @@ __device__ __forceinline__ void wgrad_finish(const f32x16 (&acc)[M / 32][K / 32]
 #pragma unroll
       for (int b = 0; b < K / 32; ++b)
 #pragma unroll
-        for (int i = 0; i < 16; ++i) lds[(32 * a + jrow(i, hh)) * K + r + 32 * b] = val[(a * (K / 32) + b) * 16 + i];    // gw[m][k]
+        for (int i = 0; i < 16; ++i) lds[(32 * a + acc_row(i, hh)) * K + r + 32 * b] = val[(a * (K / 32) + b) * 16 + i];    // gw[m][k]
       if (hh == 0) lds[M * K + r + 32 * a] = val[NA + a];
     }
   }
@@ -554,9 +546,9 @@ __global__ __launch_bounds__(256) void linear_wgrad_kernel(const TG* __restrict_
     store_rows<M, 0, TG>(rgm, lane, Gt);
     load_rows<K, TX>(x, ldx, n, (tile + stride) * 32, lane, rx);
     load_rows<M, TG>(g, ldg, n, (tile + stride) * 32, lane, rgm);
-    wave_sync_lds();
+    wave_lds_sync();
     wgrad_tile<K, M>(Gt, r, hh, TileX<K, 0>{Xt, r}, acc, gbp);     // store_rows has applied ACT
-    wave_sync_lds();
+    wave_lds_sync();
   }
 #pragma unroll
   for (int a = 0; a < M / 32; ++a) gbp[a] += __shfl_xor(gbp[a], 32);
@@ -574,19 +566,11 @@ __global__ __launch_bounds__(kSumThreads) void slab_reduce_kernel(const float* _
   else if (out1) out1[i - split] = s;
 }
 
-static int num_cus() {
-  int dev = 0, v = 0;
-  if (hipGetDevice(&dev) == hipSuccess &&
-      hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
-    return v;
-  return 256;
-}
-
 // workgroups of a launch whose `waves` waves per workgroup walk the 32-row tiles: min(ceil(n_tiles / waves), cus_mult x CUs),
 // and no fewer than `at_least` (1 where every launch must leave a slab, n = 0 included)
 static int64_t grid_of(int64_t n_tiles, int waves, int cus_mult = 1, int64_t at_least = 0) {
   int64_t grid = (n_tiles + waves - 1) / waves;
-  const int64_t cap = cus_mult * (int64_t)num_cus();
+  const int64_t cap = cus_mult * (int64_t)cu_count();
   if (grid > cap) grid = cap;
   return grid < at_least ? at_least : grid;
 }
@@ -853,7 +837,7 @@ __global__ __launch_bounds__(256) void pq_backward_parts_kernel(PartTables pt, c
     rp[1] = rp_next[1];
     issue_parts(pt, rp, lane, pa);
     load_part_ptrs(pt, n, tile + 2 * stride, lane, rp_next);
-    wave_sync_lds();
+    wave_lds_sync();
     wgrad_tile<K, M>(Gt, r, hh, TileX<K, ACT>{Xt, r}, acc, gbp);
     // dL/dx = (G w) * ELU'(x): linear_fwd_kernel<M, K, 0, GATE>'s product (the G tile's row stride M + 4 is that product's)
     // and epilogue, gate read from the x tile
@@ -865,11 +849,11 @@ __global__ __launch_bounds__(256) void pq_backward_parts_kernel(PartTables pt, c
       pin(sbase, loff);
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
-        float* yr = gx + (sbase + (i & 3) + 8 * (i >> 2)) * ldgx;
+        float* yr = gx + (sbase + acc_row(i, 0)) * ldgx;
 #pragma unroll
         for (int b = 0; b < K / 32; ++b) {
           float v = dx[b][i] + 0.f;                                 // the forward kernel's "+ bias" with no bias: -0 -> +0
-          if (ACT == 1) v *= elu1_grad(Xt[jrow(i, hh) * KS + r + 32 * b]);
+          if (ACT == 1) v *= elu1_grad(Xt[acc_row(i, hh) * KS + r + 32 * b]);
           st_f32(yr + 32 * b, loff, v);
         }
       }
@@ -878,15 +862,15 @@ __global__ __launch_bounds__(256) void pq_backward_parts_kernel(PartTables pt, c
       for (int b = 0; b < K / 32; ++b)
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-          const int64_t row = tile * 32 + jrow(i, hh);
+          const int64_t row = tile * 32 + acc_row(i, hh);
           if (row < n) {
             float v = dx[b][i] + 0.f;
-            if (ACT == 1) v *= elu1_grad(Xt[jrow(i, hh) * KS + r + 32 * b]);
+            if (ACT == 1) v *= elu1_grad(Xt[acc_row(i, hh) * KS + r + 32 * b]);
             gx[row * ldgx + r + 32 * b] = v;
           }
         }
     }
-    wave_sync_lds();
+    wave_lds_sync();
   }
 #pragma unroll
   for (int a = 0; a < M / 32; ++a) gbp[a] += __shfl_xor(gbp[a], 32);
@@ -1016,7 +1000,7 @@ __global__ __launch_bounds__(512) void gen_linear_fwd_reg_kernel(
       pin(sbase, loff);
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
-        float* yr = y + (sbase + (i & 3) + 8 * (i >> 2)) * ldy;
+        float* yr = y + (sbase + acc_row(i, 0)) * ldy;
 #pragma unroll
         for (int b = 0; b < M / 32; ++b) st_f32(yr + 32 * b, loff, acc[b][i] + bv[b]);
       }
@@ -1025,7 +1009,7 @@ __global__ __launch_bounds__(512) void gen_linear_fwd_reg_kernel(
       for (int b = 0; b < M / 32; ++b)
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-          const int64_t row = tile * 32 + jrow(i, hh);
+          const int64_t row = tile * 32 + acc_row(i, hh);
           if (row < n) y[row * ldy + r + 32 * b] = acc[b][i] + bv[b];
         }
     }
@@ -1081,9 +1065,9 @@ __global__ __launch_bounds__(256) void gen_linear_wgrad_kernel(const float* __re
     store_rows<M, 0, float>(rgm, lane, Gt);                 // rows >= n are zero: their generated x contributes nothing
     rsv = gen_load(rvec, svec, n, (tile + stride) * 32, lane);
     load_rows<M, float>(g, ldg, n, (tile + stride) * 32, lane, rgm);
-    wave_sync_lds();
+    wave_lds_sync();
     wgrad_tile<K, M>(Gt, r, hh, gen_x, acc, gbp);
-    wave_sync_lds();
+    wave_lds_sync();
   }
 #pragma unroll
   for (int a = 0; a < M / 32; ++a) gbp[a] += __shfl_xor(gbp[a], 32);
@@ -1130,11 +1114,11 @@ __global__ __launch_bounds__((FwdGeo<KG, H>::WAVES * 64)) void gen_linear_dgrad_
     const float rs_cur = rsv;
     load_rows<KG, float>(g, ldg, n, (tile + stride) * 32, lane, rg);
     rsv = gen_load(rvec, svec, n, (tile + stride) * 32, lane);
-    wave_sync_lds();
+    wave_lds_sync();
     tile_product<KG, H>(Xt, Wl, r, hh, acc);
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
-      const int row = jrow(i, hh);
+      const int row = acc_row(i, hh);
       const float rv = __shfl(rs_cur, row), sv = __shfl(rs_cur, 32 + row);
 #pragma unroll
       for (int b = 0; b < H / 32; ++b) {
@@ -1144,7 +1128,7 @@ __global__ __launch_bounds__((FwdGeo<KG, H>::WAVES * 64)) void gen_linear_dgrad_
         s2[b] += v;
       }
     }
-    wave_sync_lds();
+    wave_lds_sync();
   }
 #pragma unroll
   for (int b = 0; b < H / 32; ++b) {
@@ -1189,7 +1173,7 @@ static int launch_gen_bwd(const float* g, int64_t ldg, const float* r, const flo
       },
       "pangnn_embed_linear_bwd(wgrad)", "pangnn_embed_linear_bwd(wgrad reduce)", ws, grid_w, SLAB, M * K, g_w_out, g_b_out, s);
   if (rc) return rc;
-  float* ws2 = ws + (size_t)num_cus() * SLAB;
+  float* ws2 = ws + (size_t)cu_count() * SLAB;
   constexpr int WAVES = FwdGeo<M, K>::WAVES;
   const int64_t grid_d = grid_of(n_tiles, WAVES, 1, 1);
   return launch_then_reduce(
@@ -1212,7 +1196,6 @@ extern "C" int pangnn_linear_supported(int32_t K, int32_t M, int wgrad) {
   return 1;
 }
 
-static bool dtype_ok(int32_t d) { return d == PANGNN_DTYPE_F32 || d == PANGNN_DTYPE_BF16 || d == PANGNN_DTYPE_F16; }
 // the one 2-byte format of a call's operands (0 when all are f32), -1 when bfloat16 and float16 operands are mixed
 static int fmt16_of(int32_t a, int32_t b, int32_t c = PANGNN_DTYPE_F32) {
   int f = 0;
@@ -1223,7 +1206,6 @@ static int fmt16_of(int32_t a, int32_t b, int32_t c = PANGNN_DTYPE_F32) {
   }
   return f;
 }
-static bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
 
 static int linear_fwd_common(const void* x, int32_t x_dtype, int64_t ldx, const float* w, int w_trans, const float* bias,
                              void* y, int32_t y_dtype, int64_t ldy, int64_t n, int32_t K, int32_t M, int32_t in_act,
@@ -1231,7 +1213,7 @@ static int linear_fwd_common(const void* x, int32_t x_dtype, int64_t ldx, const 
   PG_CHECK_ARG(n >= 0, PANGNN_E_BADARG, "pangnn_linear_fwd: negative size");
   PG_CHECK_ARG(pangnn_linear_supported(K, M, 0), PANGNN_E_BADARG,
                "pangnn_linear_fwd: K and M must be 64 or 128 (got %d, %d)", (int)K, (int)M);
-  PG_CHECK_ARG(dtype_ok(x_dtype) && dtype_ok(y_dtype) && (!gate || dtype_ok(gate_dtype)), PANGNN_E_BADARG,
+  PG_CHECK_ARG(row_dtype_ok(x_dtype) && row_dtype_ok(y_dtype) && (!gate || row_dtype_ok(gate_dtype)), PANGNN_E_BADARG,
                "pangnn_linear_fwd: storage types are PANGNN_DTYPE_F32 / _BF16 / _F16");
   PG_CHECK_ARG((in_act == 0 || in_act == 1) && !(in_act && gate) && (!gate || ldgate >= M), PANGNN_E_BADARG,
                "pangnn_linear_act_fwd: in_act must be 0 or 1 (ELU) and excludes gate; ldgate >= M");
@@ -1239,7 +1221,7 @@ static int linear_fwd_common(const void* x, int32_t x_dtype, int64_t ldx, const 
                "pangnn_linear_act_fwd: a gated product is stored like its gate (it is the gate tensor's gradient)");
   if (n == 0) return 0;
   PG_CHECK_ARG(x && w && y && ldx >= K && ldy >= M, PANGNN_E_BADARG, "pangnn_linear_fwd: bad pointer / ld");
-  PG_CHECK_ARG((x_dtype != PANGNN_DTYPE_F32 ? aligned8(x) : aligned16(x)) && aligned16(w) && ldx % 4 == 0,
+  PG_CHECK_ARG(rows_aligned(x, x_dtype, ldx) && aligned16(w),
                PANGNN_E_ALIGN, "pangnn_linear_fwd: x rows must start on 16 bytes (f32) / 8 bytes (bf16, f16), w on 16, ldx % 4 == 0");
   const int fmt = fmt16_of(x_dtype, y_dtype, gate ? gate_dtype : PANGNN_DTYPE_F32);
   PG_CHECK_ARG(fmt >= 0, PANGNN_E_BADARG, "pangnn_linear_fwd: the 2-byte operands of one call are all bfloat16 or all float16");
@@ -1280,7 +1262,7 @@ extern "C" int pangnn_linear_fwd_f32(const float* x, int64_t ldx, const float* w
 }
 
 extern "C" size_t pangnn_linear_wgrad_workspace_bytes(int32_t K, int32_t M) {
-  return (size_t)num_cus() * ((size_t)M * K + M) * sizeof(float);
+  return (size_t)cu_count() * ((size_t)M * K + M) * sizeof(float);
 }
 
 extern "C" int pangnn_linear_act_wgrad_mixed(const void* g, int32_t g_dtype, int64_t ldg, const void* x, int32_t x_dtype,
@@ -1290,12 +1272,11 @@ extern "C" int pangnn_linear_act_wgrad_mixed(const void* g, int32_t g_dtype, int
   PG_CHECK_ARG(pangnn_linear_supported(K, M, 1), PANGNN_E_BADARG,
                "pangnn_linear_wgrad: unsupported (K, M) = (%d, %d)", (int)K, (int)M);
   PG_CHECK_ARG(in_act == 0 || in_act == 1, PANGNN_E_BADARG, "pangnn_linear_act_wgrad: in_act must be 0 or 1");
-  PG_CHECK_ARG(dtype_ok(g_dtype) && dtype_ok(x_dtype), PANGNN_E_BADARG,
+  PG_CHECK_ARG(row_dtype_ok(g_dtype) && row_dtype_ok(x_dtype), PANGNN_E_BADARG,
                "pangnn_linear_wgrad: storage types are PANGNN_DTYPE_F32 / _BF16 / _F16");
   PG_CHECK_ARG(gw && (n == 0 || (g && x)) && ldg >= M && ldx >= K, PANGNN_E_BADARG,
                "pangnn_linear_wgrad: bad pointer / ld");
-  PG_CHECK_ARG((g_dtype != PANGNN_DTYPE_F32 ? aligned8(g) : aligned16(g)) &&
-                   (x_dtype != PANGNN_DTYPE_F32 ? aligned8(x) : aligned16(x)) && ldg % 4 == 0 && ldx % 4 == 0,
+  PG_CHECK_ARG(rows_aligned(g, g_dtype, ldg) && rows_aligned(x, x_dtype, ldx),
                PANGNN_E_ALIGN, "pangnn_linear_wgrad: rows must start on 16 bytes (f32) / 8 bytes (bf16, f16), ld multiples of 4");
   const int fmt = fmt16_of(g_dtype, x_dtype);
   PG_CHECK_ARG(fmt >= 0, PANGNN_E_BADARG, "pangnn_linear_wgrad: the 2-byte operands of one call are all bfloat16 or all float16");
@@ -1389,7 +1370,7 @@ extern "C" int pangnn_embed_linear_fwd(const float* r, const float* s, int64_t n
 }
 
 extern "C" size_t pangnn_embed_linear_bwd_workspace_bytes(int32_t H, int32_t M) {
-  return (size_t)num_cus() * ((size_t)M * H + M + 3 * (size_t)H) * sizeof(float);
+  return (size_t)cu_count() * ((size_t)M * H + M + 3 * (size_t)H) * sizeof(float);
 }
 
 // g [n, M] = dL/dy.  Outputs: g_w_out [M, H], g_b_out [M] (nullable), sums [3, H] = [r s 1]^T dL/dh (feed

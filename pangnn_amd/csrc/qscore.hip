@@ -21,12 +21,6 @@
 namespace pangnn {
 namespace {
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
 // the edge at position k of the segment order; an id outside [0, E) (a broken plan) is reported as -1 and touches nothing
 __device__ __forceinline__ int64_t edge_at(const int32_t* __restrict__ item, int64_t k, int64_t E) {
   const int64_t e = item[k];
@@ -71,8 +65,7 @@ __global__ __launch_bounds__(kBlock) void qscore_fwd_kernel(const int64_t* __res
     const int64_t e = edge_at(item, i, E);
     if (e >= 0) mx = fmax(mx, (double)score[e] / t);
   }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) mx = fmax(mx, __shfl_xor(mx, off));
+  mx = wave_max(mx);
   double sm = 0.0;
   if (e0 >= 0) sm += exp(x0 - mx);
   for (int64_t i = i0 + kWave; i < s.end; i += kWave) {

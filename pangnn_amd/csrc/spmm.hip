@@ -14,11 +14,7 @@ namespace pangnn {
 // XF: storage format of the gathered rows — 0 float32, 1 bfloat16, 2 float16 (PANGNN_DTYPE_*; the 2-byte formats: 8 bytes per
 // lane instead of 16; SURVEY.md §8b `X f32/bf16`, the storage format of config 5, and `--mixed_precision fp16`).  Weights,
 // accumulation and the result stay fp32 — what PyG's propagate computes under autocast (a 16-bit x_j times an fp32 edge
-// weight promotes to fp32, scatter-add into an fp32 output).
-__device__ __forceinline__ float4 row_piece(const char* p, int xf) {
-  if (!xf) return *reinterpret_cast<const float4*>(p);
-  return rows16_to_f32(*reinterpret_cast<const uint2*>(p), xf);
-}
+// weight promotes to fp32, scatter-add into an fp32 output).  Pieces are loaded unpinned (row_piece<false>, common.h).
 
 template <int F, int U, bool BIG, int XF = 0>
 __global__ __launch_bounds__(kBlock) void spmm_row_kernel(
@@ -82,9 +78,9 @@ __global__ __launch_bounds__(kBlock) void spmm_row_kernel(
             const f32x4 t = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(xbase + (int64_t)c * ldx * 4));
             xv[u] = make_float4(t[0], t[1], t[2], t[3]);
           } else if (BIG) {
-            xv[u] = row_piece(xbase + (int64_t)c * ldx * ES, XF);
+            xv[u] = row_piece<false>(xbase + (int64_t)c * ldx * ES, XF);
           } else {
-            xv[u] = row_piece(xbase + (uint32_t)c * ldx_b32, XF);
+            xv[u] = row_piece<false>(xbase + (uint32_t)c * ldx_b32, XF);
           }
         } else {
           xv[u] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -383,8 +379,7 @@ static int spmm_csr_16(const char* who, int fmt, const int64_t* rowptr, const in
   if (n_rows == 0) return 0;
   PG_CHECK_ARG(rowptr && out && (x16 || n_src_rows == 0) && ldx >= F && ldo >= F, PANGNN_E_BADARG,
                "%s: null pointer / leading dimension smaller than F", who);
-  PG_CHECK_ARG((reinterpret_cast<uintptr_t>(x16) & 7u) == 0 && aligned16(out) && (!bias || aligned16(bias)) &&
-                   ldx % 4 == 0 && ldo % 4 == 0,
+  PG_CHECK_ARG(rows_aligned(x16, fmt, ldx) && aligned16(out) && (!bias || aligned16(bias)) && ldo % 4 == 0,
                PANGNN_E_ALIGN, "%s: x must be 8-byte aligned, out / bias 16-byte, ld multiples of 4", who);
   PG_CHECK_ARG((n_rows + kWavesPerBlock - 1) / kWavesPerBlock < 2147483647LL, PANGNN_E_TOOLARGE,
                "%s: too many rows for one launch", who);

@@ -1,6 +1,8 @@
 """pangnn_csr_plan (csrc/csr_plan.hip): the decoder's run-sum plan from a row pointer, against the written definition
 EdgeStructure._plan_of_sorted_keys on the expanded keys, and through EdgeStructure.csr_plan / runsum_plan against the
 torch route (graph.PLAN_KERNEL off).  Every comparison is exact: same dtypes, torch.equal."""
+import functools
+
 import pytest
 import torch
 
@@ -53,6 +55,73 @@ def test_the_plan_of_a_rowptr_is_the_plan_of_its_keys(which, name):
         plans_equal(got, want, (name, e, ct))
         again = EdgeStructure._plan_of_rowptr(rowptr, e, ct)                  # two calls: bit-identical tables
         plans_equal(again, got, (name, e, ct, "again"))
+
+
+# ---- the corners of the kernels' entry -> row search (csrc/common.h row_of_entry: the plan kernel here, the edge-dot kernels
+# in tests/test_edge_weight_grad.py) at small sizes
+SEARCH_ROWS = (1, 2, 3, 65, 130)
+
+
+def _filled(m, e):
+    """m non-empty rows that share e >= m entries: the first ends on entry 32 and the second on entry 64 where e allows (row
+    boundaries on the 32-entry plan chunks and the 64-entry edge-dot chunks), one entry in each other row and the rest in
+    the last one (boundaries off them)"""
+    lens, spare = [1] * m, e - m
+    for i in (0, 1):
+        if i < m - 1 and spare >= 31:
+            lens[i] += 31
+            spare -= 31
+    lens[-1] += spare
+    return lens
+
+
+@functools.lru_cache(maxsize=None)
+def search_corners():
+    """((name, rowptr int64 [n_rows + 1] on the CPU), ...): 1, 2, 3, 65 and 130 rows; every entry in the first row / in the
+    last row, leading empty rows, trailing empty rows, empty and non-empty rows alternating (either first), one row of 200
+    entries among single-entry rows; 1 to 329 entries"""
+    out = []
+    for n in SEARCH_ROWS:
+        lens = {}
+        for e in (1, 32, 33, 64, 65, 300):
+            lens[f"all_in_first_row-{e}"] = [e] + [0] * (n - 1)
+            if n > 1:
+                lens[f"all_in_last_row-{e}"] = [0] * (n - 1) + [e]
+        hub = [1] * n
+        hub[n // 2] = 200
+        lens["a_row_of_200_among_rows_of_one"] = hub
+        if n > 1:
+            m, k = n - n // 2, n // 2
+            for e in sorted({m, 96, 130, 300}):
+                if e >= m:
+                    lens[f"leading_empty_rows-{e}"] = [0] * k + _filled(m, e)
+                    lens[f"trailing_empty_rows-{e}"] = _filled(m, e) + [0] * k
+            for e in sorted({k, 96, 130, 300}):
+                if e >= k:
+                    full = _filled(k, e)
+                    lens[f"alternating_empty_first-{e}"] = [v for f in full for v in (0, f)] + [0] * (n - 2 * k)
+                    lens[f"alternating_full_first-{e}"] = [v for f in full for v in (f, 0)] + [0] * (n - 2 * k)
+        for name, ln in lens.items():
+            assert len(ln) == n and 1 <= sum(ln) <= 329, (n, name)
+            out.append((f"{n}_rows-{name}", torch.cat([torch.zeros(1, dtype=torch.int64), torch.cumsum(torch.tensor(ln), 0)])))
+    return tuple(out)
+
+
+def row_of_entries(rowptr):
+    """the row of every entry of a CPU row pointer: the last row r with rowptr[r] <= k, among equal row pointers the non-empty row"""
+    return torch.searchsorted(rowptr, torch.arange(int(rowptr[-1])), right=True) - 1
+
+
+@pytest.mark.parametrize("ct", [1, 2])
+def test_the_plan_at_the_corners_of_the_row_search(ct):
+    assert len(search_corners()) > 100
+    for name, rowptr in search_corners():
+        e, n_rows = int(rowptr[-1]), rowptr.numel() - 1
+        rows = row_of_entries(rowptr)
+        assert torch.equal(rows, keys_of(rowptr)), name
+        got = EdgeStructure._plan_of_rowptr(rowptr.to(DEV), e, ct)
+        assert torch.equal(got.keys.cpu().long(), rows), (name, ct)
+        plans_equal(got, EdgeStructure._plan_of_sorted_keys(rows.to(DEV), n_rows, ct), (name, ct))
 
 
 def _golden(name="cfg2_sim_1000x5"):

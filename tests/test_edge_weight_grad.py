@@ -102,6 +102,31 @@ def test_edge_dot_is_exact_on_the_integer_grid(name, f, g_rows, x_rows):
     assert none is None and torch.equal(only_sorted, out_sorted)
 
 
+@pytest.mark.parametrize("f,rows", [(16, "f32"), (64, "f16"), (256, "f32")])
+def test_edge_dot_at_the_corners_of_the_row_search(f, rows):
+    """A wave owns 64 entries of a list this short, and each of its 64 / (f / 4) sub-groups finds the row of its first entry
+    by the binary search of csrc/common.h (row_of_entry), then steps the row pointer: the row pointers of
+    test_csr_plan.search_corners, the row of entry k being searchsorted(rowptr, k, right=True) - 1 on the CPU, on the
+    integer grid of the test above (|sum| <= 16 f <= 4096: exact in any order)."""
+    from pangnn_amd import functional as PF
+    from pangnn_amd.graph import CSR
+    from test_csr_plan import SEARCH_ROWS, row_of_entries, search_corners
+    n_x = 37
+    gen = torch.Generator().manual_seed(200 + f)
+    g = torch.randint(-4, 5, (max(SEARCH_ROWS), f), generator=gen).double()
+    x = torch.randint(-4, 5, (n_x, f), generator=gen).double()
+    gd, xd = g.to(dev(), ROWS[rows]), x.to(dev(), ROWS[rows])
+    for name, rowptr in search_corners():
+        e, n = int(rowptr[-1]), rowptr.numel() - 1
+        other = torch.randint(0, n_x, (e,), generator=gen, dtype=torch.int32)
+        perm = torch.randperm(e, generator=gen).to(torch.int32)
+        ref = (g[row_of_entries(rowptr)] * x[other.long()]).sum(dim=1)
+        csr = CSR(rowptr.to(dev()), other.to(dev()), perm.to(dev()))
+        out_sorted, out_orig = PF.edge_dot(csr, gd[:n], xd)
+        assert torch.equal(out_sorted.cpu().double(), ref), (name, f, rows)
+        assert torch.equal(out_orig.cpu().double()[perm.long()], ref), (name, f, rows)
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # 2.-5. GCNConv against the oracle
 # ------------------------------------------------------------------------------------------------------------------
