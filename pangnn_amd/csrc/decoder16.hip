@@ -22,8 +22,20 @@
 //
 // Per wave and 16 edges: 48 + 24 MFMA(16x16x32) + 12 MFMA(32x32x16) in S, 24 in T; every product carries
 // fp32-level error (no two-term shortcuts).  No divergent control flow around matrix operands: the last tile is
-// padded by clamping edge ids to E-1 (dead lanes compute a duplicate whose dL/dlogit is forced to 0), so there is
-// ONE tile body, every lane is active in every MFMA / transposing LDS read, and only global stores are predicated.
+// padded by clamping edge ids to E-1 (dead lanes compute a duplicate whose dL/dlogit is forced to 0), so every lane is
+// active in every MFMA / transposing LDS read, and only global stores are predicated.
+//
+// Two walks over a wave's tiles.  The ids / keys instances (padded batches with e_live, shards, the small build, lists
+// without a plan's stream) run ONE flat tile loop with that general body for every tile and derive the chunk bookkeeping
+// per tile (next_tile, selects on carry / pidx, the part offset).  The STREAM instances — every edge is real, so only the
+// list's last tile can hold a dead position — run the CHUNK WALK: loops over the wave's chunks with a counted loop over a
+// chunk's tiles inside, all indices 32-bit scalars, the part offset loaded once per chunk, carry / pidx reset at chunk entry.
+// Whole chunks of full tiles run a body instantiated with TAIL = false (no live / store limits, no clamps, in T no
+// close_mask); the wave's final chunk (S) or final two chunks (T), which hold the list's last tile and every prefetch that
+// could point past the list, run the same body function with TAIL = true, the general logic.  The stream bodies repeat the
+// ids / keys loops' arithmetic statement for statement (tests/test_chunk_walk.py holds them bit for bit equal); the ids /
+// keys loops themselves are kept as they were, because wrapped into a shared body function they compile to other
+// instructions (profiles/chunk_walk.md).
 //
 // INVARIANT — the relus are held DOUBLED.  relu2x(x) = x + |x| = 2 relu(x) is the one-instruction relu through which a NaN of
 // either sign stays a NaN (see relu2x), so in the S and inference kernels the registers `h` (h1_frags) and `acc` after p1_logit
@@ -45,6 +57,7 @@
 // on the domain 128 |w3[j] W2[j][k]| <= FLT_MAX: above it T's image is inf where S's is finite (an alarm S would not raise).
 // Non-finite entries of W2 or w3 propagate alike: 2^-7 inf = inf, 0 inf = NaN, as with 1.0 (tests/test_dgrad_stream.py).
 #include "common.h"
+#include <type_traits>
 
 // This file is compiled TWICE (csrc/Makefile): as decoder16.o — everything, the 2-byte table format of the PQ16 instances being
 // bfloat16 — and, with -DPANGNN_D16_TABLES_F16, as decoder16_f16.o: the S and inference kernels again with PQ16 = IEEE half
@@ -86,7 +99,9 @@ __attribute__((unused)) static inline int chunk_log_for(int64_t n_tiles) {
   while (c > 0 && (n_tiles >> c) < D16_MIN_CHUNKS) --c;
   return c;
 }
-// the wave's next tile: the next one of its chunk, or the first of the chunk `cstride` chunks on
+// the wave's next tile: the next one of its chunk, or the first of the chunk `cstride` chunks on.  The flat tile loops of the
+// ids / keys instances ask per tile (64-bit uniform arithmetic: its compares issue on the vector unit); the chunk walk of the
+// STREAM instances takes `t + 1` inside a chunk and one 32-bit add per chunk (T: next32 in its kernel).
 __device__ __forceinline__ int64_t next_tile(int64_t tile, int64_t cstride, int64_t n_tiles, bool& last, int clog) {
   const int64_t t1 = tile + 1;
   last = (t1 & ((1 << clog) - 1)) == 0 || t1 >= n_tiles;
@@ -483,24 +498,30 @@ typedef HalfRowsT<false> HalfRows;
 // load per lane, row offsets by the shifts in a.ldp_b / a.ldq_b (which push the close bit out), no id of the next
 // position, no key compare; `key` carries the first word, whose sign is "a run closes behind this position".
 // Labels and the skip feature are per-call arrays of E entries and keep their clamped position.
+// TAIL = false (the chunk walk's full-tile body): `tile` and its 32 positions are known to lie inside the list — no clamp at all.
+template <bool EXTRA, bool TAIL>
+__device__ __forceinline__ HalfIn load_half_stream(const D16Params& a, const float* aux, int tile, int nt, int hx, int c) {
+  HalfIn h;
+  // the uniform tile bookkeeping in 32 bits (E < 2^31; a prefetched tile number stays below n_tiles + 16 * the chunk stride):
+  // scalar compares, where the 64-bit signed ones of the ids form run on the vector unit
+  const int e_tile = (TAIL ? (tile < nt ? tile : nt - 1) : tile) * 32;
+  const int rest = (int)a.E - 1 - e_tile;
+  const uint32_t pos = (uint32_t)(16 * hx + c), k = TAIL ? min(pos, (uint32_t)(rest < 31 ? rest : 31)) : pos;
+  const uint2 w = *reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(a.ei + e_tile) + 8u * pos);
+  h.key = (int)w.x;
+  h.key_nxt = 0;
+  h.poff = w.x << a.ldp_b;
+  h.qoff = w.y << a.ldq_b;
+  h.aux = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(aux + e_tile) + 4u * k);
+  h.w_e = EXTRA ? *reinterpret_cast<const float*>(reinterpret_cast<const char*>(a.extra + e_tile) + 4u * k) : 0.f;
+  return h;
+}
 template <bool EXTRA, bool STREAM>
 __device__ __forceinline__ HalfIn load_half(const D16Params& a, const float* aux, int64_t tile, int64_t n_tiles, int hx,
                                             int c) {
   HalfIn h;
   if (STREAM) {
-    // the uniform tile bookkeeping in 32 bits (E < 2^31; a prefetched tile number stays below n_tiles + 16 * the chunk stride):
-    // scalar compares, where the 64-bit signed ones of the ids form run on the vector unit
-    const int nt = (int)n_tiles, t32 = (int)tile;
-    const int e_tile = (t32 < nt ? t32 : nt - 1) * 32;
-    const int rest = (int)a.E - 1 - e_tile;
-    const uint32_t pos = (uint32_t)(16 * hx + c), k = min(pos, (uint32_t)(rest < 31 ? rest : 31));
-    const uint2 w = *reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(a.ei + e_tile) + 8u * pos);
-    h.key = (int)w.x;
-    h.key_nxt = 0;
-    h.poff = w.x << a.ldp_b;
-    h.qoff = w.y << a.ldq_b;
-    h.aux = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(aux + e_tile) + 4u * k);
-    h.w_e = EXTRA ? *reinterpret_cast<const float*>(reinterpret_cast<const char*>(a.extra + e_tile) + 4u * k) : 0.f;
+    h = load_half_stream<EXTRA, true>(a, aux, (int)tile, (int)n_tiles, hx, c);
     return h;
   }
   const int64_t tc = tile < n_tiles ? tile : n_tiles - 1;
@@ -717,179 +738,395 @@ __global__ __launch_bounds__(S_WAVES * 64) void decoder_train16_kernel(
   float carry = 0.f;
   int64_t pidx = 0;
 
-  while (tile < n_tiles) {
-    // chunk bookkeeping as selects (no branch in the loop body): a chunk's first tile starts from its part offset with
-    // no open run; the offset of the wave's next chunk is fetched every tile (one cached dword) and taken over at the end
-    const bool first_of_chunk = (tile & ((1 << clog) - 1)) == 0;
-    carry = first_of_chunk ? 0.f : carry;
-    pidx = first_of_chunk ? (int64_t)__builtin_amdgcn_readfirstlane(poff_cur) : pidx;
-    bool last_tile;
-    const int64_t tile_nxt = next_tile(tile, cstride, n_tiles, last_tile, clog);
-    const int64_t chunk_nxt = (tile >> clog) + cstride;
-    const int poff_nxt = RUNSUM ? rs.part_off[chunk_nxt < n_chunks ? chunk_nxt : n_chunks - 1] : 0;
-    const int store_lim = (int)min((int64_t)31, a.E - 1 - tile * 32);  // uniform: positions <= store_lim exist in the list
-    const int live_lim = (int)min((int64_t)store_lim, e_live - 1 - tile * 32);   // ... <= live_lim are real edges (may be < 0)
-    uint32_t* rec_tile = rec + tile * 256;                             // 8 dwords per edge (rec is required)
-    float* logit_tile = logits + tile * 32;                            // (required with the fused loss, optional otherwise)
-#pragma unroll 1
-    for (int hx = 0; hx < 2; ++hx) {
-      // ids of the next half tile (this tile's second half, or the first half of the wave's next tile)
-      const HalfIn in_nxt = load_half<EXTRA, STREAM>(a, auxp, hx == 0 ? tile : tile_nxt, n_tiles, hx ^ 1, c);    // one load site
-      const int pos = 16 * hx + c;
-      const bool live = pos <= live_lim;
+  if constexpr (STREAM) {
+    // ---- chunk walk: loops over the wave's chunks with a counted loop over a chunk's tiles inside.  Every index, limit and
+    // count is a 32-bit scalar (E < 2^31; a prefetched tile number stays below n_tiles + 16 * the chunk stride) — uniform 64-bit
+    // compares have no scalar form on gfx950.  Per CHUNK: the part offset (the next chunk's is requested one chunk ahead),
+    // carry / pidx reset.  Per tile: the tile after it and two pointer steps.
+    // A tile may run the full-tile body (TAIL = false) when it and the tile its second half prefetches (`tn`) both lie before the
+    // list's last tile nt - 1; tn > t, so that is `tn < nt - 1`.  Inside a chunk tn = t + 1; behind its last tile tn is the first
+    // tile of the wave's next chunk, `nfirst`.  So a chunk with nfirst < nt - 1 is a whole chunk of full tiles: the first loop
+    // below.  What is left is the wave's final chunk (nfirst past the list, or on its last tile): the second loop, general body.
+    // TWO top-level loops, each with a tile loop that runs at least once, on purpose: the per-wave LDS addresses of the body
+    // (wave base + lane offset, a dozen of them) are summed in front of a loop only when the body is certain to run in it; with
+    // the full-tile loop as a zero-or-more-trips loop inside one chunk loop they were summed again in every half tile.
+    const int nt = (int)n_tiles, ct = 1 << clog;
+    const int cstep = ((int)gridDim.x * S_WAVES) << clog;              // tiles from one chunk of the wave to its next
+    const int nch = (nt + ct - 1) >> clog;
+    const int e_last = (int)a.E - 1;
+    // One 16-edge half tile, the arithmetic of the ids loop below statement for statement (its comments are there): `in_cur` /
+    // `rows` are the half tile's ids and gathered rows, `in_nxt` the ids of the half tile behind it, loaded by the caller right
+    // in front of this body — where that load always sat.  TAIL = true is the general body: positions past store_lim (the end
+    // of the list) are clamped and enter no sum.  TAIL = false is told that all 32 positions of the tile are real and storable:
+    // no `live`, no selects on scale / g_e, no position clamp.
+    auto half_tile = [&](auto tail_c, int hx, const HalfIn& in_nxt, int live_lim, int store_lim, uint32_t* rec_tile,
+                         float* logit_tile) __attribute__((always_inline)) {
+        constexpr bool TAIL = decltype(tail_c)::value;
+        // the lane's constants again, NOT captured: the optimiser hands the value ranges of such arguments on to the shared
+        // helpers (dgrad_tile, dgrad_masks, run_sums) across calls before it inlines anything, and a value read through the
+        // closure has none — with the captures the ids instances of every kernel compile to other instructions
+        const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
+        const int wfrag0 = c * 128 + ((g ^ wsw(c)) << 4), wfrag1 = wfrag0 ^ 64;
+        const int colp = 16 * (((g & 1) << 1) | (g >> 1)) + c;
+        const int pos = 16 * hx + c;
+        const bool live = !TAIL || pos <= live_lim;
 
-      // h1 fragments (B operand of P1): lane (c, g) holds h1[c][32 ks + 8 g + 0..7]
-      float h[2][8];
-      h1_frags(rows, has_extra, in_cur.w_e, cvl, g, h);
+        // [S1] h1 fragments, P1, the next rows' gathers — the same statements stand in the ids loop below: edit both
+        float h[2][8];
+        h1_frags(rows, has_extra, in_cur.w_e, cvl, g, h);
 
-      // ---- P1: C[j][e] = b2[j] + sum_k W2[j][k] h1[e][k]
-      f32x4 acc[4];
-      uint32_t m1 = 0;                     // relu mask bits of h1 (packed inside the first product, off its split terms)
-      const float xv = p1_logit<false, true>(lds, h, wfrag0, wfrag1, g, b3v, acc, one2, &m1);
-      // the rows of the next half tile fly during the epilogue and the other two products
-      issue_half_rows(a, in_nxt, g, rows);
+        f32x4 acc[4];
+        uint32_t m1 = 0;                     // relu mask bits of h1 (packed inside the first product, off its split terms)
+        const float xv = p1_logit<false, true>(lds, h, wfrag0, wfrag1, g, b3v, acc, one2, &m1);
+        issue_half_rows(a, in_nxt, g, rows);
 
-      // ---- loss, g_e.  A lane past the end of the list looks at the list's last edge again (clamped ids): g_raw is
-      // that edge's dL/dlogit, bit-identical to what its own lane computes, so records and logits are stored by
-      // every lane without a predicate (a dead lane rewrites the last edge's values); only g_e, which feeds the sums,
-      // is zeroed.  No divergent store, hence no branch, in the loop body.
-      float g_e, g_raw;
-      if (FUSED_LOSS) {
-        const float y_e = in_cur.aux;
-        const float scale = live ? inv_denom : 0.f;
-        const float lw = 1.f + (pw - 1.f) * y_e;
-        // t = exp(-|x|) in (0, 1] as ONE v_exp_f32 of -|x| log2(e) (no over / underflow to guard on this side; the single
-        // rounding of the scaled argument moves t by <= |x| 2^-24 relative, i.e. sigmoid by <= 2e-8 absolute at its worst
-        // point |x| = 1): the library expf's two-term range reduction and its range selects were 11 more instructions
-        const float t = __expf(-fabsf(xv));
-        const float u = 1.f + t;
-        float ru = __builtin_amdgcn_rcpf(u);
-        ru = ru * (2.f - u * ru);                     // 1 / (1 + t): one Newton step on the hardware reciprocal
-        const float sig_neg = xv >= 0.f ? t * ru : ru;                              // sigmoid(-x)
-        g_raw = ((1.f - y_e) - lw * sig_neg) * inv_denom;
-        g_e = live ? g_raw : 0.f;
-        // log1p(t) = -log(1 / (1 + t)) off the reciprocal the gradient needs anyway: absolute error <= 1e-7 per term of a
-        // MEAN of O(1) terms (the loss value only; round 3 evaluated log(u) t / (u - 1) with a second Newton reciprocal)
-        const float l1p = -__logf(ru);
-        lossp = fmaf((1.f - y_e) * xv + lw * (l1p + fmaxf(-xv, 0.f)), scale, lossp);
-      } else {
-        g_raw = in_cur.aux;
-        g_e = live ? g_raw : 0.f;
-      }
-      gb3p += g_e;
-      const float g_half = 0.5f * g_e;                  // h1 and h2 are held doubled (relu2x)
-      const int posc = min(pos, store_lim);
-      if (FUSED_LOSS || logits != nullptr)                                // four lane groups, same value
-        *reinterpret_cast<float*>(reinterpret_cast<char*>(logit_tile) + 4u * (uint32_t)posc) = xv;
+        // [S2] loss and dL/dlogit — the same statements stand in the ids loop below: edit both
+        float g_e, g_raw;
+        if (FUSED_LOSS) {
+          const float y_e = in_cur.aux;
+          const float scale = live ? inv_denom : 0.f;
+          const float lw = 1.f + (pw - 1.f) * y_e;
+          const float t = __expf(-fabsf(xv));
+          const float u = 1.f + t;
+          float ru = __builtin_amdgcn_rcpf(u);
+          ru = ru * (2.f - u * ru);                     // 1 / (1 + t): one Newton step on the hardware reciprocal
+          const float sig_neg = xv >= 0.f ? t * ru : ru;                              // sigmoid(-x)
+          g_raw = ((1.f - y_e) - lw * sig_neg) * inv_denom;
+          g_e = live ? g_raw : 0.f;
+          const float l1p = -__logf(ru);
+          lossp = fmaf((1.f - y_e) * xv + lw * (l1p + fmaxf(-xv, 0.f)), scale, lossp);
+        } else {
+          g_raw = in_cur.aux;
+          g_e = live ? g_raw : 0.f;
+        }
+        gb3p += g_e;
+        const float g_half = 0.5f * g_e;                  // h1 and h2 are held doubled (relu2x)
+        const int posc = TAIL ? min(pos, store_lim) : pos;
+        if (FUSED_LOSS || logits != nullptr)                                // four lane groups, same value
+          *reinterpret_cast<float*>(reinterpret_cast<char*>(logit_tile) + 4u * (uint32_t)posc) = xv;
 
-      // ---- m2 = [h2 > 0] as bf16 0/1 (A operand of P2 and, transposed through LDS, of P3); gw3 partials
-      bf16x8 a2[2];
-      uint32_t m2 = 0;
-      {
-        u32x4 aw[2];
+        // [S3] m2 operand, dL/dw3 partials, m2 image — the same statements stand in the ids loop below: edit both
+        bf16x8 a2[2];
+        uint32_t m2 = 0;
+        {
+          u32x4 aw[2];
 #pragma unroll
-        for (int jb = 0; jb < 4; ++jb)
+          for (int jb = 0; jb < 4; ++jb)
 #pragma unroll
-          for (int pr = 0; pr < 2; ++pr) {
-            const float h2a = acc[jb][2 * pr], h2b = acc[jb][2 * pr + 1];
-            gw3a[jb][2 * pr] = fmaf(g_half, h2a, gw3a[jb][2 * pr]);            // (g_e / 2) (2 h2)
-            gw3a[jb][2 * pr + 1] = fmaf(g_half, h2b, gw3a[jb][2 * pr + 1]);
-            // the pair as two 0/1 halves: top halves packed by one v_perm_b32, [!= 0] by one v_pk_min_u16 (h2 >= 0 after
-            // the relu: its top half is non-zero exactly for a positive normal float)
-            const uint32_t t2 = nz16x2(__builtin_amdgcn_perm(__builtin_bit_cast(uint32_t, h2b), __builtin_bit_cast(uint32_t, h2a),
-                                                             0x07060302u), one2);
-            m2 = (m2 << 1) | t2;
-            aw[jb >> 1][2 * (jb & 1) + pr] = __umul24(t2, 0x3f80u);    // bf16 1.0 / 0.0 (v_mul_u32_u24: full rate; the
-                                                                      // optimiser cannot see t2 < 2^17 behind `one2`)
+            for (int pr = 0; pr < 2; ++pr) {
+              const float h2a = acc[jb][2 * pr], h2b = acc[jb][2 * pr + 1];
+              gw3a[jb][2 * pr] = fmaf(g_half, h2a, gw3a[jb][2 * pr]);            // (g_e / 2) (2 h2)
+              gw3a[jb][2 * pr + 1] = fmaf(g_half, h2b, gw3a[jb][2 * pr + 1]);
+              const uint32_t t2 = nz16x2(__builtin_amdgcn_perm(__builtin_bit_cast(uint32_t, h2b), __builtin_bit_cast(uint32_t, h2a),
+                                                               0x07060302u), one2);
+              m2 = (m2 << 1) | t2;
+              aw[jb >> 1][2 * (jb & 1) + pr] = __umul24(t2, 0x3f80u);    // bf16 1.0 / 0.0 (v_mul_u32_u24)
+            }
+          a2[0] = __builtin_bit_cast(bf16x8, aw[0]);
+          a2[1] = __builtin_bit_cast(bf16x8, aw[1]);
+        }
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+          struct P { short4v lo, hi; };
+          const P pk = __builtin_bit_cast(P, a2[t]);
+          *reinterpret_cast<short4v*>(wv + WV_M2 + (m2w ^ ((2 * t) << 5))) = pk.lo;        // columns 16 (2t) + 4 g ..
+          *reinterpret_cast<short4v*>(wv + WV_M2 + (m2w ^ ((2 * t + 1) << 5))) = pk.hi;    // columns 16 (2t+1) + 4 g ..
+        }
+        // [S4] Hg images, P3, records — the same statements stand in the ids loop below: edit both
+        auto write_hg = [&](int ks) {
+          float hg[8];
+#pragma unroll
+          for (int s = 0; s < 8; ++s) hg[s] = g_half * h[ks][s];             // (g_e / 2) (2 h1)
+          const Split3 sb = split8(hg);
+          const int off = WV_HG + (ks ? hgw1 : hgw0);
+          *reinterpret_cast<bf16x8*>(wv + off) = sb.hi;
+          *reinterpret_cast<bf16x8*>(wv + off + T_IMG) = sb.mid;
+          *reinterpret_cast<bf16x8*>(wv + off + 2 * T_IMG) = sb.lo;
+        };
+        bf16x8 am[2];
+        auto p3_block = [&](int nb) {
+#pragma unroll
+          for (int term = 2; term >= 0; --term) {
+            const bf16x8 bh = ld_tr8(wv + WV_HG + term * T_IMG, tr3h[0] ^ (nb << 6), tr3h[1] ^ (nb << 6));
+#pragma unroll
+            for (int mb = 0; mb < 2; ++mb)
+              acc3[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am[mb], bh, acc3[mb][nb], 0, 0, 0);
           }
-        a2[0] = __builtin_bit_cast(bf16x8, aw[0]);
-        a2[1] = __builtin_bit_cast(bf16x8, aw[1]);
-      }
+        };
+        write_hg(0);
+        wave_lds_sync();
 #pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        struct P { short4v lo, hi; };
-        const P pk = __builtin_bit_cast(P, a2[t]);
-        *reinterpret_cast<short4v*>(wv + WV_M2 + (m2w ^ ((2 * t) << 5))) = pk.lo;        // columns 16 (2t) + 4 g ..
-        *reinterpret_cast<short4v*>(wv + WV_M2 + (m2w ^ ((2 * t + 1) << 5))) = pk.hi;    // columns 16 (2t+1) + 4 g ..
-      }
-      // ---- Hg = g_e h1 split three ways -> tile images (B operand of P3), one K-step (= one 32-column block of
-      // dL/dW2) at a time: the matrix instructions of block 0 run while the vector unit splits block 1 and packs the
-      // relu bits, those of block 1 while it starts on P2
-      auto write_hg = [&](int ks) {
-        float hg[8];
-#pragma unroll
-        for (int s = 0; s < 8; ++s) hg[s] = g_half * h[ks][s];             // (g_e / 2) (2 h1)
-        const Split3 sb = split8(hg);
-        const int off = WV_HG + (ks ? hgw1 : hgw0);
-        *reinterpret_cast<bf16x8*>(wv + off) = sb.hi;
-        *reinterpret_cast<bf16x8*>(wv + off + T_IMG) = sb.mid;
-        *reinterpret_cast<bf16x8*>(wv + off + 2 * T_IMG) = sb.lo;
-      };
-      // P3: acc3[mb][nb] += m2^T (Hg_lo + Hg_mid + Hg_hi) of column block nb, K = the 16 edges
-      bf16x8 am[2];
-      auto p3_block = [&](int nb) {
-#pragma unroll
-        for (int term = 2; term >= 0; --term) {
-          const bf16x8 bh = ld_tr8(wv + WV_HG + term * T_IMG, tr3h[0] ^ (nb << 6), tr3h[1] ^ (nb << 6));
-#pragma unroll
-          for (int mb = 0; mb < 2; ++mb)
-            acc3[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am[mb], bh, acc3[mb][nb], 0, 0, 0);
+        for (int mb = 0; mb < 2; ++mb) am[mb] = ld_tr8(wv + WV_M2, tr3h[0] ^ (mb << 6), tr3h[1] ^ (mb << 6));
+        __builtin_amdgcn_s_setprio(1);
+        p3_block(0);
+        write_hg(1);
+        const uint32_t recw = (m2 & 0x00ff00ffu) | ((m1 & 0x00ff00ffu) << 8);
+        *reinterpret_cast<uint32_t*>(wv + WV_REC + 16 * c + 4 * g) = recw;
+        *reinterpret_cast<float*>(wv + WV_GL + 4 * c) = g_e;               // the four lane groups write the same value
+        if (has_extra) *reinterpret_cast<float*>(wv + WV_WL + 4 * c) = in_cur.w_e;
+        {
+          char* r = reinterpret_cast<char*>(rec_tile) + (32u * (uint32_t)posc + 4u * (uint32_t)g);
+          *reinterpret_cast<uint32_t*>(r) = recw;
+          *reinterpret_cast<uint32_t*>(r + 16) = __builtin_bit_cast(uint32_t, g_raw);
         }
-      };
-      write_hg(0);
-      wave_lds_sync();
-#pragma unroll
-      for (int mb = 0; mb < 2; ++mb) am[mb] = ld_tr8(wv + WV_M2, tr3h[0] ^ (mb << 6), tr3h[1] ^ (mb << 6));
-      __builtin_amdgcn_s_setprio(1);
-      p3_block(0);
-      write_hg(1);
-      // record dword g of the edge: m2 bits in the low byte of each half (bit 7 - n / 23 - n for the pair n), m1 bits in the
-      // high byte — the T kernel turns the m2 bits into bf16 0 / 1 with one AND + one 24-bit multiply per dword
-      const uint32_t recw = (m2 & 0x00ff00ffu) | ((m1 & 0x00ff00ffu) << 8);
-      *reinterpret_cast<uint32_t*>(wv + WV_REC + 16 * c + 4 * g) = recw;
-      *reinterpret_cast<float*>(wv + WV_GL + 4 * c) = g_e;               // the four lane groups write the same value
-      if (has_extra) *reinterpret_cast<float*>(wv + WV_WL + 4 * c) = in_cur.w_e;
-      {
-        // scalar tile base + 32-bit lane offset (saddr stores); dL/dlogit goes into dwords 4 .. 7: lane group g of the T
-        // kernel reads its mask dword and g_e through ONE address (offsets 0 and 16)
-        char* r = reinterpret_cast<char*>(rec_tile) + (32u * (uint32_t)posc + 4u * (uint32_t)g);
-        *reinterpret_cast<uint32_t*>(r) = recw;
-        *reinterpret_cast<uint32_t*>(r + 16) = __builtin_bit_cast(uint32_t, g_raw);
-      }
-      wave_lds_sync();
-      p3_block(1);
-      __builtin_amdgcn_s_setprio(0);
+        wave_lds_sync();
+        p3_block(1);
+        __builtin_amdgcn_s_setprio(0);
 
-      // ---- P2 + run sums by source
-      if (RUNSUM || has_extra) {
-        f32x4 v[4], gm[4];
-        dgrad_tile<false>(lds, wv + WV_REC, wv + WV_GL, a2, c, g, LDS_W2P + wfrag0, LDS_W2P + wfrag1, v, gm);
-        if (has_extra) {
-          // the skip feature's gradient needs the rows themselves: multiplied out on the side (config 5's instances only);
-          // the run sums below still take the factors, so that they are the same arithmetic in every instance
-          f32x4 pv[4];
+        // [S5] P2, skip-feature gradient, run sums — the same statements stand in the ids loop below: edit both
+        if (RUNSUM || has_extra) {
+          f32x4 v[4], gm[4];
+          dgrad_tile<false>(lds, wv + WV_REC, wv + WV_GL, a2, c, g, LDS_W2P + wfrag0, LDS_W2P + wfrag1, v, gm);
+          if (has_extra) {
+            f32x4 pv[4];
 #pragma unroll
-          for (int kb = 0; kb < 4; ++kb) pv[kb] = v[kb];
-          dgrad_apply(pv, gm);
-          const f32x4 w4 = *reinterpret_cast<const f32x4*>(wv + WV_WL + 16 * g);
+            for (int kb = 0; kb < 4; ++kb) pv[kb] = v[kb];
+            dgrad_apply(pv, gm);
+            const f32x4 w4 = *reinterpret_cast<const f32x4*>(wv + WV_WL + 16 * g);
 #pragma unroll
-          for (int kb = 0; kb < 4; ++kb)
+            for (int kb = 0; kb < 4; ++kb)
 #pragma unroll
-            for (int i = 0; i < 4; ++i) gcv[kb] = fmaf(w4[i], pv[kb][i], gcv[kb]);
+              for (int i = 0; i < 4; ++i) gcv[kb] = fmaf(w4[i], pv[kb][i], gcv[kb]);
+          }
+          if (RUNSUM) {
+            const bool closes = in_cur.key < 0;                          // the sign of the position's first word
+            const unsigned long long bal = __ballot(closes);
+            const unsigned m16 = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(bal & 0xffffull));
+            run_sums(v, gm, m16, carry, rs.part, pidx, wv, lane, c, g, colp);
+          }
         }
-        if (RUNSUM) {
-          // key change, or end of the chunk (STREAM: both are the sign of the position's first word)
-          const bool closes = STREAM ? in_cur.key < 0 : (in_cur.key != in_cur.key_nxt || (pos == 31 && last_tile));
-          const unsigned long long bal = __ballot(closes);
-          const unsigned m16 = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(bal & 0xffffull));
-          run_sums(v, gm, m16, carry, rs.part, pidx, wv, lane, c, g, colp);
+        wave_lds_sync();          // the next half tile overwrites the images / recl / gl
+        in_cur = in_nxt;
+    };
+    int first = (int)tile, poff = poff_cur;
+    // whole chunks of full tiles
+    while (first + cstep < nt - 1) {
+      const int nfirst = first + cstep, end = first + ct;
+      const int poff_nxt = rs.part_off[nfirst >> clog];                // requested one chunk ahead
+      carry = 0.f;
+      pidx = (int64_t)__builtin_amdgcn_readfirstlane(poff);
+      uint32_t* rec_tile = rec + (int64_t)first * 256;                 // 8 dwords per edge (rec is required)
+      float* logit_tile = logits + (int64_t)first * 32;                // (required with the fused loss, optional otherwise)
+      int t = first;
+#pragma unroll 1
+      do {
+        const int tn = t + 1 == end ? nfirst : t + 1;
+#pragma unroll 1
+        for (int hx = 0; hx < 2; ++hx) {
+          // ids of the next half tile (this tile's second half, or the first half of the wave's next tile)
+          const HalfIn in_nxt = load_half_stream<EXTRA, false>(a, auxp, hx == 0 ? t : tn, nt, hx ^ 1, c);    // one load site
+          half_tile(std::false_type{}, hx, in_nxt, 31, 31, rec_tile, logit_tile);
         }
-      }
-      wave_lds_sync();          // the next half tile overwrites the images / recl / gl
-      in_cur = in_nxt;
+        rec_tile += 256;
+        logit_tile += 32;
+      } while (++t < end);
+      poff = poff_nxt;
+      first = nfirst;
     }
-    poff_cur = last_tile ? poff_nxt : poff_cur;
-    tile = tile_nxt;
+    // the wave's final chunk: the general body, the prefetch behind its last tile clamped to the list
+    while (first < nt) {
+      const int nfirst = first + cstep, cn = nfirst >> clog, end = min(first + ct, nt);
+      const int poff_nxt = rs.part_off[cn < nch ? cn : nch - 1];
+      carry = 0.f;
+      pidx = (int64_t)__builtin_amdgcn_readfirstlane(poff);
+      uint32_t* rec_tile = rec + (int64_t)first * 256;
+      float* logit_tile = logits + (int64_t)first * 32;
+      int t = first;
+#pragma unroll 1
+      do {
+        const int tn = t + 1 == end ? nfirst : t + 1;
+        const int store_lim = min(31, e_last - t * 32);                // uniform: positions <= store_lim exist in the list
+#pragma unroll 1
+        for (int hx = 0; hx < 2; ++hx) {
+          const HalfIn in_nxt = load_half_stream<EXTRA, true>(a, auxp, hx == 0 ? t : tn, nt, hx ^ 1, c);
+          half_tile(std::true_type{}, hx, in_nxt, store_lim, store_lim, rec_tile, logit_tile);
+        }
+        rec_tile += 256;
+        logit_tile += 32;
+      } while (++t < end);
+      poff = poff_nxt;
+      first = nfirst;
+    }
+  } else {
+    while (tile < n_tiles) {
+      // chunk bookkeeping as selects (no branch in the loop body): a chunk's first tile starts from its part offset with
+      // no open run; the offset of the wave's next chunk is fetched every tile (one cached dword) and taken over at the end
+      const bool first_of_chunk = (tile & ((1 << clog) - 1)) == 0;
+      carry = first_of_chunk ? 0.f : carry;
+      pidx = first_of_chunk ? (int64_t)__builtin_amdgcn_readfirstlane(poff_cur) : pidx;
+      bool last_tile;
+      const int64_t tile_nxt = next_tile(tile, cstride, n_tiles, last_tile, clog);
+      const int64_t chunk_nxt = (tile >> clog) + cstride;
+      const int poff_nxt = RUNSUM ? rs.part_off[chunk_nxt < n_chunks ? chunk_nxt : n_chunks - 1] : 0;
+      const int store_lim = (int)min((int64_t)31, a.E - 1 - tile * 32);  // uniform: positions <= store_lim exist in the list
+      const int live_lim = (int)min((int64_t)store_lim, e_live - 1 - tile * 32);   // ... <= live_lim are real edges (may be < 0)
+      uint32_t* rec_tile = rec + tile * 256;                             // 8 dwords per edge (rec is required)
+      float* logit_tile = logits + tile * 32;                            // (required with the fused loss, optional otherwise)
+#pragma unroll 1
+      for (int hx = 0; hx < 2; ++hx) {
+        // ids of the next half tile (this tile's second half, or the first half of the wave's next tile)
+        const HalfIn in_nxt = load_half<EXTRA, false>(a, auxp, hx == 0 ? tile : tile_nxt, n_tiles, hx ^ 1, c);    // one load site
+        const int pos = 16 * hx + c;
+        const bool live = pos <= live_lim;
+
+        // h1 fragments (B operand of P1): lane (c, g) holds h1[c][32 ks + 8 g + 0..7]
+        // [S1] h1 fragments, P1, the next rows' gathers — the same statements stand in half_tile (the STREAM instances' body) above: edit both
+        float h[2][8];
+        h1_frags(rows, has_extra, in_cur.w_e, cvl, g, h);
+
+        // ---- P1: C[j][e] = b2[j] + sum_k W2[j][k] h1[e][k]
+        f32x4 acc[4];
+        uint32_t m1 = 0;                     // relu mask bits of h1 (packed inside the first product, off its split terms)
+        const float xv = p1_logit<false, true>(lds, h, wfrag0, wfrag1, g, b3v, acc, one2, &m1);
+        // the rows of the next half tile fly during the epilogue and the other two products
+        issue_half_rows(a, in_nxt, g, rows);
+
+        // ---- loss, g_e.  A lane past the end of the list looks at the list's last edge again (clamped ids): g_raw is
+        // that edge's dL/dlogit, bit-identical to what its own lane computes, so records and logits are stored by
+        // every lane without a predicate (a dead lane rewrites the last edge's values); only g_e, which feeds the sums,
+        // is zeroed.  No divergent store, hence no branch, in the loop body.
+        // [S2] loss and dL/dlogit — the same statements stand in half_tile (the STREAM instances' body) above: edit both
+        float g_e, g_raw;
+        if (FUSED_LOSS) {
+          const float y_e = in_cur.aux;
+          const float scale = live ? inv_denom : 0.f;
+          const float lw = 1.f + (pw - 1.f) * y_e;
+          // t = exp(-|x|) in (0, 1] as ONE v_exp_f32 of -|x| log2(e) (no over / underflow to guard on this side; the single
+          // rounding of the scaled argument moves t by <= |x| 2^-24 relative, i.e. sigmoid by <= 2e-8 absolute at its worst
+          // point |x| = 1): the library expf's two-term range reduction and its range selects were 11 more instructions
+          const float t = __expf(-fabsf(xv));
+          const float u = 1.f + t;
+          float ru = __builtin_amdgcn_rcpf(u);
+          ru = ru * (2.f - u * ru);                     // 1 / (1 + t): one Newton step on the hardware reciprocal
+          const float sig_neg = xv >= 0.f ? t * ru : ru;                              // sigmoid(-x)
+          g_raw = ((1.f - y_e) - lw * sig_neg) * inv_denom;
+          g_e = live ? g_raw : 0.f;
+          // log1p(t) = -log(1 / (1 + t)) off the reciprocal the gradient needs anyway: absolute error <= 1e-7 per term of a
+          // MEAN of O(1) terms (the loss value only; round 3 evaluated log(u) t / (u - 1) with a second Newton reciprocal)
+          const float l1p = -__logf(ru);
+          lossp = fmaf((1.f - y_e) * xv + lw * (l1p + fmaxf(-xv, 0.f)), scale, lossp);
+        } else {
+          g_raw = in_cur.aux;
+          g_e = live ? g_raw : 0.f;
+        }
+        gb3p += g_e;
+        const float g_half = 0.5f * g_e;                  // h1 and h2 are held doubled (relu2x)
+        const int posc = min(pos, store_lim);
+        if (FUSED_LOSS || logits != nullptr)                                // four lane groups, same value
+          *reinterpret_cast<float*>(reinterpret_cast<char*>(logit_tile) + 4u * (uint32_t)posc) = xv;
+
+        // ---- m2 = [h2 > 0] as bf16 0/1 (A operand of P2 and, transposed through LDS, of P3); gw3 partials
+        // [S3] m2 operand, dL/dw3 partials, m2 image — the same statements stand in half_tile (the STREAM instances' body) above: edit both
+        bf16x8 a2[2];
+        uint32_t m2 = 0;
+        {
+          u32x4 aw[2];
+#pragma unroll
+          for (int jb = 0; jb < 4; ++jb)
+#pragma unroll
+            for (int pr = 0; pr < 2; ++pr) {
+              const float h2a = acc[jb][2 * pr], h2b = acc[jb][2 * pr + 1];
+              gw3a[jb][2 * pr] = fmaf(g_half, h2a, gw3a[jb][2 * pr]);            // (g_e / 2) (2 h2)
+              gw3a[jb][2 * pr + 1] = fmaf(g_half, h2b, gw3a[jb][2 * pr + 1]);
+              // the pair as two 0/1 halves: top halves packed by one v_perm_b32, [!= 0] by one v_pk_min_u16 (h2 >= 0 after
+              // the relu: its top half is non-zero exactly for a positive normal float)
+              const uint32_t t2 = nz16x2(__builtin_amdgcn_perm(__builtin_bit_cast(uint32_t, h2b), __builtin_bit_cast(uint32_t, h2a),
+                                                               0x07060302u), one2);
+              m2 = (m2 << 1) | t2;
+              aw[jb >> 1][2 * (jb & 1) + pr] = __umul24(t2, 0x3f80u);    // bf16 1.0 / 0.0 (v_mul_u32_u24: full rate; the
+                                                                        // optimiser cannot see t2 < 2^17 behind `one2`)
+            }
+          a2[0] = __builtin_bit_cast(bf16x8, aw[0]);
+          a2[1] = __builtin_bit_cast(bf16x8, aw[1]);
+        }
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+          struct P { short4v lo, hi; };
+          const P pk = __builtin_bit_cast(P, a2[t]);
+          *reinterpret_cast<short4v*>(wv + WV_M2 + (m2w ^ ((2 * t) << 5))) = pk.lo;        // columns 16 (2t) + 4 g ..
+          *reinterpret_cast<short4v*>(wv + WV_M2 + (m2w ^ ((2 * t + 1) << 5))) = pk.hi;    // columns 16 (2t+1) + 4 g ..
+        }
+        // ---- Hg = g_e h1 split three ways -> tile images (B operand of P3), one K-step (= one 32-column block of
+        // dL/dW2) at a time: the matrix instructions of block 0 run while the vector unit splits block 1 and packs the
+        // relu bits, those of block 1 while it starts on P2
+        // [S4] Hg images, P3, records — the same statements stand in half_tile (the STREAM instances' body) above: edit both
+        auto write_hg = [&](int ks) {
+          float hg[8];
+#pragma unroll
+          for (int s = 0; s < 8; ++s) hg[s] = g_half * h[ks][s];             // (g_e / 2) (2 h1)
+          const Split3 sb = split8(hg);
+          const int off = WV_HG + (ks ? hgw1 : hgw0);
+          *reinterpret_cast<bf16x8*>(wv + off) = sb.hi;
+          *reinterpret_cast<bf16x8*>(wv + off + T_IMG) = sb.mid;
+          *reinterpret_cast<bf16x8*>(wv + off + 2 * T_IMG) = sb.lo;
+        };
+        // P3: acc3[mb][nb] += m2^T (Hg_lo + Hg_mid + Hg_hi) of column block nb, K = the 16 edges
+        bf16x8 am[2];
+        auto p3_block = [&](int nb) {
+#pragma unroll
+          for (int term = 2; term >= 0; --term) {
+            const bf16x8 bh = ld_tr8(wv + WV_HG + term * T_IMG, tr3h[0] ^ (nb << 6), tr3h[1] ^ (nb << 6));
+#pragma unroll
+            for (int mb = 0; mb < 2; ++mb)
+              acc3[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am[mb], bh, acc3[mb][nb], 0, 0, 0);
+          }
+        };
+        write_hg(0);
+        wave_lds_sync();
+#pragma unroll
+        for (int mb = 0; mb < 2; ++mb) am[mb] = ld_tr8(wv + WV_M2, tr3h[0] ^ (mb << 6), tr3h[1] ^ (mb << 6));
+        __builtin_amdgcn_s_setprio(1);
+        p3_block(0);
+        write_hg(1);
+        // record dword g of the edge: m2 bits in the low byte of each half (bit 7 - n / 23 - n for the pair n), m1 bits in the
+        // high byte — the T kernel turns the m2 bits into bf16 0 / 1 with one AND + one 24-bit multiply per dword
+        const uint32_t recw = (m2 & 0x00ff00ffu) | ((m1 & 0x00ff00ffu) << 8);
+        *reinterpret_cast<uint32_t*>(wv + WV_REC + 16 * c + 4 * g) = recw;
+        *reinterpret_cast<float*>(wv + WV_GL + 4 * c) = g_e;               // the four lane groups write the same value
+        if (has_extra) *reinterpret_cast<float*>(wv + WV_WL + 4 * c) = in_cur.w_e;
+        {
+          // scalar tile base + 32-bit lane offset (saddr stores); dL/dlogit goes into dwords 4 .. 7: lane group g of the T
+          // kernel reads its mask dword and g_e through ONE address (offsets 0 and 16)
+          char* r = reinterpret_cast<char*>(rec_tile) + (32u * (uint32_t)posc + 4u * (uint32_t)g);
+          *reinterpret_cast<uint32_t*>(r) = recw;
+          *reinterpret_cast<uint32_t*>(r + 16) = __builtin_bit_cast(uint32_t, g_raw);
+        }
+        wave_lds_sync();
+        p3_block(1);
+        __builtin_amdgcn_s_setprio(0);
+
+        // ---- P2 + run sums by source
+        // [S5] P2, skip-feature gradient, run sums — the same statements stand in half_tile (the STREAM instances' body) above: edit both
+        if (RUNSUM || has_extra) {
+          f32x4 v[4], gm[4];
+          dgrad_tile<false>(lds, wv + WV_REC, wv + WV_GL, a2, c, g, LDS_W2P + wfrag0, LDS_W2P + wfrag1, v, gm);
+          if (has_extra) {
+            // the skip feature's gradient needs the rows themselves: multiplied out on the side (config 5's instances only);
+            // the run sums below still take the factors, so that they are the same arithmetic in every instance
+            f32x4 pv[4];
+#pragma unroll
+            for (int kb = 0; kb < 4; ++kb) pv[kb] = v[kb];
+            dgrad_apply(pv, gm);
+            const f32x4 w4 = *reinterpret_cast<const f32x4*>(wv + WV_WL + 16 * g);
+#pragma unroll
+            for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+              for (int i = 0; i < 4; ++i) gcv[kb] = fmaf(w4[i], pv[kb][i], gcv[kb]);
+          }
+          if (RUNSUM) {
+            // key change, or end of the chunk
+            const bool closes = in_cur.key != in_cur.key_nxt || (pos == 31 && last_tile);
+            const unsigned long long bal = __ballot(closes);
+            const unsigned m16 = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(bal & 0xffffull));
+            run_sums(v, gm, m16, carry, rs.part, pidx, wv, lane, c, g, colp);
+          }
+        }
+        wave_lds_sync();          // the next half tile overwrites the images / recl / gl
+        in_cur = in_nxt;
+      }
+      poff_cur = last_tile ? poff_nxt : poff_cur;
+      tile = tile_nxt;
+    }
   }
 
   // ---- finish: per-lane partials -> workgroup slab.  The eight waves are added as a fixed binary tree,
@@ -1012,21 +1249,33 @@ __global__ __launch_bounds__(S_WAVES * 64) void decoder_train16_kernel(
 // none) the keys route below runs exactly as before.
 struct TIds { uint32_t e; int key, key_nxt; };       // STREAM: e = the word, keys unused (dead registers)
 struct TIn { uint32_t recw; float g_e; uint32_t e; int key, key_nxt; };
+// The stream's words of half `hx` of tile `tile`, all uniform bookkeeping in 32 bits (scalar compares).  TAIL: the tile number
+// is clamped to the list's last tile and the position to its last position — the padding of the last tile repeats the last
+// position's word; its close bit is sorted out per tile (close_mask).  TAIL = false: all 32 positions are known to exist.
+template <bool TAIL>
+__device__ __forceinline__ TIds load_tpos(const uint32_t* tpos, int E, int tile, int nt, int hx, int c) {
+  TIds t;
+  const int p_tile = (TAIL ? (tile < nt ? tile : nt - 1) : tile) * 32;
+  const int rest = E - 1 - p_tile;
+  const uint32_t pos = (uint32_t)(16 * hx + c), k = TAIL ? min(pos, (uint32_t)(rest < 31 ? rest : 31)) : pos;
+  t.key = t.key_nxt = 0;
+  t.e = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(tpos + p_tile) + 4u * k);
+  return t;
+}
 template <bool PERM, bool KEYS, bool STREAM>
 __device__ __forceinline__ TIds load_ids(const int32_t* perm, const int32_t* keys, const uint32_t* tpos, int64_t E, int64_t tile,
                                          int64_t n_tiles, int hx, int c) {
   TIds t;
+  if (STREAM) {
+    t = load_tpos<true>(tpos, (int)E, (int)tile, (int)n_tiles, hx, c);
+    return t;
+  }
   const int64_t tc = tile < n_tiles ? tile : n_tiles - 1;
   const int64_t p_tile = tc * 32;
   const int64_t rest = E - 1 - p_tile;
   const uint32_t lim = (uint32_t)(rest < 31 ? rest : 31);                 // uniform: last valid position inside the tile
   const uint32_t k = min((uint32_t)(16 * hx + c), lim);
   t.key = t.key_nxt = 0;
-  if (STREAM) {
-    // the padding of the last tile repeats the last position's word; its close bit is sorted out per tile (close_mask)
-    t.e = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(tpos + p_tile) + 4u * k);
-    return t;
-  }
   const uint32_t lim_n = (uint32_t)(rest < 32 ? rest : 32);               // position 32 = first position of the next tile
   const uint32_t kn = min(k + 1u, lim_n);
   if (KEYS) {                                                             // (the parameter sums alone take no keys: NULL)
@@ -1052,8 +1301,9 @@ __device__ __forceinline__ TIn load_rec(const char* recg, const TIds& id) {
 // STREAM: the close bits of a tile's 32 positions that count.  In the last tile of a list whose length is no multiple of 32,
 // positions lim .. 31 all repeat the word of position lim (the last of the list, whose bit is set: it ends its chunk): the
 // run closes ONCE, at position 31 — where the keys route closes it (its clamped key == key_nxt everywhere but there).
-__device__ __forceinline__ uint32_t close_mask(int64_t E, int64_t tile) {
-  const int64_t rest = E - 1 - tile * 32;
+// Only the general (TAIL) body of the chunk walk asks: every other tile is full and takes its ballot as it is.
+__device__ __forceinline__ uint32_t close_mask(int E, int tile) {
+  const int rest = E - 1 - tile * 32;
   return rest < 31 ? (((1u << (uint32_t)rest) - 1u) | 0x80000000u) : 0xffffffffu;
 }
 
@@ -1103,90 +1353,200 @@ __global__ __launch_bounds__(T_WAVES * 64) void decoder_dgrad16_kernel(
   int poff_cur = (RUN && tile < n_tiles) ? rs.part_off[tile >> clog] : 0;
   float carry = 0.f;
   int64_t pidx = 0;
-  while (tile < n_tiles) {
-    const bool first_of_chunk = (tile & ((1 << clog) - 1)) == 0;
-    carry = first_of_chunk ? 0.f : carry;
-    pidx = first_of_chunk ? (int64_t)__builtin_amdgcn_readfirstlane(poff_cur) : pidx;
-    const bool last_tile = last1;                                      // this tile ends its chunk
-    const int64_t chunk_nxt = (tile >> clog) + cstride;
-    const int poff_nxt = RUN ? rs.part_off[chunk_nxt < n_chunks ? chunk_nxt : n_chunks - 1] : 0;
-    const int live_lim = (int)min((int64_t)31, e_live - 1 - tile * 32);
-    bool last2;
-    const int64_t tile2 = next_tile(tile1 < n_tiles ? tile1 : n_tiles - 1, cstride, n_tiles, last2, clog);
-    TIn nxt[2];
+
+  if constexpr (STREAM) {
+    // ---- chunk walk (as in S): loops over the wave's chunks with a counted loop over a chunk's tiles inside, every index a
+    // 32-bit scalar.  Per chunk: the part offset (the next chunk's is requested one chunk ahead), carry / pidx reset.  T prefetches
+    // the words of the tile TWO behind the current one (`t2`), so a tile may run the full-tile body when t2 < nt - 1 (then the
+    // tile itself and the one between are full too).  Every t2 of a chunk is at most nfirst + cstep, the first tile of the wave's
+    // chunk after next: a chunk with first + 2 cstep < nt - 1 is a whole chunk of full tiles — the first loop.  The wave's last
+    // two chunks take the general body — the second loop.  Two top-level loops for the reason given in S.
+    const int nt = (int)n_tiles, ct = 1 << clog, e32 = (int)E;
+    const int cstep = ((int)gridDim.x * T_WAVES) << clog;              // tiles from one chunk of the wave to its next
+    const int nch = (nt + ct - 1) >> clog;
+    // the wave's tile behind t: the next one of its chunk, or the first of its next chunk
+    auto next32 = [&](int t) { return (((t + 1) & (ct - 1)) == 0 || t + 1 >= nt) ? ((t >> clog) << clog) + cstep : t + 1; };
+    // One 32-edge tile, the arithmetic of the keys loop below statement for statement (its comments are there): `cur` holds the
+    // tile's records, `ids_nxt` the words of the wave's next tile, t2 is the tile after that, whose words are requested here.
+    // TAIL = true is the general body: positions past live_lim enter no sum, the close bits of the list's last tile go through
+    // `cmask` (close_mask), the word loads are clamped to the list.  TAIL = false: all 32 positions of this tile and of t2 are
+    // real — no live_lim, no close_mask, no clamp.
+    auto tile_body = [&](auto tail_c, int t2, int live_lim, uint32_t cmask) __attribute__((always_inline)) {
+      constexpr bool TAIL = decltype(tail_c)::value;
+      // the lane's constants again, not captured (see the S kernel's half_tile: the ids / keys instances stay what they were)
+      const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
+      const int wfrag0 = c * 128 + ((g ^ wsw(c)) << 4), wfrag1 = wfrag0 ^ 64;
+      const int colp = 16 * (((g & 1) << 1) | (g >> 1)) + c;
+      // [T1] records of the next tile, words / ids of the one after — the same statements stand in the keys loop below: edit both
+      TIn nxt[2];
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      nxt[h] = load_rec(recg, ids_nxt[h]);
-      ids_nxt[h] = load_ids<PERM, RUN, STREAM>(perm, keys, tpos, E, tile2, n_tiles, h, c);
-    }
-    bf16x8 a2[2][2];
+      for (int h = 0; h < 2; ++h) {
+        nxt[h] = load_rec(recg, ids_nxt[h]);
+        ids_nxt[h] = load_tpos<TAIL>(tpos, e32, t2, nt, h, c);
+      }
+      // [T2] LDS records, m2 operands, dL/db2 partials — the same statements stand in the keys loop below: edit both
+      bf16x8 a2[2][2];
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const float g_e = 16 * h + c <= live_lim ? cur[h].g_e : 0.f;
-      const uint32_t recw = cur[h].recw;
-      *reinterpret_cast<uint32_t*>(wv + TW_REC + 256 * h + 16 * c + 4 * g) = recw;
-      *reinterpret_cast<float*>(wv + TW_GL + 64 * h + 4 * c) = g_e;
-      // m2 bits of lane (c, g): pair n = 4 t + qd (elements 2 qd, 2 qd + 1 of K-step t) sits at bits 7 - n and 23 - n:
-      // (recw & (0x10001 << p)) * (0x3c00 >> p) = 0x3c00 / 0 in each half (p <= 7: the products stay inside their halves).
-      // 0x3c00 is T's mask value (T_MASK16): 2^-7 as the bf16 A operand of P2, whose B images are 128 W2' (stage_weights16,
-      // which = 2 with scale 128) — the products, hence P2's accumulators, are bit for bit those of 1.0 x W2' — and 1.0 as
-      // an IEEE half, which v_fma_mix_f32 takes as an operand of the dL/db2 sums below.
+      for (int h = 0; h < 2; ++h) {
+        const float g_e = (!TAIL || 16 * h + c <= live_lim) ? cur[h].g_e : 0.f;
+        const uint32_t recw = cur[h].recw;
+        *reinterpret_cast<uint32_t*>(wv + TW_REC + 256 * h + 16 * c + 4 * g) = recw;
+        *reinterpret_cast<float*>(wv + TW_GL + 64 * h + 4 * c) = g_e;
 #pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        u32x4 w;
-        uint32_t yb[4];
-#pragma unroll
-        for (int qd = 0; qd < 4; ++qd) {
-          const int p = 7 - (4 * t + qd);
-          yb[qd] = recw & (0x00010001u << p);
-          asm volatile("" : "+v"(yb[qd]));      // opaque: keeps ONE and per pair (the optimiser otherwise re-derives byte 0
-          w[qd] = __umul24(yb[qd], T_MASK16 >> p);    //                                  from recw with a second and below)
-        }
-        a2[h][t] = __builtin_bit_cast(bf16x8, w);
-        if (gb2_slabs != nullptr) {
-          // dL/db2 partials: the mask halves of the operand words themselves, 1.0 / 0.0 as IEEE halves — one v_fma_mix_f32
-          // per element (half operand by op_sel; tools/valu_issue_rate.hip: issues like v_fma_f32, every lane right beside
-          // bf16 MFMAs, profiles/t_vector_stream.md).  (Until this form each element cost a v_cvt_f32_ubyte of its record
-          // bit + a v_fma_f32, the sums carrying a factor 2^p; round 3 rebuilt 1.0 / 0.0 from a bf16 1.0 operand: the
-          // optimiser folded that into a v_mul_lo_u32 per pair, a quarter-rate instruction, 16 per tile.)
+        for (int t = 0; t < 2; ++t) {
+          u32x4 w;
+          uint32_t yb[4];
 #pragma unroll
           for (int qd = 0; qd < 4; ++qd) {
-            const int jb = 2 * t + (qd >> 1), i0 = 2 * (qd & 1);
-            const f16x2 m = __builtin_bit_cast(f16x2, (uint32_t)w[qd]);
-            gb2a[jb][i0] = fmaf((float)m[0], g_e, gb2a[jb][i0]);
-            gb2a[jb][i0 + 1] = fmaf((float)m[1], g_e, gb2a[jb][i0 + 1]);
+            const int p = 7 - (4 * t + qd);
+            yb[qd] = recw & (0x00010001u << p);
+            asm volatile("" : "+v"(yb[qd]));
+            w[qd] = __umul24(yb[qd], T_MASK16 >> p);
+          }
+          a2[h][t] = __builtin_bit_cast(bf16x8, w);
+          if (gb2_slabs != nullptr) {
+#pragma unroll
+            for (int qd = 0; qd < 4; ++qd) {
+              const int jb = 2 * t + (qd >> 1), i0 = 2 * (qd & 1);
+              const f16x2 m = __builtin_bit_cast(f16x2, (uint32_t)w[qd]);
+              gb2a[jb][i0] = fmaf((float)m[0], g_e, gb2a[jb][i0]);
+              gb2a[jb][i0 + 1] = fmaf((float)m[1], g_e, gb2a[jb][i0 + 1]);
+            }
           }
         }
       }
-    }
-    wave_lds_sync();
-    if (RUN) {
+      wave_lds_sync();
+      // [T3] P2 and run sums — the same statements stand in the keys loop below: edit both
       f32x4 v[2][4];
       dgrad_tile2(lds, a2, wfrag0, wfrag1, v);
-      const uint32_t cmask = STREAM ? close_mask(E, tile) : 0u;          // scalar: wave-uniform operands
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
         f32x4 gm[4];
         dgrad_masks(wv + TW_REC + 256 * h, wv + TW_GL + 64 * h, c, g, gm);
-        unsigned m16;
-        if (STREAM) {
-          const unsigned long long bal = __ballot((int)cur[h].e < 0);                           // the word's close bit
-          m16 = ((unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(bal & 0xffffull)) & (cmask >> (16 * h))) & 0xffffu;
-        } else {
-          const bool closes = cur[h].key != cur[h].key_nxt || (h == 1 && c == 15 && last_tile);   // key change, or end of the chunk
-          const unsigned long long bal = __ballot(closes);
-          m16 = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(bal & 0xffffull));
-        }
+        const unsigned long long bal = __ballot((int)cur[h].e < 0);                           // the word's close bit
+        unsigned m16 = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(bal & 0xffffull));
+        if (TAIL) m16 = (m16 & (cmask >> (16 * h))) & 0xffffu;          // scalar: wave-uniform operands
         run_sums(v[h], gm, m16, carry, rs.part, pidx, wv, lane, c, g, colp);
       }
-    }
-    wave_lds_sync();          // the next tile overwrites recl / gl
+      wave_lds_sync();          // the next tile overwrites recl / gl
 #pragma unroll
-    for (int h = 0; h < 2; ++h) cur[h] = nxt[h];
-    poff_cur = last_tile ? poff_nxt : poff_cur;
-    tile = tile1;
-    tile1 = tile2;
-    last1 = last2;
+      for (int h = 0; h < 2; ++h) cur[h] = nxt[h];
+    };
+    int first = (int)tile, t1 = (int)tile1, poff = poff_cur;
+    // whole chunks of full tiles
+    while (first + 2 * cstep < nt - 1) {
+      const int nfirst = first + cstep, end = first + ct;
+      const int poff_nxt = rs.part_off[nfirst >> clog];                // requested one chunk ahead
+      carry = 0.f;
+      pidx = (int64_t)__builtin_amdgcn_readfirstlane(poff);
+      int t = first;
+#pragma unroll 1
+      do {
+        const int t2 = next32(t1);
+        tile_body(std::false_type{}, t2, 31, 0u);
+        t1 = t2;
+      } while (++t < end);
+      poff = poff_nxt;
+      first = nfirst;
+    }
+    // the wave's last two chunks: the general body, prefetches clamped to the list
+    while (first < nt) {
+      const int nfirst = first + cstep, cn = nfirst >> clog, end = min(first + ct, nt);
+      const int poff_nxt = rs.part_off[cn < nch ? cn : nch - 1];
+      carry = 0.f;
+      pidx = (int64_t)__builtin_amdgcn_readfirstlane(poff);
+      int t = first;
+#pragma unroll 1
+      do {
+        const int t2 = next32(t1 < nt ? t1 : nt - 1);
+        tile_body(std::true_type{}, t2, min(31, e32 - 1 - t * 32), close_mask(e32, t));
+        t1 = t2;
+      } while (++t < end);
+      poff = poff_nxt;
+      first = nfirst;
+    }
+  } else {
+    while (tile < n_tiles) {
+      const bool first_of_chunk = (tile & ((1 << clog) - 1)) == 0;
+      carry = first_of_chunk ? 0.f : carry;
+      pidx = first_of_chunk ? (int64_t)__builtin_amdgcn_readfirstlane(poff_cur) : pidx;
+      const bool last_tile = last1;                                      // this tile ends its chunk
+      const int64_t chunk_nxt = (tile >> clog) + cstride;
+      const int poff_nxt = RUN ? rs.part_off[chunk_nxt < n_chunks ? chunk_nxt : n_chunks - 1] : 0;
+      const int live_lim = (int)min((int64_t)31, e_live - 1 - tile * 32);
+      bool last2;
+      const int64_t tile2 = next_tile(tile1 < n_tiles ? tile1 : n_tiles - 1, cstride, n_tiles, last2, clog);
+      // [T1] records of the next tile, words / ids of the one after — the same statements stand in tile_body (the STREAM instance's body) above: edit both
+      TIn nxt[2];
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        nxt[h] = load_rec(recg, ids_nxt[h]);
+        ids_nxt[h] = load_ids<PERM, RUN, false>(perm, keys, tpos, E, tile2, n_tiles, h, c);
+      }
+      // [T2] LDS records, m2 operands, dL/db2 partials — the same statements stand in tile_body (the STREAM instance's body) above: edit both
+      bf16x8 a2[2][2];
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const float g_e = 16 * h + c <= live_lim ? cur[h].g_e : 0.f;
+        const uint32_t recw = cur[h].recw;
+        *reinterpret_cast<uint32_t*>(wv + TW_REC + 256 * h + 16 * c + 4 * g) = recw;
+        *reinterpret_cast<float*>(wv + TW_GL + 64 * h + 4 * c) = g_e;
+        // m2 bits of lane (c, g): pair n = 4 t + qd (elements 2 qd, 2 qd + 1 of K-step t) sits at bits 7 - n and 23 - n:
+        // (recw & (0x10001 << p)) * (0x3c00 >> p) = 0x3c00 / 0 in each half (p <= 7: the products stay inside their halves).
+        // 0x3c00 is T's mask value (T_MASK16): 2^-7 as the bf16 A operand of P2, whose B images are 128 W2' (stage_weights16,
+        // which = 2 with scale 128) — the products, hence P2's accumulators, are bit for bit those of 1.0 x W2' — and 1.0 as
+        // an IEEE half, which v_fma_mix_f32 takes as an operand of the dL/db2 sums below.
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+          u32x4 w;
+          uint32_t yb[4];
+#pragma unroll
+          for (int qd = 0; qd < 4; ++qd) {
+            const int p = 7 - (4 * t + qd);
+            yb[qd] = recw & (0x00010001u << p);
+            asm volatile("" : "+v"(yb[qd]));      // opaque: keeps ONE and per pair (the optimiser otherwise re-derives byte 0
+            w[qd] = __umul24(yb[qd], T_MASK16 >> p);    //                                  from recw with a second and below)
+          }
+          a2[h][t] = __builtin_bit_cast(bf16x8, w);
+          if (gb2_slabs != nullptr) {
+            // dL/db2 partials: the mask halves of the operand words themselves, 1.0 / 0.0 as IEEE halves — one v_fma_mix_f32
+            // per element (half operand by op_sel; tools/valu_issue_rate.hip: issues like v_fma_f32, every lane right beside
+            // bf16 MFMAs, profiles/t_vector_stream.md).  (Until this form each element cost a v_cvt_f32_ubyte of its record
+            // bit + a v_fma_f32, the sums carrying a factor 2^p; round 3 rebuilt 1.0 / 0.0 from a bf16 1.0 operand: the
+            // optimiser folded that into a v_mul_lo_u32 per pair, a quarter-rate instruction, 16 per tile.)
+#pragma unroll
+            for (int qd = 0; qd < 4; ++qd) {
+              const int jb = 2 * t + (qd >> 1), i0 = 2 * (qd & 1);
+              const f16x2 m = __builtin_bit_cast(f16x2, (uint32_t)w[qd]);
+              gb2a[jb][i0] = fmaf((float)m[0], g_e, gb2a[jb][i0]);
+              gb2a[jb][i0 + 1] = fmaf((float)m[1], g_e, gb2a[jb][i0 + 1]);
+            }
+          }
+        }
+      }
+      wave_lds_sync();
+      if (RUN) {
+        // [T3] P2 and run sums — the same statements stand in tile_body (the STREAM instance's body) above: edit both
+        f32x4 v[2][4];
+        dgrad_tile2(lds, a2, wfrag0, wfrag1, v);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          f32x4 gm[4];
+          dgrad_masks(wv + TW_REC + 256 * h, wv + TW_GL + 64 * h, c, g, gm);
+          const bool closes = cur[h].key != cur[h].key_nxt || (h == 1 && c == 15 && last_tile);   // key change, or end of the chunk
+          const unsigned long long bal = __ballot(closes);
+          const unsigned m16 = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(bal & 0xffffull));
+          run_sums(v[h], gm, m16, carry, rs.part, pidx, wv, lane, c, g, colp);
+        }
+      }
+      wave_lds_sync();          // the next tile overwrites recl / gl
+#pragma unroll
+      for (int h = 0; h < 2; ++h) cur[h] = nxt[h];
+      poff_cur = last_tile ? poff_nxt : poff_cur;
+      tile = tile1;
+      tile1 = tile2;
+      last1 = last2;
+    }
   }
   if (gb2_slabs != nullptr) {
     // dL/db2 partials of the workgroup in fixed wave order

@@ -1,30 +1,16 @@
 """Static instruction mix of the main loop of a kernel in gfx950 ISA text (hipcc -S --cuda-device-only).
-usage: python tools/isa_loop_stats.py file.s <kernel-name-substring> [mfma-mnemonic-prefix]
-The loop is taken as the innermost backward branch that encloses every MFMA of the kernel."""
+usage: python tools/isa_loop_stats.py file.s <kernel-name-substring> [mfma-mnemonic-prefix] [--loops]
+The loop is taken as the innermost backward branch that encloses every MFMA of the kernel.
+--loops: a kernel with several tile loops (the chunk walk of decoder16.hip: a full-tile loop and a general one) — every
+innermost loop that holds MFMAs is listed by itself, in program order."""
 import collections
 import re
 import sys
 
 
-def main(path, name, mf_prefix="v_mfma"):
-    src = open(path).read().split("\n")
-    start = [i for i, l in enumerate(src) if re.match(r"^_Z\w*:", l) and name in l][0]
-    end = [i for i in range(start, len(src)) if src[i].strip().startswith("s_endpgm")][0]
-    body = src[start:end]
-    mf = [i for i, l in enumerate(body) if l.strip().startswith(mf_prefix)]
-    lab = {}
-    for i, l in enumerate(body):
-        m = re.match(r"^(\.LBB\d+_\d+):", l)
-        if m:
-            lab[m.group(1)] = i
-    cands = []
-    for i, l in enumerate(body):
-        m = re.match(r"\s*s_c?branch\w*\s+(\.LBB\d+_\d+)", l)
-        if m and m.group(1) in lab and lab[m.group(1)] < mf[0] and i > mf[-1]:
-            cands.append((lab[m.group(1)], i))
-    a, b = max(cands, key=lambda x: x[0])
+def mix(lines):
     cnt, ops = collections.Counter(), collections.Counter()
-    for l in body[a:b + 1]:
+    for l in lines:
         s = l.strip()
         if not s or s[0] in ";." or s.endswith(":"):
             continue
@@ -46,12 +32,39 @@ def main(path, name, mf_prefix="v_mfma"):
             cnt["s_nop"] += 1
         elif op.startswith("s_"):
             cnt["salu"] += 1
-    print(f"{name}: loop lines {a}..{b} of {len(body)}", dict(cnt))
-    print("  valu:", ops.most_common(24))
+    return cnt, ops
+
+
+def main(path, name, mf_prefix="v_mfma", every_loop=False):
+    src = open(path).read().split("\n")
+    start = [i for i, l in enumerate(src) if re.match(r"^_Z\w*:", l) and name in l][0]
+    end = [i for i in range(start, len(src)) if src[i].strip().startswith("s_endpgm")][0]
+    body = src[start:end]
+    mf = [i for i, l in enumerate(body) if l.strip().startswith(mf_prefix)]
+    lab = {}
+    for i, l in enumerate(body):
+        m = re.match(r"^(\.LBB\d+_\d+):", l)
+        if m:
+            lab[m.group(1)] = i
+    back = []                                     # (label line, branch line) of every backward branch
+    for i, l in enumerate(body):
+        m = re.match(r"\s*s_c?branch\w*\s+(\.LBB\d+_\d+)", l)
+        if m and m.group(1) in lab and lab[m.group(1)] < i:
+            back.append((lab[m.group(1)], i))
+    if every_loop:
+        holds = [(a, b) for a, b in back if any(a < x < b for x in mf)]
+        loops = [(a, b) for a, b in holds if not any((c, d) != (a, b) and a <= c and d <= b for c, d in holds)]
+    else:
+        loops = [max([(a, b) for a, b in back if a < mf[0] and b > mf[-1]], key=lambda x: x[0])]
+    for a, b in sorted(loops):
+        cnt, ops = mix(body[a:b + 1])
+        print(f"{name}: loop lines {a}..{b} of {len(body)}", dict(cnt))
+        print("  valu:", ops.most_common(24))
     for l in src[end:end + 120]:
         if any(k in l for k in ("NumVgprs", "ScratchSize", "Occupancy", "LDSByteSize")):
             print("  ", l.strip())
 
 
 if __name__ == "__main__":
-    main(sys.argv[1], sys.argv[2], *(sys.argv[3:4]))
+    args = [a for a in sys.argv[1:] if a != "--loops"]
+    main(args[0], args[1], *(args[2:3]), every_loop="--loops" in sys.argv)
