@@ -26,16 +26,22 @@
 // active in every MFMA / transposing LDS read, and only global stores are predicated.
 //
 // Two walks over a wave's tiles.  The ids / keys instances (padded batches with e_live, shards, the small build, lists
-// without a plan's stream) run ONE flat tile loop with that general body for every tile and derive the chunk bookkeeping
+// without a plan's stream) run ONE flat tile loop with the general body for every tile and derive the chunk bookkeeping
 // per tile (next_tile, selects on carry / pidx, the part offset).  The STREAM instances — every edge is real, so only the
 // list's last tile can hold a dead position — run the CHUNK WALK: loops over the wave's chunks with a counted loop over a
 // chunk's tiles inside, all indices 32-bit scalars, the part offset loaded once per chunk, carry / pidx reset at chunk entry.
 // Whole chunks of full tiles run a body instantiated with TAIL = false (no live / store limits, no clamps, in T no
 // close_mask); the wave's final chunk (S) or final two chunks (T), which hold the list's last tile and every prefetch that
-// could point past the list, run the same body function with TAIL = true, the general logic.  The stream bodies repeat the
-// ids / keys loops' arithmetic statement for statement (tests/test_chunk_walk.py holds them bit for bit equal); the ids /
-// keys loops themselves are kept as they were, because wrapped into a shared body function they compile to other
-// instructions (profiles/chunk_walk.md).
+// could point past the list, run the same body function with TAIL = true, the general logic.
+// T has ONE body for both walks (tile_body, 32 edges): the keys loop keeps its bookkeeping and calls it with TAIL = true;
+// the route changes only where the next ids come from (load_tpos or load_ids) and how a run end is recognised (the stream
+// word's close bit, or a key change / the chunk's last position), TAIL switches the padding logic.
+// S still has TWO textual copies of its half-tile arithmetic: half_tile (the STREAM instances' body) and, statement for
+// statement, the ids loop below it, tied by the [S1] … [S5] markers (tests/test_chunk_walk.py holds them bit for bit
+// equal).  Calling half_tile from the ids loop as well leaves the STREAM instances untouched and the ids instances on
+// the same instruction mix, but the four <F, RUNSUM = false, PQ16 = true, EXTRA = false> instances then run 1.6 to 3 %
+// slower at 75 M edges: their m1 packing leaves the shadow of P1's matrix instructions (profiles/decoder_one_body.md).
+// (profiles/chunk_walk.md.)
 //
 // INVARIANT — the relus are held DOUBLED.  relu2x(x) = x + |x| = 2 relu(x) is the one-instruction relu through which a NaN of
 // either sign stays a NaN (see relu2x), so in the S and inference kernels the registers `h` (h1_frags) and `acc` after p1_logit
@@ -1327,8 +1333,6 @@ __global__ __launch_bounds__(T_WAVES * 64) void decoder_dgrad16_kernel(
   char* wv = lds + T_WAVE0 + wave * TW_BYTES;
   stage_weights16(w2, nullptr, w3, nullptr, lds, T_WAVES * 64, 2, 0, T_VEC, 128.f);
   __syncthreads();
-  const int wfrag0 = c * 128 + ((g ^ wsw(c)) << 4), wfrag1 = wfrag0 ^ 64;
-  const int colp = 16 * (((g & 1) << 1) | (g >> 1)) + c;
   const char* recg = reinterpret_cast<const char*>(rec) + 4 * g;
   // positions >= e_live of the order are padding (the pads of a fixed-shape batch sort last): dL/dlogit = 0 there
   const int64_t e_live = e_live_p ? min(e_live_p[0], E) : E;
@@ -1354,6 +1358,90 @@ __global__ __launch_bounds__(T_WAVES * 64) void decoder_dgrad16_kernel(
   float carry = 0.f;
   int64_t pidx = 0;
 
+  const int nt = (int)n_tiles, e32 = (int)E;                           // the stream's tile and position counts (E < 2^31)
+  // One 32-edge tile: THE body of every instance, called by both walks below.  `cur` holds the tile's records, `ids_nxt` the
+  // words / ids of the wave's next tile, t2 is the tile after that, whose words / ids are requested here (the stream's words
+  // by load_tpos with a 32-bit tile number, perm / keys by load_ids with the keys loop's 64-bit one).  The route changes only
+  // that load and how a run end is recognised: the word's close bit, or a key change / `last_tile` (this tile ends its chunk;
+  // read by the keys route alone).  RUN = false (the parameter sums alone) skips P2 and the run sums.
+  // TAIL = true is the general body: positions past live_lim (the end of the list, or of a padded batch's real edges) enter
+  // no sum, and on the stream route the close bits of the list's last tile go through `cmask` (close_mask; the keys route
+  // does not read it) and the word loads are clamped to the list.  TAIL = false — the chunk walk's full tiles: all 32
+  // positions of this tile and of t2 are real — no live_lim, no close_mask, no clamp.
+  auto tile_body = [&](auto tail_c, auto t2, int live_lim, bool last_tile, uint32_t cmask) __attribute__((always_inline)) {
+    constexpr bool TAIL = decltype(tail_c)::value;
+    // the lane's constants here, not captured from the kernel's scope (see the S kernel's half_tile)
+    const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
+    const int wfrag0 = c * 128 + ((g ^ wsw(c)) << 4), wfrag1 = wfrag0 ^ 64;
+    const int colp = 16 * (((g & 1) << 1) | (g >> 1)) + c;
+    TIn nxt[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      nxt[h] = load_rec(recg, ids_nxt[h]);
+      if constexpr (STREAM) ids_nxt[h] = load_tpos<TAIL>(tpos, e32, t2, nt, h, c);
+      else ids_nxt[h] = load_ids<PERM, RUN, false>(perm, keys, tpos, E, t2, n_tiles, h, c);
+    }
+    bf16x8 a2[2][2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const float g_e = (!TAIL || 16 * h + c <= live_lim) ? cur[h].g_e : 0.f;
+      const uint32_t recw = cur[h].recw;
+      *reinterpret_cast<uint32_t*>(wv + TW_REC + 256 * h + 16 * c + 4 * g) = recw;
+      *reinterpret_cast<float*>(wv + TW_GL + 64 * h + 4 * c) = g_e;
+      // m2 bits of lane (c, g): pair n = 4 t + qd (elements 2 qd, 2 qd + 1 of K-step t) sits at bits 7 - n and 23 - n:
+      // (recw & (0x10001 << p)) * (0x3c00 >> p) = 0x3c00 / 0 in each half (p <= 7: the products stay inside their halves).
+      // 0x3c00 is T's mask value (T_MASK16): 2^-7 as the bf16 A operand of P2, whose B images are 128 W2' (stage_weights16,
+      // which = 2 with scale 128) — the products, hence P2's accumulators, are bit for bit those of 1.0 x W2' — and 1.0 as
+      // an IEEE half, which v_fma_mix_f32 takes as an operand of the dL/db2 sums below.
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        u32x4 w;
+        uint32_t yb[4];
+#pragma unroll
+        for (int qd = 0; qd < 4; ++qd) {
+          const int p = 7 - (4 * t + qd);
+          yb[qd] = recw & (0x00010001u << p);
+          asm volatile("" : "+v"(yb[qd]));      // opaque: keeps ONE and per pair (the optimiser otherwise re-derives byte 0
+          w[qd] = __umul24(yb[qd], T_MASK16 >> p);    //                                  from recw with a second and below)
+        }
+        a2[h][t] = __builtin_bit_cast(bf16x8, w);
+        if (gb2_slabs != nullptr) {
+          // dL/db2 partials: the mask halves of the operand words themselves, 1.0 / 0.0 as IEEE halves — one v_fma_mix_f32
+          // per element (half operand by op_sel; tools/valu_issue_rate.hip: issues like v_fma_f32, every lane right beside
+          // bf16 MFMAs, profiles/t_vector_stream.md).  (Until this form each element cost a v_cvt_f32_ubyte of its record
+          // bit + a v_fma_f32, the sums carrying a factor 2^p; round 3 rebuilt 1.0 / 0.0 from a bf16 1.0 operand: the
+          // optimiser folded that into a v_mul_lo_u32 per pair, a quarter-rate instruction, 16 per tile.)
+#pragma unroll
+          for (int qd = 0; qd < 4; ++qd) {
+            const int jb = 2 * t + (qd >> 1), i0 = 2 * (qd & 1);
+            const f16x2 m = __builtin_bit_cast(f16x2, (uint32_t)w[qd]);
+            gb2a[jb][i0] = fmaf((float)m[0], g_e, gb2a[jb][i0]);
+            gb2a[jb][i0 + 1] = fmaf((float)m[1], g_e, gb2a[jb][i0 + 1]);
+          }
+        }
+      }
+    }
+    wave_lds_sync();
+    if (RUN) {
+      f32x4 v[2][4];
+      dgrad_tile2(lds, a2, wfrag0, wfrag1, v);
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        f32x4 gm[4];
+        dgrad_masks(wv + TW_REC + 256 * h, wv + TW_GL + 64 * h, c, g, gm);
+        bool closes;
+        if constexpr (STREAM) closes = (int)cur[h].e < 0;                                     // the word's close bit
+        else closes = cur[h].key != cur[h].key_nxt || (h == 1 && c == 15 && last_tile);       // key change, or end of the chunk
+        const unsigned long long bal = __ballot(closes);
+        unsigned m16 = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(bal & 0xffffull));
+        if (STREAM && TAIL) m16 = (m16 & (cmask >> (16 * h))) & 0xffffu;          // scalar: wave-uniform operands
+        run_sums(v[h], gm, m16, carry, rs.part, pidx, wv, lane, c, g, colp);
+      }
+    }
+    wave_lds_sync();          // the next tile overwrites recl / gl
+#pragma unroll
+    for (int h = 0; h < 2; ++h) cur[h] = nxt[h];
+  };
   if constexpr (STREAM) {
     // ---- chunk walk (as in S): loops over the wave's chunks with a counted loop over a chunk's tiles inside, every index a
     // 32-bit scalar.  Per chunk: the part offset (the next chunk's is requested one chunk ahead), carry / pidx reset.  T prefetches
@@ -1361,77 +1449,11 @@ __global__ __launch_bounds__(T_WAVES * 64) void decoder_dgrad16_kernel(
     // tile itself and the one between are full too).  Every t2 of a chunk is at most nfirst + cstep, the first tile of the wave's
     // chunk after next: a chunk with first + 2 cstep < nt - 1 is a whole chunk of full tiles — the first loop.  The wave's last
     // two chunks take the general body — the second loop.  Two top-level loops for the reason given in S.
-    const int nt = (int)n_tiles, ct = 1 << clog, e32 = (int)E;
-    const int cstep = ((int)gridDim.x * T_WAVES) << clog;              // tiles from one chunk of the wave to its next
+    const int ct = 1 << clog;
+    const int cstep = ((int)gridDim.x * T_WAVES) << clog;             // tiles from one chunk of the wave to its next
     const int nch = (nt + ct - 1) >> clog;
     // the wave's tile behind t: the next one of its chunk, or the first of its next chunk
     auto next32 = [&](int t) { return (((t + 1) & (ct - 1)) == 0 || t + 1 >= nt) ? ((t >> clog) << clog) + cstep : t + 1; };
-    // One 32-edge tile, the arithmetic of the keys loop below statement for statement (its comments are there): `cur` holds the
-    // tile's records, `ids_nxt` the words of the wave's next tile, t2 is the tile after that, whose words are requested here.
-    // TAIL = true is the general body: positions past live_lim enter no sum, the close bits of the list's last tile go through
-    // `cmask` (close_mask), the word loads are clamped to the list.  TAIL = false: all 32 positions of this tile and of t2 are
-    // real — no live_lim, no close_mask, no clamp.
-    auto tile_body = [&](auto tail_c, int t2, int live_lim, uint32_t cmask) __attribute__((always_inline)) {
-      constexpr bool TAIL = decltype(tail_c)::value;
-      // the lane's constants again, not captured (see the S kernel's half_tile: the ids / keys instances stay what they were)
-      const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
-      const int wfrag0 = c * 128 + ((g ^ wsw(c)) << 4), wfrag1 = wfrag0 ^ 64;
-      const int colp = 16 * (((g & 1) << 1) | (g >> 1)) + c;
-      // [T1] records of the next tile, words / ids of the one after — the same statements stand in the keys loop below: edit both
-      TIn nxt[2];
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        nxt[h] = load_rec(recg, ids_nxt[h]);
-        ids_nxt[h] = load_tpos<TAIL>(tpos, e32, t2, nt, h, c);
-      }
-      // [T2] LDS records, m2 operands, dL/db2 partials — the same statements stand in the keys loop below: edit both
-      bf16x8 a2[2][2];
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const float g_e = (!TAIL || 16 * h + c <= live_lim) ? cur[h].g_e : 0.f;
-        const uint32_t recw = cur[h].recw;
-        *reinterpret_cast<uint32_t*>(wv + TW_REC + 256 * h + 16 * c + 4 * g) = recw;
-        *reinterpret_cast<float*>(wv + TW_GL + 64 * h + 4 * c) = g_e;
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-          u32x4 w;
-          uint32_t yb[4];
-#pragma unroll
-          for (int qd = 0; qd < 4; ++qd) {
-            const int p = 7 - (4 * t + qd);
-            yb[qd] = recw & (0x00010001u << p);
-            asm volatile("" : "+v"(yb[qd]));
-            w[qd] = __umul24(yb[qd], T_MASK16 >> p);
-          }
-          a2[h][t] = __builtin_bit_cast(bf16x8, w);
-          if (gb2_slabs != nullptr) {
-#pragma unroll
-            for (int qd = 0; qd < 4; ++qd) {
-              const int jb = 2 * t + (qd >> 1), i0 = 2 * (qd & 1);
-              const f16x2 m = __builtin_bit_cast(f16x2, (uint32_t)w[qd]);
-              gb2a[jb][i0] = fmaf((float)m[0], g_e, gb2a[jb][i0]);
-              gb2a[jb][i0 + 1] = fmaf((float)m[1], g_e, gb2a[jb][i0 + 1]);
-            }
-          }
-        }
-      }
-      wave_lds_sync();
-      // [T3] P2 and run sums — the same statements stand in the keys loop below: edit both
-      f32x4 v[2][4];
-      dgrad_tile2(lds, a2, wfrag0, wfrag1, v);
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        f32x4 gm[4];
-        dgrad_masks(wv + TW_REC + 256 * h, wv + TW_GL + 64 * h, c, g, gm);
-        const unsigned long long bal = __ballot((int)cur[h].e < 0);                           // the word's close bit
-        unsigned m16 = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(bal & 0xffffull));
-        if (TAIL) m16 = (m16 & (cmask >> (16 * h))) & 0xffffu;          // scalar: wave-uniform operands
-        run_sums(v[h], gm, m16, carry, rs.part, pidx, wv, lane, c, g, colp);
-      }
-      wave_lds_sync();          // the next tile overwrites recl / gl
-#pragma unroll
-      for (int h = 0; h < 2; ++h) cur[h] = nxt[h];
-    };
     int first = (int)tile, t1 = (int)tile1, poff = poff_cur;
     // whole chunks of full tiles
     while (first + 2 * cstep < nt - 1) {
@@ -1443,7 +1465,7 @@ __global__ __launch_bounds__(T_WAVES * 64) void decoder_dgrad16_kernel(
 #pragma unroll 1
       do {
         const int t2 = next32(t1);
-        tile_body(std::false_type{}, t2, 31, 0u);
+        tile_body(std::false_type{}, t2, 31, false, 0u);
         t1 = t2;
       } while (++t < end);
       poff = poff_nxt;
@@ -1459,7 +1481,7 @@ __global__ __launch_bounds__(T_WAVES * 64) void decoder_dgrad16_kernel(
 #pragma unroll 1
       do {
         const int t2 = next32(t1 < nt ? t1 : nt - 1);
-        tile_body(std::true_type{}, t2, min(31, e32 - 1 - t * 32), close_mask(e32, t));
+        tile_body(std::true_type{}, t2, min(31, e32 - 1 - t * 32), false, close_mask(e32, t));
         t1 = t2;
       } while (++t < end);
       poff = poff_nxt;
@@ -1476,72 +1498,7 @@ __global__ __launch_bounds__(T_WAVES * 64) void decoder_dgrad16_kernel(
       const int live_lim = (int)min((int64_t)31, e_live - 1 - tile * 32);
       bool last2;
       const int64_t tile2 = next_tile(tile1 < n_tiles ? tile1 : n_tiles - 1, cstride, n_tiles, last2, clog);
-      // [T1] records of the next tile, words / ids of the one after — the same statements stand in tile_body (the STREAM instance's body) above: edit both
-      TIn nxt[2];
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        nxt[h] = load_rec(recg, ids_nxt[h]);
-        ids_nxt[h] = load_ids<PERM, RUN, false>(perm, keys, tpos, E, tile2, n_tiles, h, c);
-      }
-      // [T2] LDS records, m2 operands, dL/db2 partials — the same statements stand in tile_body (the STREAM instance's body) above: edit both
-      bf16x8 a2[2][2];
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const float g_e = 16 * h + c <= live_lim ? cur[h].g_e : 0.f;
-        const uint32_t recw = cur[h].recw;
-        *reinterpret_cast<uint32_t*>(wv + TW_REC + 256 * h + 16 * c + 4 * g) = recw;
-        *reinterpret_cast<float*>(wv + TW_GL + 64 * h + 4 * c) = g_e;
-        // m2 bits of lane (c, g): pair n = 4 t + qd (elements 2 qd, 2 qd + 1 of K-step t) sits at bits 7 - n and 23 - n:
-        // (recw & (0x10001 << p)) * (0x3c00 >> p) = 0x3c00 / 0 in each half (p <= 7: the products stay inside their halves).
-        // 0x3c00 is T's mask value (T_MASK16): 2^-7 as the bf16 A operand of P2, whose B images are 128 W2' (stage_weights16,
-        // which = 2 with scale 128) — the products, hence P2's accumulators, are bit for bit those of 1.0 x W2' — and 1.0 as
-        // an IEEE half, which v_fma_mix_f32 takes as an operand of the dL/db2 sums below.
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-          u32x4 w;
-          uint32_t yb[4];
-#pragma unroll
-          for (int qd = 0; qd < 4; ++qd) {
-            const int p = 7 - (4 * t + qd);
-            yb[qd] = recw & (0x00010001u << p);
-            asm volatile("" : "+v"(yb[qd]));      // opaque: keeps ONE and per pair (the optimiser otherwise re-derives byte 0
-            w[qd] = __umul24(yb[qd], T_MASK16 >> p);    //                                  from recw with a second and below)
-          }
-          a2[h][t] = __builtin_bit_cast(bf16x8, w);
-          if (gb2_slabs != nullptr) {
-            // dL/db2 partials: the mask halves of the operand words themselves, 1.0 / 0.0 as IEEE halves — one v_fma_mix_f32
-            // per element (half operand by op_sel; tools/valu_issue_rate.hip: issues like v_fma_f32, every lane right beside
-            // bf16 MFMAs, profiles/t_vector_stream.md).  (Until this form each element cost a v_cvt_f32_ubyte of its record
-            // bit + a v_fma_f32, the sums carrying a factor 2^p; round 3 rebuilt 1.0 / 0.0 from a bf16 1.0 operand: the
-            // optimiser folded that into a v_mul_lo_u32 per pair, a quarter-rate instruction, 16 per tile.)
-#pragma unroll
-            for (int qd = 0; qd < 4; ++qd) {
-              const int jb = 2 * t + (qd >> 1), i0 = 2 * (qd & 1);
-              const f16x2 m = __builtin_bit_cast(f16x2, (uint32_t)w[qd]);
-              gb2a[jb][i0] = fmaf((float)m[0], g_e, gb2a[jb][i0]);
-              gb2a[jb][i0 + 1] = fmaf((float)m[1], g_e, gb2a[jb][i0 + 1]);
-            }
-          }
-        }
-      }
-      wave_lds_sync();
-      if (RUN) {
-        // [T3] P2 and run sums — the same statements stand in tile_body (the STREAM instance's body) above: edit both
-        f32x4 v[2][4];
-        dgrad_tile2(lds, a2, wfrag0, wfrag1, v);
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          f32x4 gm[4];
-          dgrad_masks(wv + TW_REC + 256 * h, wv + TW_GL + 64 * h, c, g, gm);
-          const bool closes = cur[h].key != cur[h].key_nxt || (h == 1 && c == 15 && last_tile);   // key change, or end of the chunk
-          const unsigned long long bal = __ballot(closes);
-          const unsigned m16 = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(bal & 0xffffull));
-          run_sums(v[h], gm, m16, carry, rs.part, pidx, wv, lane, c, g, colp);
-        }
-      }
-      wave_lds_sync();          // the next tile overwrites recl / gl
-#pragma unroll
-      for (int h = 0; h < 2; ++h) cur[h] = nxt[h];
+      tile_body(std::true_type{}, tile2, live_lim, last_tile, 0u);      // the general body for every tile (cmask: not read)
       poff_cur = last_tile ? poff_nxt : poff_cur;
       tile = tile1;
       tile1 = tile2;

@@ -4,7 +4,9 @@ instances of the same library on the same inputs — bit for bit.
 The STREAM instances walk a wave's chunks in two loops: whole chunks of full tiles run a body without any tail or padding
 logic (no live / store limits, no clamps, T without close_mask), the wave's final chunk (S) or final two chunks (T) run the
 general body, which also handles the list's last tile and every prefetch that would point past the list.  The ids / keys
-instances are the code they were (one flat tile loop, the general body everywhere), so they are the reference: logits and the
+instances run one flat tile loop with the general body for every tile, their own per-tile bookkeeping and their own run-end
+test — in T by calling the same body function as the walk, in S through a second textual copy of the half tile's statements —
+and tests/test_decoder_run_sums.py pins them against a host reference, so they are the reference for the walk: logits and the
 fused loss, the record table, the S and T part rows slot for slot (guard rows untouched), the per-workgroup slabs and every
 parameter gradient reduced from them, and dL/db2 must be equal.
 
