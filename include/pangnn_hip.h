@@ -520,6 +520,41 @@ int    pangnn_confusion_update_f32(const float* scores, const float* labels, int
                                    int apply_sigmoid, int64_t* counts, pangnn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Everything an epoch keeps of ONE batch's logits, folded into device state by one capturable call: no host read-back, no
+ * allocation, no synchronisation, no float atomics — the same input gives the same bits in every run.
+ * (pangnn.py:218-222: running training loss + training confusion matrix; pangnn.py:241-289: the validation loop.)
+ *
+ *   m = live[0], the number of real entries of a padded batch (device int64; NULL: n_max; a value outside [0, n_max]: n_max).
+ *   Only logits[0:m] / labels[0:m] are read.  m == 0 adds nothing and the batch is not counted.
+ *
+ * state: PANGNN_BATCH_STATS_WORDS int64 words, 8-byte aligned, zeroed by the caller, only ever added to here:
+ *   [0..3] counts[2*label + prediction], label = labels[i] > 0.5, prediction = sigmoid(logits[i]) >= threshold[0] — the
+ *          predicate of pangnn_confusion_update_f32 (one device function serves both);
+ *   [4]    batches   += 1
+ *   [5]    cursor    += m  when the batch was appended (below)
+ *   [6]    overflow   = 1  when it could not be
+ *   [7]    loss_sum (double) += L,  L = loss_in[0] when loss_in is given, else the mean over the m real entries of the per-entry
+ *          term of pangnn_bce_logits_f32 (fp32 terms, one device function serves both), summed in float64 in a fixed order;
+ *   [8]    low 4 bytes: last_loss (float) = L
+ *   the remaining words are the caller's (pangnn_amd keeps the threshold there).
+ * threshold: device float, read by the kernel (it can change between replays of a captured graph).  pos_weight: device float or
+ * NULL (1).  loss_in: device float or NULL.
+ * Ranking data (cap > 0): scores float[cap] / score_labels uint8[cap] receive logits[0:m] as stored (no sigmoid: an exact
+ * copy) and labels[0:m] > 0.5 at positions cursor .. cursor + m; if they do not fit, nothing is appended and overflow is set
+ * (counts and loss are still taken).  cap == 0: no ranking data, the two buffers are not touched.
+ * n_max up to the small-structure limit (16384): one workgroup; above: per-workgroup partials in `workspace`
+ * (pangnn_batch_stats_workspace_bytes(n_max) bytes, 8-byte aligned, 0 below the limit) + a one-workgroup finish kernel.
+ * Null logits / labels / state / threshold, n_max < 0, cap < 0 or cap > 0 without both buffers: PANGNN_E_BADARG; n_max >= 2^40:
+ * PANGNN_E_TOOLARGE; a workspace that is NULL or too small where one is needed: PANGNN_E_WORKSPACE.
+ * ---------------------------------------------------------------------------------------- */
+#define PANGNN_BATCH_STATS_WORDS 16
+int64_t pangnn_batch_stats_workspace_bytes(int64_t n_max);
+int    pangnn_batch_stats_f32(const float* logits, const float* labels, int64_t n_max, const int64_t* live,
+                              const float* pos_weight, const float* threshold, const float* loss_in, int64_t* state,
+                              float* scores, uint8_t* score_labels, int64_t cap, void* workspace, int64_t workspace_bytes,
+                              pangnn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * out[0, c] = sum_n r[n] g[n, c], out[1, c] = sum_n s[n] g[n, c]  (out [2, F], F divides 256).
  * Backward of the scalar-feature embedding feeding the first GCN layer (src/gnn.py:97,125,158): the layer's
  * input is h0 = x w^T + 1 b^T, so dL/dw = (A_hat x)^T g and dL/db = (A_hat 1)^T g with g = dL/d(A_hat h0);

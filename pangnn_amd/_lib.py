@@ -67,6 +67,9 @@ SIGNATURES = {
     "pangnn_linear_act_backward_parts_f32": (C.c_int, [_p, _p, _i64, _p, _p, _i64, _p, _i64, _p, _i64, _i32, _i32, _i32, _p, _i64,
                                                        _p, _p, _p, _i64, _p]),
     "pangnn_confusion_update_f32": (C.c_int, [_p, _p, _i64, C.c_float, C.c_int, _p, _p]),
+    # (logits, labels, n_max, live, pos_weight, threshold, loss_in, state, scores, score_labels, cap, workspace, bytes, stream)
+    "pangnn_batch_stats_workspace_bytes": (_i64, [_i64]),
+    "pangnn_batch_stats_f32": (C.c_int, [_p, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _i64, _p, _i64, _p]),
     "pangnn_weighted_colsum_workspace_bytes": (_sz, [_i32]),
     "pangnn_weighted_colsum_f32": (C.c_int, [_p, _i64, _p, _p, _i64, _i32, _p, _p, _sz, _p]),
     "pangnn_band_propagate_workspace_bytes": (_sz, [_i32]),

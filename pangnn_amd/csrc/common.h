@@ -65,7 +65,25 @@ inline bool rows_aligned(const void* p, int32_t dtype, int64_t ld) {
 // Launch with kSumThreads threads and (len + 63) / 64 blocks; the result is valid in wave 0 (threadIdx.x < 64).
 constexpr int kSumGroups = 16;
 constexpr int kSumThreads = kSumGroups * kWave;
+// the longest edge list of the small-structure path (graph_build.hip): what one workgroup takes whole, a collated mini-batch
+constexpr int kSmallMaxEdges = 16384;
 #ifdef __HIPCC__
+// ---- the two per-edge expressions of the loss and the confusion counts, stated once for every kernel that evaluates them
+// (edge_ops.hip: bce_kernel, confusion_kernel; batch_stats.hip)
+// prediction = (score >= threshold), score = sigmoid(x) or x itself (pangnn.py:219-221); label = (y > 0.5)
+__device__ __forceinline__ bool predicted_positive(float x, float threshold, bool apply_sigmoid) {
+  const float score = apply_sigmoid ? 1.0f / (1.0f + expf(-x)) : x;
+  return score >= threshold;
+}
+__device__ __forceinline__ bool label_positive(float y) { return y > 0.5f; }
+// BCEWithLogits(pos_weight) of one edge: (1-y) x + (1 + (pw-1) y) softplus(-x), softplus(-x) = log1p(exp(-|x|)) + max(-x, 0)
+__device__ __forceinline__ float bce_term(float x, float y, float pw) {
+  const float lw = 1.f + (pw - 1.f) * y;
+  const float t = expf(-fabsf(x));
+  const float sp = log1pf(t) + fmaxf(-x, 0.f);
+  return (1.f - y) * x + lw * sp;
+}
+
 // ---- 2-byte row formats (storage only; every sum and product is fp32).  A kernel templated on its storage type uses
 // `unsigned short` for bfloat16 bits (bf16 -> f32 is a shift) and `_Float16` for IEEE half (`--mixed_precision fp16`,
 // src/setup.py:50; v_cvt_f32_f16 / v_cvt_f16_f32); RowFmt<T>::value is the PANGNN_DTYPE_* code of T.

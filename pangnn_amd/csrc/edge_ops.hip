@@ -173,8 +173,7 @@ __global__ __launch_bounds__(kBlock) void bce_kernel(const float* __restrict__ x
     const float lw = 1.f + (pw - 1.f) * yv;
     const float ax = fabsf(xv);
     const float t = expf(-ax);
-    const float sp = log1pf(t) + fmaxf(-xv, 0.f);            // softplus(-x)
-    acc += (1.f - yv) * xv + lw * sp;
+    acc += bce_term(xv, yv, pw);                             // (its exp(-|x|) and label weight are t and lw below)
     // dl/dx through the SMALL sigmoid s = sigmoid(-|x|) on both sides: (1-y) - lw s for x >= 0, lw s - pw y for x < 0 (the same
     // value, lw - 1 + y = pw y).  Written as (1-y) - lw / (1 + t), the negative side loses s below 2^-24 (x < -16.6, where
     // 1 + t == 1): a label-0 edge then gets the gradient 0 instead of sigmoid(x).
@@ -208,9 +207,7 @@ __global__ __launch_bounds__(kBlock) void confusion_kernel(const float* __restri
   __shared__ unsigned int red[kBlock / kWave][4];
   unsigned int c[4] = {0u, 0u, 0u, 0u};
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
-    const float xv = x[i];
-    const float score = apply_sigmoid ? 1.0f / (1.0f + expf(-xv)) : xv;
-    const int pred = score >= threshold ? 1 : 0, lab = y[i] > 0.5f ? 1 : 0;
+    const int pred = predicted_positive(x[i], threshold, apply_sigmoid != 0) ? 1 : 0, lab = label_positive(y[i]) ? 1 : 0;
     c[2 * lab + pred] += 1u;
   }
 #pragma unroll

@@ -156,7 +156,6 @@ extern "C" const void* pangnn_csr_build_flag_ptr(void* workspace, int64_t num_ed
 // ==============================================================================================================
 namespace pangnn {
 
-constexpr int kSmallMaxEdges = 16384;
 constexpr int kSmallMaxNodes = 65536;
 constexpr int kSmallThreads = 1024;
 

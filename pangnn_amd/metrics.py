@@ -189,3 +189,154 @@ def youden_threshold(scores, target) -> torch.Tensor:
     m = BinaryAUROC()
     m.update(scores, target)
     return m.optimal_threshold()
+
+
+class EpochStats:
+    """What an epoch keeps of its batches' logits, as device state that ONE capturable launch per batch adds to
+    (`pangnn_batch_stats_f32`, csrc/batch_stats.hip): the confusion counts at a device-resident threshold, the sum of the
+    batches' mean BCEWithLogits(pos_weight) losses and their number, and — `capacity > 0` — the raw logits and labels of every
+    real edge, from which ROC-AUC, PR-AUC and the Youden threshold are computed once at the end (pangnn.py:218-222: the
+    running training loss and confusion matrix; pangnn.py:241-289: the validation loop).  The batch may be a padded
+    fixed-shape one (`live`: the device count of its real edges), and `update` reads nothing back, so it can end the
+    captured step of `train.ReplayedFreshStep` / `train.ReplayedFreshEval`.
+
+    State: `state`, int64[16] — counts[4] (index 2*label + prediction), batches, cursor, overflow, loss_sum (float64),
+    last_loss (float32) and the threshold (float32), all in one allocation with the kernel's partials behind them — plus the
+    two ranking buffers `scores` float32[capacity] / `labels` uint8[capacity].  Logits are stored, not probabilities: the
+    appended data is an exact copy of what the model returned, and the sigmoid is applied once in `compute()`.
+    A batch without a real edge adds nothing and is not counted (torch's mean over no element is NaN).  A batch that does not
+    fit the ranking buffers is not appended and sets `overflow` (its counts and loss are still taken): `compute()` raises.
+
+    CPU tensors run the same definition in plain torch (prediction `torch.sigmoid(x) >= threshold`, loss the float64
+    `binary_cross_entropy_with_logits` of the real entries)."""
+
+    WORDS = 16                 # PANGNN_BATCH_STATS_WORDS
+    _ZEROED = 9                # words reset() clears: everything but the threshold
+
+    def __init__(self, capacity: int = 0, threshold: float = 0.5, device=None):
+        dev = torch.device("cuda" if device is None else device)
+        if dev.type == "cuda" and dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        self.capacity = int(capacity)
+        if self.capacity < 0:
+            raise ValueError("capacity must be >= 0")
+        self._ws_bytes = int(_lib.load().pangnn_batch_stats_workspace_bytes(1 << 30)) if dev.type == "cuda" else 0
+        whole = torch.zeros(self.WORDS + self._ws_bytes // 8, dtype=torch.int64, device=dev)
+        self.state, self._workspace = whole[:self.WORDS], whole[self.WORDS:]
+        self.counts = self.state[:4]
+        f32 = self.state[8:10].view(torch.float32)
+        self._loss_sum, self._last_loss, self._threshold = self.state[7:8].view(torch.float64), f32[0:1], f32[2:3]
+        self.scores = torch.zeros(self.capacity, dtype=torch.float32, device=dev)
+        self.labels = torch.zeros(self.capacity, dtype=torch.uint8, device=dev)
+        self.set_threshold(threshold)
+
+    # 0-d views of the state: reading one of them on the host is a synchronisation
+    batches = property(lambda self: self.state[4])
+    cursor = property(lambda self: self.state[5])
+    overflow = property(lambda self: self.state[6])
+    loss_sum = property(lambda self: self._loss_sum[0])
+    last_loss = property(lambda self: self._last_loss[0])
+    device = property(lambda self: self.state.device)
+
+    def set_threshold(self, t: float):
+        """writes the device scalar the next update reads (pangnn.py's --dynamic_binary_threshold): one fill on the current
+        stream, no re-capture"""
+        self.threshold = float(t)
+        self._threshold.fill_(self.threshold)
+
+    def reset(self):
+        self.state[:self._ZEROED].zero_()
+
+    def _scalar(self, v, dtype):
+        """a 1-element tensor of `dtype` on the state's device, or None"""
+        if v is None:
+            return None
+        if not torch.is_tensor(v):
+            return torch.tensor([v], dtype=dtype, device=self.device)
+        v = v.detach().reshape(-1)[:1]
+        return v if (v.dtype == dtype and v.device == self.device) else v.to(device=self.device, dtype=dtype)
+
+    def update(self, logits, labels, live=None, pos_weight=None, loss=None):
+        """fold one batch in: `logits` / `labels` [n_max], of which the first `live[0]` are real (a device int64 tensor, as a
+        padded batch carries it; None: all).  `pos_weight`: the loss's positive weight; `loss`: the batch's loss where the
+        caller already has it (then none is computed).  One launch on the current stream; nothing is read back."""
+        x, y = logits.detach().reshape(-1), labels.detach().reshape(-1)
+        if x.shape != y.shape:
+            raise ValueError(f"{x.shape[0]} logits for {y.shape[0]} labels")
+        if x.device != self.device or y.device != self.device:
+            raise ValueError(f"EpochStats on {self.device} got a batch on {x.device}")
+        x, y = x.to(torch.float32).contiguous(), y.to(torch.float32).contiguous()
+        live, pw, loss = self._scalar(live, torch.int64), self._scalar(pos_weight, torch.float32), self._scalar(loss, torch.float32)
+        if not x.is_cuda:
+            return self._update_host(x, y, live, pw, loss)
+        with _lib.device_guard(x.device):
+            _lib.check(_lib.load().pangnn_batch_stats_f32(
+                x.data_ptr(), y.data_ptr(), x.shape[0], _lib.ptr(live), _lib.ptr(pw), self._threshold.data_ptr(), _lib.ptr(loss),
+                self.state.data_ptr(), _lib.ptr(self.scores) if self.capacity else None,
+                _lib.ptr(self.labels) if self.capacity else None, self.capacity, self._workspace.data_ptr(), self._ws_bytes,
+                _lib.stream_ptr()), "pangnn_batch_stats_f32")
+
+    def _update_host(self, x, y, live, pw, loss):
+        n = x.shape[0]
+        m = n if live is None else int(live[0])
+        m = n if (m < 0 or m > n) else m
+        if m == 0:
+            return
+        xs, lab = x[:m], y[:m] > 0.5
+        pred = torch.sigmoid(xs) >= self._threshold
+        self.counts += torch.bincount(2 * lab.to(torch.int64) + pred.to(torch.int64), minlength=4)
+        if loss is None:
+            one = torch.nn.functional.binary_cross_entropy_with_logits(
+                xs.double(), y[:m].double(), pos_weight=None if pw is None else pw.double())
+        else:
+            one = loss[0].double()
+        self._loss_sum += one
+        self._last_loss.copy_(one.float() if loss is None else loss[:1])
+        self.state[4] += 1
+        if self.capacity:
+            c = int(self.state[5])
+            if 0 <= c and c + m <= self.capacity:
+                self.scores[c:c + m] = xs
+                self.labels[c:c + m] = lab.to(torch.uint8)
+                self.state[5] = c + m
+            else:
+                self.state[6] = 1
+
+    def confusion(self) -> torch.Tensor:
+        """[[tn, fp], [fn, tp]] int64, as BinaryConfusionMatrix.compute"""
+        return self.counts.view(2, 2).clone()
+
+    def _ranking(self, cursor: int):
+        """(BinaryAUROC, BinaryAveragePrecision) fed ONCE with the collected probabilities: one sort serves both"""
+        auroc = BinaryAUROC()
+        ap = BinaryAveragePrecision(share_curve_with=auroc)
+        prob, lab = torch.sigmoid(self.scores[:cursor]), self.labels[:cursor]
+        auroc.update(prob, lab)
+        ap.update(prob, lab)
+        return auroc, ap
+
+    def compute(self) -> dict:
+        """the keys of `train.evaluate`: the confusion summary, `loss` = loss_sum / batches and — with ranking data —
+        `roc_auc` / `pr_auc`.  The only host read-out."""
+        import struct
+        st = self.state.tolist()
+        if st[6]:
+            raise RuntimeError(f"EpochStats: a batch did not fit the {self.capacity} ranking entries (overflow); size the "
+                               f"capacity to the pass and reset()")
+        if st[4] == 0:
+            raise ValueError("EpochStats.compute() needs at least one counted batch")
+        res = summary_from_confusion(torch.tensor(st[:4], dtype=torch.int64))
+        res["loss"] = struct.unpack("<d", struct.pack("<q", st[7]))[0] / st[4]
+        if self.capacity:
+            auroc, ap = self._ranking(st[5])
+            res.update(roc_auc=float(auroc.compute()), pr_auc=float(ap.compute()))
+        return res
+
+    def optimal_threshold(self) -> torch.Tensor:
+        """Youden threshold of the collected scores (`youden_threshold` of their probabilities): what
+        --dynamic_binary_threshold feeds back into `set_threshold`"""
+        if not self.capacity:
+            raise ValueError("EpochStats(capacity=0) keeps no scores")
+        if int(self.state[6]):
+            raise RuntimeError("EpochStats: overflow")
+        return self._ranking(int(self.state[5]))[0].optimal_threshold()

@@ -123,7 +123,76 @@ class GraphedTrainStep:
         return self.loss, self.logits
 
 
-class ReplayedFreshStep:
+class _PaddedReplay:
+    """What train.ReplayedFreshStep and train.ReplayedFreshEval share: fixed-shape buffers sized by `SubGraphDataset.padded_spec`
+    (everyday ones of `slack` x the mean batch, worst-case ones built on first use), the step `self._step(buf)` captured into
+    one HIP graph per set of buffers, and the choice of the set a batch fits.  A subclass states `_step(buf)` (one padded
+    step, no host read-back; returns a tuple of tensors) and `_kept()`: the tensors a step changes that building a slot must
+    leave as they were (the warm-up steps before capture run for real)."""
+
+    def _init_slots(self, ds, batch_size, graphs, capture, warmup, slack):
+        self.ds, self.capture, self.warmup = ds, bool(capture), int(warmup)
+        self._first = list(range(min(batch_size, ds.num_graphs))) if graphs is None else [int(i) for i in list(graphs)[:batch_size]]
+        worst = ds.padded_spec(batch_size, graphs)
+        tight = worst if slack is None else ds.padded_spec(batch_size, graphs, slack)
+        self.spec, self.spec_worst = tight, worst
+        self._slots = {}                                   # spec -> (buffers, captured graph | None, the step's outputs | None)
+        self._slot(tight)
+
+    def _kept(self):
+        return []
+
+    def _restore(self, saved):
+        with torch.no_grad():
+            for t, v in zip(self._kept(), saved):
+                t.copy_(v)
+
+    def _slot(self, spec):
+        """the buffers (and, with capture, the captured graph) of the padded shapes `spec`, built on first use"""
+        hit = self._slots.get(spec)
+        if hit is not None:
+            return hit
+        ds = self.ds
+        buf = ds.padded_buffers(spec)
+        first = [i for i in self._first]
+        while len(first) > 1 and not ds.fits(spec, first):
+            first.pop()
+        ds.set_graph_ids(buf, first)
+        if not self.capture:
+            self._slots[spec] = (buf, None, None)
+            return self._slots[spec]
+        # the warm-up steps run on a side stream and are real steps on `first`: what they change is restored afterwards
+        # (values copied back into the very tensors the captured graph updates), so that building a slot is not a step
+        saved = self._save()
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            for _ in range(max(self.warmup, 1)):
+                self._step(buf)
+        torch.cuda.current_stream().wait_stream(s)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            outs = self._step(buf)
+        torch.cuda.synchronize()
+        self._restore(saved)
+        self._slots[spec] = (buf, graph, outs)
+        return self._slots[spec]
+
+    def _save(self):
+        return [t.detach().clone() for t in self._kept()]
+
+    def _run(self, graph_ids):
+        """(the step's outputs on the disjoint union of the sub-graphs `graph_ids`, its number of real edges)"""
+        spec = self.spec if self.ds.fits(self.spec, graph_ids) else self.spec_worst
+        buf, graph, outs = self._slot(spec)
+        edges = self.ds.set_graph_ids(buf, graph_ids)[1]
+        if graph is not None:
+            graph.replay()
+            return outs, edges
+        return self._step(buf), edges
+
+
+class ReplayedFreshStep(_PaddedReplay):
     """The reference's real regime — `DataLoader(batch_size=32, shuffle=True)`: every step sees a NEW batch
     (pangnn.py:152-153,180-216) — as ONE captured HIP graph that serves every mini-batch of a `SubGraphDataset`.
 
@@ -140,10 +209,12 @@ class ReplayedFreshStep:
     the kernel arguments) and one graph launch.  `capture=False` runs the very same padded step eagerly (the reference
     point of the bit-equality test).  Results equal the unpadded fresh step (`train_step` on `ds.batch(...)`) up to fp32
     re-association: padded rows are zero rows of every sum, but the per-workgroup partial sums of the node-level kernels are
-    grouped by the padded row count."""
+    grouped by the padded row count.
+    `stats`: a `metrics.EpochStats` (typically `capacity=0`) that the captured step ends with — the running training loss and
+    the training confusion matrix of pangnn.py:218-222 with no host work per step; None: nothing changes."""
 
     def __init__(self, model, optimizer, ds, pos_weight, batch_size: int = 32, graphs=None, capture: bool = True,
-                 warmup: int = 2, slack: float = 1.4):
+                 warmup: int = 2, slack: float = 1.4, stats=None):
         """`slack`: the everyday buffers hold `slack` x the mean batch (SubGraphDataset.padded_spec); a batch that exceeds them
         runs through a second, worst-case set of buffers (and its own captured graph), built on first use.  None: worst-case
         buffers only."""
@@ -153,49 +224,21 @@ class ReplayedFreshStep:
                     raise ValueError("ReplayedFreshStep(capture=True) needs torch.optim.Adam(..., capturable=True)")
         if not hasattr(model, "loss_and_logits"):
             raise ValueError("ReplayedFreshStep needs a model with the fused loss_and_logits path")
-        self.model, self.optimizer, self.ds, self.pos_weight = model, optimizer, ds, pos_weight
-        self.capture, self.warmup = bool(capture), int(warmup)
-        self._first = list(range(min(batch_size, ds.num_graphs))) if graphs is None else [int(i) for i in list(graphs)[:batch_size]]
-        worst = ds.padded_spec(batch_size, graphs)
-        tight = worst if slack is None else ds.padded_spec(batch_size, graphs, slack)
-        self.spec, self.spec_worst = tight, worst
-        self._slots = {}                                   # spec -> (buffers, captured graph | None, loss, logits)
-        self._slot(tight)
+        self.model, self.optimizer, self.pos_weight, self.stats = model, optimizer, pos_weight, stats
+        self._init_slots(ds, batch_size, graphs, capture, warmup, slack)
 
-    def _slot(self, spec):
-        """the buffers (and, with capture, the captured graph) of the padded shapes `spec`, built on first use"""
-        hit = self._slots.get(spec)
-        if hit is not None:
-            return hit
-        ds, model, optimizer = self.ds, self.model, self.optimizer
-        buf = ds.padded_buffers(spec)
-        first = [i for i in self._first]
-        while len(first) > 1 and not ds.fits(spec, first):
-            first.pop()
-        ds.set_graph_ids(buf, first)
-        if not self.capture:
-            self._slots[spec] = (buf, None, None, None)
-            return self._slots[spec]
-        # the warm-up steps run on a side stream and train on `first`: parameters and optimizer state are restored
-        # afterwards (values copied back into the very tensors the captured graph updates), so that building a slot is
-        # not a training step
+    def _kept(self):
+        return list(self.model.parameters()) + ([] if self.stats is None else [self.stats.state])
+
+    def _save(self):
         import copy
-        saved_p = [p.detach().clone() for p in model.parameters()]
-        opt_state = copy.deepcopy(optimizer.state_dict())
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for _ in range(max(self.warmup, 1)):
-                self._step(buf)
-        torch.cuda.current_stream().wait_stream(s)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            loss, logits = self._step(buf)
-        torch.cuda.synchronize()
+        return super()._save(), copy.deepcopy(self.optimizer.state_dict())
+
+    def _restore(self, saved):
+        tensors, opt_state = saved
+        super()._restore(tensors)
         with torch.no_grad():
-            for p, q in zip(model.parameters(), saved_p):
-                p.copy_(q)
-            new_state = optimizer.state_dict()["state"]
+            new_state = self.optimizer.state_dict()["state"]
             for k, st_ in new_state.items():
                 old = opt_state["state"].get(k)
                 for name, v in st_.items():
@@ -204,8 +247,6 @@ class ReplayedFreshStep:
                             v.copy_(old[name])
                         else:
                             v.zero_()                      # a fresh optimizer: forget what the warm-up accumulated
-        self._slots[spec] = (buf, graph, loss, logits)
-        return self._slots[spec]
 
     def _step(self, buf):
         """one padded fresh step: everything a new batch needs, no host read-back"""
@@ -214,17 +255,98 @@ class ReplayedFreshStep:
         loss, out = self.model.loss_and_logits(buf, buf.y, self.pos_weight)
         loss.backward(PF.unit_grad(loss.device))
         self.optimizer.step()
-        return loss.detach(), out.detach()
+        loss, out = loss.detach(), out.detach()
+        if self.stats is not None:
+            self.stats.update(out, buf.y, live=buf.live_edges, loss=loss)
+        return loss, out
 
     def __call__(self, graph_ids):
         """train on the disjoint union of the sub-graphs `graph_ids` (host ints, any order, at most batch_size);
         returns (loss, logits of the batch's real edges) as device tensors without synchronising.  With capture the two
         are VIEWS of the captured graph's static outputs: the next call overwrites them — clone what must outlive it."""
-        spec = self.spec if self.ds.fits(self.spec, graph_ids) else self.spec_worst
-        buf, graph, loss, logits = self._slot(spec)
-        edges = self.ds.set_graph_ids(buf, graph_ids)[1]
-        if graph is not None:
-            graph.replay()
-            return loss, logits[:edges]
-        loss, out = self._step(buf)
+        (loss, out), edges = self._run(graph_ids)
         return loss, out[:edges]
+
+
+class ReplayedFreshEval(_PaddedReplay):
+    """The validation loop of pangnn.py:241-289 over a `SubGraphDataset` as ONE captured HIP graph: the fixed-shape buffers and
+    slot logic of `ReplayedFreshStep`, and a step that runs under `torch.no_grad()` with the model in eval mode:
+        ds.collate_padded(buf);  out = model(buf);  stats.update(out, buf.y, live=buf.live_edges, pos_weight=pos_weight)
+    `out` are plain logits of all max_edges entries; those of the padded tail are whatever the decoder computes for the inert
+    self loops and are never read (`metrics.EpochStats` takes the number of real edges from device memory).  So every decoder
+    and width `model(buf)` supports in eval mode is served — `mlp` at any node_dim, `cosine`, `dot`, with or without
+    `skip_connections` / `base_model` — wider than the training replay; `--union_edge_weights` is not (the padded buffers carry
+    no union list).  Per batch the host does one id write and one graph launch; loss, confusion counts and the scores the
+    ranking metrics need accumulate in `self.stats`, read out once by `compute()`.
+    `ranking`: keep scores and labels for ROC-AUC / PR-AUC; the capacity is the edge total of `graphs` (default: all), i.e. one
+    pass over that validation set between two `reset()`s.  `capture=False` runs the very same padded step eagerly.
+    The model's `training` flag is as before after construction and after every call; parameters are never touched and no
+    autograd graph is kept."""
+
+    def __init__(self, model, ds, pos_weight, batch_size: int = 32, graphs=None, capture: bool = True, warmup: int = 1,
+                 slack: float = 1.4, threshold: float = 0.5, ranking: bool = True):
+        from .metrics import EpochStats
+        if getattr(getattr(model, "flags", None), "union_edge_weights", False):
+            raise NotImplementedError("ReplayedFreshEval: a padded batch carries no union edge list (--union_edge_weights)")
+        dev = ds.edge_index.device
+        if pos_weight is not None:       # the device scalar the captured launch reads: made once, never inside the capture
+            pos_weight = torch.as_tensor(pos_weight).detach().to(device=dev, dtype=torch.float32).reshape(-1)[:1]
+        self.model, self.pos_weight = model, pos_weight
+        h = ds._host()
+        idx = range(ds.num_graphs) if graphs is None else [int(i) for i in graphs]
+        capacity = sum(h.edge[i + 1] - h.edge[i] for i in idx) if ranking else 0
+        self.stats = EpochStats(capacity, threshold, device=ds.edge_index.device)
+        self._init_slots(ds, batch_size, graphs, capture, warmup, slack)
+
+    def _kept(self):
+        return [self.stats.state]
+
+    @torch.no_grad()
+    def _step(self, buf):
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            self.ds.collate_padded(buf)
+            out = self.model(buf)
+            self.stats.update(out, buf.y, live=buf.live_edges, pos_weight=self.pos_weight)
+        finally:
+            self.model.train(was_training)
+        return (out,)
+
+    def __call__(self, graph_ids):
+        """evaluate the disjoint union of the sub-graphs `graph_ids` (host ints, any order, at most batch_size) and fold it into
+        `self.stats`; returns the logits of the batch's real edges without synchronising — with capture a VIEW of the captured
+        graph's static output, which the next call overwrites"""
+        (out,), edges = self._run(graph_ids)
+        return out[:edges]
+
+    def compute(self) -> dict:
+        return self.stats.compute()
+
+    def reset(self):
+        self.stats.reset()
+
+
+def run_epoch(step, evaluator, train_ids, val_ids, batch_size: int = 32, generator=None) -> dict:
+    """One epoch of the reference's loop (pangnn.py:180-322) over the two replayed objects: shuffle `train_ids`, replay the
+    training batches (`step`: a ReplayedFreshStep built with `stats=`), replay the validation batches (`evaluator`: a
+    ReplayedFreshEval), read out once.  Returns the reference's epoch scalars (pangnn.py:296-322):
+    train_loss / train_acc / train_f1 and val_loss / val_acc / val_precision / val_recall / val_f1 / val_roc_auc / val_pr_auc."""
+    if step.stats is None:
+        raise ValueError("run_epoch needs ReplayedFreshStep(..., stats=EpochStats(...))")
+    train_ids, val_ids = [int(i) for i in train_ids], [int(i) for i in val_ids]
+    order = torch.randperm(len(train_ids), generator=generator).tolist()
+    step.stats.reset()
+    evaluator.reset()
+    for k in range(0, len(order), batch_size):
+        step([train_ids[j] for j in order[k:k + batch_size]])
+    for k in range(0, len(val_ids), batch_size):
+        evaluator(val_ids[k:k + batch_size])
+    tr, va = step.stats.compute(), evaluator.compute()
+    res = dict(train_loss=tr["loss"], train_acc=tr["accuracy"], train_f1=tr["f1"])
+    res.update(val_loss=va["loss"], val_acc=va["accuracy"], val_precision=va["precision"], val_recall=va["recall"],
+               val_f1=va["f1"])
+    for k in ("roc_auc", "pr_auc"):
+        if k in va:
+            res["val_" + k] = va[k]
+    return res
