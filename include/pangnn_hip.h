@@ -34,7 +34,9 @@ extern "C" {
  * Likewise pangnn_edge_dot_mixed, pangnn_gcn_norm_bwd_f32 and its _workspace_bytes (dL/d(edge_weight) of GCNConv), and
  * pangnn_qscore_fwd / pangnn_qscore_bwd with PANGNN_DTYPE_F64 (the differentiable Q-score edge weights), and
  * pangnn_csr_plan_tpos + pangnn_decoder_dgrad_stream_f32 (the T pass on one position word per edge), and
- * pangnn_csr_plan_spos + pangnn_decoder_train_stream_f32 / _mixed (the S pass on one word pair per position). */
+ * pangnn_csr_plan_spos + pangnn_decoder_train_stream_f32 / _mixed (the S pass on one word pair per position), and
+ * pangnn_decoder_mlp_loss_live_f32 / pangnn_decoder_nd_loss_live_f32 / pangnn_edge_score_loss_live_mixed (the fused-loss
+ * passes of the strict-fp32, node_dim 32 / 128 and cosine / dot decoders on a padded batch). */
 #define PANGNN_ABI_VERSION 3
 
 #define PANGNN_E_BADARG    (-1)  /* null pointer / negative size / unsupported feature width */
@@ -294,6 +296,18 @@ int pangnn_decoder_mlp_loss_f32(const float* p, int64_t ldp, const float* q, int
                                 float* g_b2, float* g_w3, float* g_b3, float* g_cvec, float* part_buf,
                                 const int32_t* part_off, int32_t precision, void* workspace,
                                 size_t workspace_bytes, pangnn_stream_t stream);
+/* ... of a fixed-shape padded batch: live_edges (DEVICE int64[1], required) as described under `live_edges` below — the first
+ * m = min(max(*live_edges, 0), num_edges) edges are real, the loss is their mean (`denom` is ignored) and the padding enters
+ * no sum.  Every other argument, the workspace and the return codes as pangnn_decoder_mlp_loss_f32; the workspace size is
+ * passed as an int64_t, as in the nd family (a negative one: PANGNN_E_WORKSPACE). */
+int pangnn_decoder_mlp_loss_live_f32(const float* p, int64_t ldp, const float* q, int64_t ldq, int64_t num_nodes,
+                                     const int64_t* edge_index, int64_t ld, int64_t num_edges, const float* extra,
+                                     const float* cvec, const float* w2, const float* b2, const float* w3,
+                                     const float* b3, int32_t D, const float* y, const float* pos_weight,
+                                     int64_t denom, float* logits, float* loss, float* g_h1, float* g_w2,
+                                     float* g_b2, float* g_w3, float* g_b3, float* g_cvec, float* part_buf,
+                                     const int32_t* part_off, int32_t precision, const int64_t* live_edges,
+                                     void* workspace, int64_t workspace_bytes, pangnn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * The same fused link decoder for node_dim D in {32, 128} (`--node_dim`, src/setup.py:38): two more instances of the width
@@ -329,6 +343,15 @@ int pangnn_decoder_nd_loss_f32(const float* p, int64_t ldp, const float* q, int6
                                float* g_b2, float* g_w3, float* g_b3, float* g_cvec, float* part_buf,
                                const int32_t* part_off, void* workspace, int64_t workspace_bytes,
                                pangnn_stream_t stream);
+/* ... of a fixed-shape padded batch (live_edges required, `denom` ignored): see pangnn_decoder_mlp_loss_live_f32 */
+int pangnn_decoder_nd_loss_live_f32(const float* p, int64_t ldp, const float* q, int64_t ldq, int64_t num_nodes,
+                                    const int64_t* edge_index, int64_t ld, int64_t num_edges, const float* extra,
+                                    const float* cvec, const float* w2, const float* b2, const float* w3,
+                                    const float* b3, int32_t D, const float* y, const float* pos_weight,
+                                    int64_t denom, float* logits, float* loss, float* g_h1, float* g_w2,
+                                    float* g_b2, float* g_w3, float* g_b3, float* g_cvec, float* part_buf,
+                                    const int32_t* part_off, const int64_t* live_edges, void* workspace,
+                                    int64_t workspace_bytes, pangnn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Two-wave-per-SIMD training decoder (csrc/decoder16.hip) — what `precision = 1` training uses.
@@ -383,6 +406,12 @@ int pangnn_decoder_nd_loss_f32(const float* p, int64_t ldp, const float* q, int6
  *   edges (`denom` is ignored); in T the positions >= *live_edges of the order are the padding and contribute 0 whatever
  *   their records hold (the pads must sort last: their endpoints are the largest node id).  A value above num_edges counts
  *   as num_edges.  NULL: every edge is real.
+ *   The one-pass fused-loss kernels of the other decoders take the same count through entry points of their own, where it is
+ *   required: pangnn_decoder_mlp_loss_live_f32 / pangnn_decoder_nd_loss_live_f32 (strict fp32, node_dim 64 / 32 and 128) and
+ *   pangnn_edge_score_loss_live_mixed (cosine / dot).  With m = min(max(*live_edges, 0), num_edges): logits are written for all
+ *   num_edges positions; dL/dlogit of an edge k >= m is exactly 0, so its dL/dh1 row (strict fp32) is a zero row and it adds
+ *   zeros to every parameter sum, run part and node row; loss and dL/dlogit[0:m] use 1.0f / (float)max(m, 1) (`denom` is
+ *   ignored); m == 0 gives loss 0 and all-zero gradients.  The tables the padded edges gather must be finite.
  * Both are reproducible (fixed-order sums, no float atomics).
  * ---------------------------------------------------------------------------------------- */
 int    pangnn_decoder_chunk_tiles(void);
@@ -703,6 +732,17 @@ int    pangnn_edge_score_loss_mixed(const void* z, int32_t z_dtype, int64_t ldz,
                                     int64_t ld, int64_t num_edges, int32_t d, int32_t mode, const float* y,
                                     const float* pos_weight, int64_t denom, float* norms, float* logits, float* loss,
                                     float* g_logits, float* loss_parts, pangnn_stream_t stream);
+/* ... of a fixed-shape padded batch (pangnn_collate_subgraphs_padded): live_edges (DEVICE int64[1], required) = the number of
+ * real edges, read by the kernel, semantics as documented for `live_edges` of the decoder entry points above — with
+ * m = min(max(*live_edges, 0), num_edges): logits[0:num_edges] are all written, g_logits[k] is exactly 0 for k >= m, loss and
+ * g_logits[0:m] use 1.0f / (float)max(m, 1) (`denom` is ignored), m == 0 gives loss 0 and zero gradients.
+ * pangnn_edge_score_bwd_mixed is the backward as it is: a padded edge's g = 0 adds exact zeros behind the real entries of a
+ * row, and a padded node (only such edges) gets a zero row, the cosine diagonal term included (z finite). */
+int    pangnn_edge_score_loss_live_mixed(const void* z, int32_t z_dtype, int64_t ldz, int64_t num_nodes,
+                                         const int64_t* edge_index, int64_t ld, int64_t num_edges, int32_t d, int32_t mode,
+                                         const float* y, const float* pos_weight, int64_t denom, float* norms, float* logits,
+                                         float* loss, float* g_logits, float* loss_parts, const int64_t* live_edges,
+                                         pangnn_stream_t stream);
 /* Backward: gz[n] (fp32, row stride ldg, 16-byte aligned) = g_scale[0] * dL/dz[n], written once per node, with g[E] = dL/dlogit
  * in edge order and g_scale a DEVICE scalar (nullable = 1: `loss.backward()` needs no host read of the upstream gradient):
  *   dot:    sum_{out-edges e=(n,m)} g_e z_m + sum_{in-edges e=(m,n)} g_e z_m

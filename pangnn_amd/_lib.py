@@ -95,6 +95,12 @@ SIGNATURES = {
                                               _p, _p, _i64,                            # y, pos_weight, denom
                                               _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,  # logits .. part_off
                                               _i32, _p, _sz, _p]),
+    # ... of a padded fixed-shape batch: live_edges (device int64[1], required) in front of the workspace
+    "pangnn_decoder_mlp_loss_live_f32": (C.c_int, [_p, _i64, _p, _i64, _i64, _p, _i64, _i64, _p, _p, _p, _p, _p, _p, _i32,
+                                                   _p, _p, _i64,                            # y, pos_weight, denom (ignored)
+                                                   _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,  # logits .. part_off
+                                                   _i32, _p, _p, _i64, _p]),                # precision, live_edges, workspace,
+                                                                                            # bytes (int64), stream
     # the same decoder for node_dim 32 / 128 (the same template of csrc/decoder.hip): the arguments above without `precision`
     "pangnn_decoder_nd_supported": (C.c_int, [_i32]),
     "pangnn_decoder_nd_fwd_f32": (C.c_int, [_p, _i64, _p, _i64, _i64, _p, _i64, _i64, _p, _p, _p, _p, _p, _p, _i32,
@@ -107,6 +113,10 @@ SIGNATURES = {
                                              _p, _p, _i64,                            # y, pos_weight, denom
                                              _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,  # logits .. part_off
                                              _p, _i64, _p]),
+    "pangnn_decoder_nd_loss_live_f32": (C.c_int, [_p, _i64, _p, _i64, _i64, _p, _i64, _i64, _p, _p, _p, _p, _p, _p, _i32,
+                                                  _p, _p, _i64,                            # y, pos_weight, denom (ignored)
+                                                  _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,  # logits .. part_off
+                                                  _p, _p, _i64, _p]),                      # live_edges, workspace, bytes, stream
     "pangnn_softmax_qscore_f64": (C.c_int, [_p, _p, _i64, _i64, C.c_double, C.c_double, C.c_double, _p, _p]),
     # two-wave-per-SIMD training decoder (csrc/decoder16.hip): S kernel (+ by-source run sums, per-edge records)
     "pangnn_decoder_chunk_tiles": (C.c_int, []),
@@ -140,6 +150,9 @@ SIGNATURES = {
     "pangnn_edge_score_loss_mixed": (C.c_int, [_p, _i32, _i64, _i64, _p, _i64, _i64, _i32, _i32,
                                                _p, _p, _i64,                            # y, pos_weight, denom
                                                _p, _p, _p, _p, _p, _p]),                # norms, logits, loss, g_logits, parts, stream
+    "pangnn_edge_score_loss_live_mixed": (C.c_int, [_p, _i32, _i64, _i64, _p, _i64, _i64, _i32, _i32,
+                                                    _p, _p, _i64,                       # y, pos_weight, denom (ignored)
+                                                    _p, _p, _p, _p, _p, _p, _p]),       # norms .. parts, live_edges, stream
     "pangnn_edge_score_bwd_mixed": (C.c_int, [_p, _i32, _i64, _i64, _i64, _i32, _i32,
                                               _p, _p, _p, _p, _p, _i64, _p,            # by source (+ segments, parts)
                                               _p, _p, _p, _p, _p, _i64, _p,            # by target

@@ -17,7 +17,8 @@
 // the A operand (written out as dL/dh1pre [E, D]).  Parameter gradients are accumulated in registers across all tiles of
 // a wave, reduced over the workgroup's waves in a fixed order and written as one partial slab per workgroup; a second
 // tiny kernel sums the slabs in index order => bitwise reproducible, no float atomics.  One forward kernel, one backward
-// kernel <D, FUSED_LOSS, RUNSUM>, one reduce kernel.
+// kernel <D, FUSED_LOSS, RUNSUM, LIVE> (LIVE: the fused loss of a padded batch, real-edge count read on the device), one
+// reduce kernel.
 //
 // What the width changes:
 //   D = 32   8 waves per workgroup; everything is one 32 x 32 block.
@@ -324,10 +325,23 @@ struct RunSumParams {
   float* part; const int32_t* part_off;
 };
 
-template <int D, bool FUSED_LOSS, bool RUNSUM>
+// LIVE (with FUSED_LOSS): the list is a fixed-shape padded batch whose first m = min(max(live_edges[0], 0), E) edges are real
+// (include/pangnn_hip.h, live_edges; one uniform load per workgroup, outside the tile loop).  An edge >= m still exists — its
+// gather and its logit store are in bounds — but it gets dL/dlogit = +0 and no loss term, and the mean is over max(m, 1)
+// edges (lp.inv_denom is not read).  Everything behind dL/dlogit is a product with it: the edge's dL/dh1 row is written as
+// zeros (the segment sums and the run parts read every row), and the parameter slabs, gcvec and the run parts receive zeros
+// from it (finite P | Q rows and weights).  The instances without LIVE never read the count and keep their FULL tile body
+// free of selects.
+// `given`: the one per-edge input that does not come with the fused loss — dL/dlogits [E] (float) without FUSED_LOSS,
+// live_edges (int64) with LIVE, unused otherwise.  One slot for both (a call has one or the other) keeps the argument block
+// of the instances without LIVE what it was before LIVE existed, and their code with it: the same instruction streams at
+// D = 64 and 128; at D = 32 the same instructions to within one, in another register allocation.
+template <int D, bool FUSED_LOSS, bool RUNSUM, bool LIVE = false>
 __global__ __launch_bounds__(Shape<D>::WAVES * 64) void decoder_bwd_kernel(
-    DecParams a, const float* __restrict__ g_logits, LossParams lp, RunSumParams rs, float* __restrict__ g_h1,
+    DecParams a, const void* __restrict__ given, LossParams lp, RunSumParams rs, float* __restrict__ g_h1,
     float* __restrict__ slabs, int64_t n_tiles) {
+  static_assert(FUSED_LOSS || !LIVE, "live_edges belongs to the fused loss");
+  const float* __restrict__ g_logits = static_cast<const float*>(given);
   using S = Shape<D>;
   constexpr int NB = S::NB, RS = S::RS, WAVES = S::WAVES;
   // D = 128: dL/dW2 is shared out over the workgroup's four waves, wave w owning the 32 rows j of block w (4 blocks of
@@ -371,6 +385,13 @@ __global__ __launch_bounds__(Shape<D>::WAVES * 64) void decoder_bwd_kernel(
   float lossp = 0.f;            // FUSED_LOSS: partial of the (already 1/denom-scaled) loss
   const float b3v = a.b3[0];
   const float pw = (FUSED_LOSS && lp.pos_weight) ? lp.pos_weight[0] : 1.f;
+  int64_t m_live = a.E;         // LIVE: the number of real edges
+  float inv_denom = lp.inv_denom;
+  if constexpr (LIVE) {
+    const int64_t lv = static_cast<const int64_t*>(given)[0];
+    m_live = lv < 0 ? 0 : lv > a.E ? a.E : lv;
+    inv_denom = 1.0f / (float)(m_live > 1 ? m_live : 1);   // the host's 1.0f / (float)denom of the list cut to m edges
+  }
 
   // what a tile carries from its front half (forward recomputation) to its back half (dL/dh1)
   f32x16 acc[NB];      // h2[j][e], lane (e = r, hh), rows acc_row(i,hh) + 32b
@@ -408,6 +429,7 @@ __global__ __launch_bounds__(Shape<D>::WAVES * 64) void decoder_bwd_kernel(
     g_e = 0.f;
     float y_e = 0.f;
     const bool live = FULL || ebase + r < a.E;
+    const bool real = LIVE ? ebase + r < m_live : live;     // (m_live <= E: a real edge is in bounds)
     if (FUSED_LOSS) {
       if (live) y_e = lp.y[ebase + r];
       if (lane < 32) wl[lane] = w_e;
@@ -429,7 +451,7 @@ __global__ __launch_bounds__(Shape<D>::WAVES * 64) void decoder_bwd_kernel(
       float ru = __builtin_amdgcn_rcpf(u);
       ru = ru * (2.f - u * ru);                     // 1 / (1 + t), one Newton step on the hardware reciprocal
       const float sig_neg = xv >= 0.f ? t * ru : ru;                              // sigmoid(-x)
-      g_e = live ? ((1.f - y_e) - lw * sig_neg) * lp.inv_denom : 0.f;
+      g_e = real ? ((1.f - y_e) - lw * sig_neg) * inv_denom : 0.f;
       // softplus(-x) = log1p(t) + max(-x, 0);  log1p(t) = log(u) * t / (u - 1) with u = fl(1 + t) (exact u - 1),
       // = t when u == 1
       const float um1 = u - 1.f;
@@ -438,7 +460,7 @@ __global__ __launch_bounds__(Shape<D>::WAVES * 64) void decoder_bwd_kernel(
       const float l1p = um1 == 0.f ? t : logf(u) * (t * rm);
       gl[r] = g_e;                                   // the two halves write the same value
       gb3p += g_e;                                   // per-half partials; lane 0's half is the one read out
-      lossp += live ? ((1.f - y_e) * xv + lw * (l1p + fmaxf(-xv, 0.f))) * lp.inv_denom : 0.f;   // select, not a branch
+      lossp += real ? ((1.f - y_e) * xv + lw * (l1p + fmaxf(-xv, 0.f))) * inv_denom : 0.f;   // select, not a branch
       if (hh == 0 && live) lp.logits[ebase + r] = xv;
     }
   };
@@ -796,9 +818,9 @@ struct GradOut {   // the outputs and the workspace of the two training operatio
   void* workspace; size_t workspace_bytes;
 };
 
-// the backward kernel (lp: with the fused loss) and the reduction over its slabs
-static int launch_bwd(const char* who, const DecArgs& c, const float* g_logits, const LossParams* lp, float* loss,
-                      int32_t precision, const GradOut& o, hipStream_t s) {
+// the backward kernel (lp: with the fused loss; live: of a padded batch, with lp) and the reduction over its slabs
+static int launch_bwd(const char* who, const DecArgs& c, const float* g_logits, const LossParams* lp, const int64_t* live,
+                      float* loss, int32_t precision, const GradOut& o, hipStream_t s) {
   PG_CHECK_ARG(o.g_w2 && o.g_b2 && o.g_w3 && o.g_b3, PANGNN_E_BADARG, "%s: null gradient output", who);
   PG_CHECK_ARG(precision == 0, PANGNN_E_BADARG,
                "%s: only precision 0 (f32 MFMA) here; the bf16 matrix-pipe mode is pangnn_decoder_train_f32 + "
@@ -822,10 +844,13 @@ static int launch_bwd(const char* who, const DecArgs& c, const float* g_logits, 
     with_width(c.D, [&](auto d) {
       constexpr int D = decltype(d)::value;
       const dim3 b(Shape<D>::WAVES * 64);
-      if (lp && rs.part) hipLaunchKernelGGL((decoder_bwd_kernel<D, true, true>), g, b, 0, s, a, g_logits, l, rs, o.g_h1, ws, n_tiles);
-      else if (lp) hipLaunchKernelGGL((decoder_bwd_kernel<D, true, false>), g, b, 0, s, a, g_logits, l, rs, o.g_h1, ws, n_tiles);
-      else if (rs.part) hipLaunchKernelGGL((decoder_bwd_kernel<D, false, true>), g, b, 0, s, a, g_logits, l, rs, o.g_h1, ws, n_tiles);
-      else hipLaunchKernelGGL((decoder_bwd_kernel<D, false, false>), g, b, 0, s, a, g_logits, l, rs, o.g_h1, ws, n_tiles);
+      const void* given = lp ? static_cast<const void*>(live) : static_cast<const void*>(g_logits);
+      if (lp && live && rs.part) hipLaunchKernelGGL((decoder_bwd_kernel<D, true, true, true>), g, b, 0, s, a, given, l, rs, o.g_h1, ws, n_tiles);
+      else if (lp && live) hipLaunchKernelGGL((decoder_bwd_kernel<D, true, false, true>), g, b, 0, s, a, given, l, rs, o.g_h1, ws, n_tiles);
+      else if (lp && rs.part) hipLaunchKernelGGL((decoder_bwd_kernel<D, true, true>), g, b, 0, s, a, given, l, rs, o.g_h1, ws, n_tiles);
+      else if (lp) hipLaunchKernelGGL((decoder_bwd_kernel<D, true, false>), g, b, 0, s, a, given, l, rs, o.g_h1, ws, n_tiles);
+      else if (rs.part) hipLaunchKernelGGL((decoder_bwd_kernel<D, false, true>), g, b, 0, s, a, given, l, rs, o.g_h1, ws, n_tiles);
+      else hipLaunchKernelGGL((decoder_bwd_kernel<D, false, false>), g, b, 0, s, a, given, l, rs, o.g_h1, ws, n_tiles);
     });
     PG_CHECK_LAUNCH(who);
   }
@@ -837,16 +862,21 @@ static int decoder_bwd(const char* who, bool nd, const DecArgs& c, const float* 
   int rc = check_common(who, nd, c);
   if (rc) return rc;
   PG_CHECK_ARG(c.E == 0 || g_logits, PANGNN_E_BADARG, "%s: null g_logits", who);
-  return launch_bwd(who, c, g_logits, nullptr, nullptr, precision, o, s);
+  return launch_bwd(who, c, g_logits, nullptr, nullptr, nullptr, precision, o, s);
 }
 
+// `want_live`: the *_loss_live_f32 entry points — live_edges is required and `denom` is not looked at (the kernel divides by
+// the live count it reads)
 static int decoder_loss(const char* who, bool nd, const DecArgs& c, const float* y, const float* pos_weight, int64_t denom,
-                        float* logits, float* loss, int32_t precision, const GradOut& o, hipStream_t s) {
+                        float* logits, float* loss, int32_t precision, const GradOut& o, bool want_live, const int64_t* live,
+                        hipStream_t s) {
   int rc = check_common(who, nd, c);
   if (rc) return rc;
-  PG_CHECK_ARG(denom > 0 && loss && (c.E == 0 || (y && logits)), PANGNN_E_BADARG, "%s: bad denom / null pointer", who);
-  const LossParams lp{y, pos_weight, 1.0f / (float)denom, logits};
-  return launch_bwd(who, c, nullptr, &lp, loss, precision, o, s);
+  PG_CHECK_ARG((want_live || denom > 0) && loss && (c.E == 0 || (y && logits)), PANGNN_E_BADARG,
+               "%s: bad denom / null pointer", who);
+  PG_CHECK_ARG(!want_live || live, PANGNN_E_BADARG, "%s: null live_edges", who);
+  const LossParams lp{y, pos_weight, want_live ? 0.f : 1.0f / (float)denom, logits};
+  return launch_bwd(who, c, nullptr, &lp, want_live ? live : nullptr, loss, precision, o, s);
 }
 
 // the nd family passes its workspace size as an int64_t: a negative one is too small
@@ -897,8 +927,22 @@ extern "C" int pangnn_decoder_mlp_loss_f32(const float* p, int64_t ldp, const fl
                                            size_t workspace_bytes, pangnn_stream_t stream) {
   const DecArgs c{p, ldp, q, ldq, num_nodes, edge_index, ld, num_edges, extra, cvec, w2, b2, w3, b3, D};
   const GradOut o{g_h1, g_w2, g_b2, g_w3, g_b3, g_cvec, part_buf, part_off, workspace, workspace_bytes};
-  return decoder_loss("pangnn_decoder_mlp_loss_f32", false, c, y, pos_weight, denom, logits, loss, precision, o,
+  return decoder_loss("pangnn_decoder_mlp_loss_f32", false, c, y, pos_weight, denom, logits, loss, precision, o, false, nullptr,
                       (hipStream_t)stream);
+}
+
+extern "C" int pangnn_decoder_mlp_loss_live_f32(const float* p, int64_t ldp, const float* q, int64_t ldq, int64_t num_nodes,
+                                                const int64_t* edge_index, int64_t ld, int64_t num_edges, const float* extra,
+                                                const float* cvec, const float* w2, const float* b2, const float* w3,
+                                                const float* b3, int32_t D, const float* y, const float* pos_weight,
+                                                int64_t denom, float* logits, float* loss, float* g_h1, float* g_w2,
+                                                float* g_b2, float* g_w3, float* g_b3, float* g_cvec, float* part_buf,
+                                                const int32_t* part_off, int32_t precision, const int64_t* live_edges,
+                                                void* workspace, int64_t workspace_bytes, pangnn_stream_t stream) {
+  const DecArgs c{p, ldp, q, ldq, num_nodes, edge_index, ld, num_edges, extra, cvec, w2, b2, w3, b3, D};
+  const GradOut o{g_h1, g_w2, g_b2, g_w3, g_b3, g_cvec, part_buf, part_off, workspace, ws_size(workspace_bytes)};
+  return decoder_loss("pangnn_decoder_mlp_loss_live_f32", false, c, y, pos_weight, denom, logits, loss, precision, o, true,
+                      live_edges, (hipStream_t)stream);
 }
 
 extern "C" int pangnn_decoder_nd_supported(int32_t D) { return nd_supported(D) ? 1 : 0; }
@@ -937,5 +981,20 @@ extern "C" int pangnn_decoder_nd_loss_f32(const float* p, int64_t ldp, const flo
                                           pangnn_stream_t stream) {
   const DecArgs c{p, ldp, q, ldq, num_nodes, edge_index, ld, num_edges, extra, cvec, w2, b2, w3, b3, D};
   const GradOut o{g_h1, g_w2, g_b2, g_w3, g_b3, g_cvec, part_buf, part_off, workspace, ws_size(workspace_bytes)};
-  return decoder_loss("pangnn_decoder_nd_loss_f32", true, c, y, pos_weight, denom, logits, loss, 0, o, (hipStream_t)stream);
+  return decoder_loss("pangnn_decoder_nd_loss_f32", true, c, y, pos_weight, denom, logits, loss, 0, o, false, nullptr,
+                      (hipStream_t)stream);
+}
+
+extern "C" int pangnn_decoder_nd_loss_live_f32(const float* p, int64_t ldp, const float* q, int64_t ldq, int64_t num_nodes,
+                                               const int64_t* edge_index, int64_t ld, int64_t num_edges, const float* extra,
+                                               const float* cvec, const float* w2, const float* b2, const float* w3,
+                                               const float* b3, int32_t D, const float* y, const float* pos_weight,
+                                               int64_t denom, float* logits, float* loss, float* g_h1, float* g_w2,
+                                               float* g_b2, float* g_w3, float* g_b3, float* g_cvec, float* part_buf,
+                                               const int32_t* part_off, const int64_t* live_edges, void* workspace,
+                                               int64_t workspace_bytes, pangnn_stream_t stream) {
+  const DecArgs c{p, ldp, q, ldq, num_nodes, edge_index, ld, num_edges, extra, cvec, w2, b2, w3, b3, D};
+  const GradOut o{g_h1, g_w2, g_b2, g_w3, g_b3, g_cvec, part_buf, part_off, workspace, ws_size(workspace_bytes)};
+  return decoder_loss("pangnn_decoder_nd_loss_live_f32", true, c, y, pos_weight, denom, logits, loss, 0, o, true, live_edges,
+                      (hipStream_t)stream);
 }

@@ -34,14 +34,19 @@ __global__ __launch_bounds__(kBlock) void score_norm_kernel(const char* __restri
 }
 
 // one group of G lanes per edge, U edges per group in flight; LOSS: BCEWithLogits(pos_weight) as bce_kernel computes it, one
-// partial per block (fixed slice of edges, fixed order), finished by score_loss_finish_kernel
-template <int D, int XF, int MODE, bool LOSS>
+// partial per block (fixed slice of edges, fixed order), finished by score_loss_finish_kernel.
+// LIVE (with LOSS): the list is a fixed-shape padded batch whose first m = min(max(live[0], 0), e) edges are real
+// (include/pangnn_hip.h, live_edges): every edge keeps its logit, an edge k >= m gets dL/dlogit = +0 and adds nothing to the
+// loss, and the mean is over max(m, 1) edges (inv_denom is not read).  live[0] is one uniform load per block, outside the edge
+// loop; the instances without LIVE never look at `live` and are the code they were before it existed.
+template <int D, int XF, int MODE, bool LOSS, bool LIVE = false>
 __global__ __launch_bounds__(kBlock) void edge_score_kernel(const char* __restrict__ z, int64_t ldz,
                                                             const int64_t* __restrict__ ei, int64_t ld, int64_t e,
                                                             const float* __restrict__ norms, float* __restrict__ logits,
                                                             const float* __restrict__ y, const float* __restrict__ pos_weight,
                                                             float inv_denom, float* __restrict__ g_logits,
-                                                            float* __restrict__ partial) {
+                                                            float* __restrict__ partial, const int64_t* __restrict__ live) {
+  static_assert(LOSS || !LIVE, "live_edges belongs to the fused loss");
   constexpr int G = D / 4, ES = XF ? 2 : 4, U = 2;
   const int lane = threadIdx.x & (kWave - 1), fl = lane % G;
   const int64_t groups = (int64_t)gridDim.x * (kBlock / G);
@@ -49,6 +54,12 @@ __global__ __launch_bounds__(kBlock) void edge_score_kernel(const char* __restri
   const char* zb = z + fl * 4 * ES;
   const uint64_t ldb = (uint64_t)ldz * ES;
   const float pw = (LOSS && pos_weight) ? pos_weight[0] : 1.f;
+  int64_t m = e;                                             // LIVE: the number of real edges
+  if (LIVE) {
+    const int64_t lv = live[0];
+    m = lv < 0 ? 0 : lv > e ? e : lv;
+    inv_denom = 1.0f / (float)(m > 1 ? m : 1);               // the host's 1.0f / (float)denom of the list cut to m edges
+  }
   float acc = 0.f;
   for (int64_t k = gid; k < e; k += U * groups) {
     int64_t s[U], d[U];
@@ -77,9 +88,10 @@ __global__ __launch_bounds__(kBlock) void edge_score_kernel(const char* __restri
           const float ax = fabsf(x);
           const float t = expf(-ax);
           const float sp = log1pf(t) + fmaxf(-x, 0.f);                      // softplus(-x)
-          acc += (1.f - yv) * x + lw * sp;
+          const bool real = !LIVE || kk < m;                                // padding: no term, dL/dlogit = 0 whatever x is
+          if (real) acc += (1.f - yv) * x + lw * sp;
           const float sm = t / (1.f + t);                                   // sigmoid(-|x|): bce_kernel's form of dl/dx
-          g_logits[kk] = (x >= 0.f ? (1.f - yv) - lw * sm : lw * sm - pw * yv) * inv_denom;
+          g_logits[kk] = real ? (x >= 0.f ? (1.f - yv) - lw * sm : lw * sm - pw * yv) * inv_denom : 0.f;
         }
       }
     }
@@ -192,7 +204,11 @@ __device__ __forceinline__ void score_order(const ScoreOrder& o, int64_t node, c
   }
 }
 
-// one wave per node: out-edges (by source), then in-edges (by target), the diagonal term, the upstream scale; one store
+// one wave per node: out-edges (by source), then in-edges (by target), the diagonal term, the upstream scale; one store.
+// A padded batch (pangnn_edge_score_loss_live_mixed) needs nothing here: a padded edge arrives with g_e = +0, so its c_e z_m
+// term adds an exact zero to the row of either endpoint (z finite) and, being later in list order than every real edge, it sits
+// behind them in the stable CSR rows: the real entries keep their sub-group and their order, the row sum its bits.  A padded node
+// has only such edges: acc = 0 and, for cosine, ds = sum g_e cos_e = 0, so the diagonal term k_n ds z_n is 0 too — a zero row.
 template <int D, int XF, int MODE>
 __global__ __launch_bounds__(kBlock) void score_grad_kernel(const char* __restrict__ z, int64_t ldz, int64_t n,
                                                             ScoreOrder src, ScoreOrder dst, const float* __restrict__ g,
@@ -240,19 +256,24 @@ int launch_norms(const void* z, int64_t ldz, int64_t n, float* norms, hipStream_
 
 template <int D, int XF, int MODE>
 int launch_edges(const void* z, int64_t ldz, const int64_t* ei, int64_t ld, int64_t e, const float* norms, float* logits,
-                 const float* y, const float* pw, int64_t denom, float* loss, float* g_logits, float* parts, hipStream_t s) {
+                 const float* y, const float* pw, int64_t denom, float* loss, float* g_logits, float* parts,
+                 const int64_t* live, hipStream_t s) {
   const bool fused = loss != nullptr;
   int64_t blocks = blocks_for(e, kBlock / (D / 4));
   blocks = blocks < 1 ? 1 : blocks > kScoreMaxBlocks ? kScoreMaxBlocks : blocks;
   if (!fused) {
     if (e == 0) return 0;
     hipLaunchKernelGGL((edge_score_kernel<D, XF, MODE, false>), dim3(blocks), dim3(kBlock), 0, s, static_cast<const char*>(z),
-                       ldz, ei, ld, e, norms, logits, nullptr, nullptr, 0.f, nullptr, nullptr);
+                       ldz, ei, ld, e, norms, logits, nullptr, nullptr, 0.f, nullptr, nullptr, nullptr);
     PG_CHECK_LAUNCH("pangnn_edge_score_mixed");
     return 0;
   }
-  hipLaunchKernelGGL((edge_score_kernel<D, XF, MODE, true>), dim3(blocks), dim3(kBlock), 0, s, static_cast<const char*>(z), ldz,
-                     ei, ld, e, norms, logits, y, pw, 1.0f / (float)denom, g_logits, parts);
+  if (live)
+    hipLaunchKernelGGL((edge_score_kernel<D, XF, MODE, true, true>), dim3(blocks), dim3(kBlock), 0, s,
+                       static_cast<const char*>(z), ldz, ei, ld, e, norms, logits, y, pw, 0.f, g_logits, parts, live);
+  else
+    hipLaunchKernelGGL((edge_score_kernel<D, XF, MODE, true>), dim3(blocks), dim3(kBlock), 0, s, static_cast<const char*>(z),
+                       ldz, ei, ld, e, norms, logits, y, pw, 1.0f / (float)denom, g_logits, parts, nullptr);
   PG_CHECK_LAUNCH("pangnn_edge_score_loss_mixed");
   hipLaunchKernelGGL(score_loss_finish_kernel, dim3(1), dim3(kWave), 0, s, parts, (int)blocks, loss);
   PG_CHECK_LAUNCH("pangnn_edge_score_loss_mixed(finish)");
@@ -304,12 +325,13 @@ int dispatch3(int d, int xf, int mode, A... a) {
 template <int D, int XF, int MODE>
 struct FwdFn {
   static int run(const void* z, int64_t ldz, int64_t n, const int64_t* ei, int64_t ld, int64_t e, float* norms, float* logits,
-                 const float* y, const float* pw, int64_t denom, float* loss, float* g_logits, float* parts, hipStream_t s) {
+                 const float* y, const float* pw, int64_t denom, float* loss, float* g_logits, float* parts, const int64_t* live,
+                 hipStream_t s) {
     if (MODE == PANGNN_SCORE_COSINE) {
       const int rc = launch_norms<D, XF>(z, ldz, n, norms, s);
       if (rc) return rc;
     }
-    return launch_edges<D, XF, MODE>(z, ldz, ei, ld, e, norms, logits, y, pw, denom, loss, g_logits, parts, s);
+    return launch_edges<D, XF, MODE>(z, ldz, ei, ld, e, norms, logits, y, pw, denom, loss, g_logits, parts, live, s);
   }
 };
 
@@ -355,7 +377,7 @@ extern "C" int pangnn_edge_score_mixed(const void* z, int32_t z_dtype, int64_t l
   PG_CHECK_ARG(mode == PANGNN_SCORE_DOT || num_nodes == 0 || norms, PANGNN_E_BADARG, "%s: cosine needs norms", fn);
   return dispatch3<FwdFn>(d, z_dtype, mode, z, ldz, num_nodes, edge_index, ld, num_edges, norms, logits,
                           (const float*)nullptr, (const float*)nullptr, (int64_t)1, (float*)nullptr, (float*)nullptr,
-                          (float*)nullptr, (hipStream_t)stream);
+                          (float*)nullptr, (const int64_t*)nullptr, (hipStream_t)stream);
 }
 
 extern "C" int pangnn_edge_score_loss_mixed(const void* z, int32_t z_dtype, int64_t ldz, int64_t num_nodes,
@@ -370,7 +392,22 @@ extern "C" int pangnn_edge_score_loss_mixed(const void* z, int32_t z_dtype, int6
                "%s: null pointer", fn);
   PG_CHECK_ARG(mode == PANGNN_SCORE_DOT || num_nodes == 0 || norms, PANGNN_E_BADARG, "%s: cosine needs norms", fn);
   return dispatch3<FwdFn>(d, z_dtype, mode, z, ldz, num_nodes, edge_index, ld, num_edges, norms, logits, y, pos_weight, denom,
-                          loss, g_logits, loss_parts, (hipStream_t)stream);
+                          loss, g_logits, loss_parts, (const int64_t*)nullptr, (hipStream_t)stream);
+}
+
+extern "C" int pangnn_edge_score_loss_live_mixed(const void* z, int32_t z_dtype, int64_t ldz, int64_t num_nodes,
+                                                 const int64_t* edge_index, int64_t ld, int64_t num_edges, int32_t d,
+                                                 int32_t mode, const float* y, const float* pos_weight, int64_t denom,
+                                                 float* norms, float* logits, float* loss, float* g_logits, float* loss_parts,
+                                                 const int64_t* live_edges, pangnn_stream_t stream) {
+  const char* fn = "pangnn_edge_score_loss_live_mixed";
+  if (int rc = check_rows(fn, z, z_dtype, ldz, num_nodes, num_edges, d, mode)) return rc;
+  PG_CHECK_ARG(ld >= num_edges, PANGNN_E_BADARG, "%s: ld < num_edges", fn);     // denom is ignored: the kernel divides by the live count
+  PG_CHECK_ARG(live_edges && loss && loss_parts && (num_edges == 0 || (edge_index && logits && y && g_logits)), PANGNN_E_BADARG,
+               "%s: null pointer", fn);
+  PG_CHECK_ARG(mode == PANGNN_SCORE_DOT || num_nodes == 0 || norms, PANGNN_E_BADARG, "%s: cosine needs norms", fn);
+  return dispatch3<FwdFn>(d, z_dtype, mode, z, ldz, num_nodes, edge_index, ld, num_edges, norms, logits, y, pos_weight,
+                          (int64_t)1, loss, g_logits, loss_parts, live_edges, (hipStream_t)stream);
 }
 
 extern "C" int pangnn_edge_score_bwd_mixed(const void* z, int32_t z_dtype, int64_t ldz, int64_t num_nodes, int64_t num_edges,

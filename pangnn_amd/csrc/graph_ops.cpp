@@ -1,5 +1,5 @@
 // The per-step operators that READ A GRAPH, in C++ end to end (round 5):
-//   gcn_propagate, embed_conv_in, embed_conv_in_linear, embed_propagate, decoder_loss, decoder_loss_z, decoder_mlp, edge_score, edge_score_loss,
+//   gcn_propagate, embed_conv_in, embed_conv_in_linear, embed_propagate, decoder_loss, decoder_loss_z, decoder_mlp, edge_score, edge_score_loss, edge_score_loss_live,
 //   edge_conv
 //   and their backward ops
 // — schema, HIP ("CUDA" key) implementation and autograd formula (torch::autograd::Function under the Autograd key), like
@@ -877,7 +877,8 @@ at::Tensor score_rows(const char* op, const at::Tensor& z, int64_t mode) {
 std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> score_forward(const char* op, const at::Tensor& z,
                                                                          const at::Tensor& edge_index, int64_t mode,
                                                                          const c10::optional<at::Tensor>& y,
-                                                                         const c10::optional<at::Tensor>& pos_weight, int64_t denom) {
+                                                                         const c10::optional<at::Tensor>& pos_weight, int64_t denom,
+                                                                         const c10::optional<at::Tensor>& live = c10::nullopt) {
   const at::Tensor zr = score_rows(op, z, mode);
   const DeviceGuard guard(z.device());
   const int64_t n = zr.size(0);
@@ -896,6 +897,14 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> score_forward(const c
   c10::optional<at::Tensor> pw;
   if (defined(pos_weight)) pw = f32c(*pos_weight).reshape({-1});
   at::Tensor loss = at::empty({1}, fo), g_logits = at::empty({e}, fo), parts = at::empty({PANGNN_EDGE_SCORE_LOSS_PARTS}, fo);
+  if (defined(live)) {      // a padded fixed-shape batch: the kernel reads the number of real edges and divides by it
+    check_rc(pangnn_edge_score_loss_live_mixed(zr.data_ptr(), dtype_code(zr), zr.stride(0), n, v.ei.data_ptr<int64_t>(), e, e,
+                                               (int32_t)zr.size(1), (int32_t)mode, yy.data_ptr<float>(), opt_ptr<float>(pw), denom,
+                                               nrm, logits.data_ptr<float>(), loss.data_ptr<float>(), g_logits.data_ptr<float>(),
+                                               parts.data_ptr<float>(), live->data_ptr<int64_t>(), stream_of(z)),
+             "pangnn_edge_score_loss_live_mixed");
+    return {logits, norms, loss.view(at::IntArrayRef{}), g_logits};
+  }
   check_rc(pangnn_edge_score_loss_mixed(zr.data_ptr(), dtype_code(zr), zr.stride(0), n, v.ei.data_ptr<int64_t>(), e, e,
                                         (int32_t)zr.size(1), (int32_t)mode, yy.data_ptr<float>(), opt_ptr<float>(pw), denom, nrm,
                                         logits.data_ptr<float>(), loss.data_ptr<float>(), g_logits.data_ptr<float>(),
@@ -917,6 +926,21 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> edge_score_loss(const
   operand_any_float("edge_score_loss", "pos_weight", pos_weight, z);
   TORCH_CHECK(y.dim() == 1 && y.size(0) == edge_index.size(1) && denom > 0, "pangnn::edge_score_loss: y must be [E], denom > 0");
   auto [logits, norms, loss, g_logits] = score_forward("edge_score_loss", z, edge_index, mode, y, pos_weight, denom);
+  return {loss, logits, g_logits, norms};
+}
+
+// ... of a padded fixed-shape batch: `live` (device int64, at least one element) = the number of real edges
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> edge_score_loss_live(const at::Tensor& z, const at::Tensor& edge_index,
+                                                                                int64_t mode, const at::Tensor& y,
+                                                                                const c10::optional<at::Tensor>& pos_weight,
+                                                                                const at::Tensor& live) {
+  operand_any_float("edge_score_loss_live", "y", y, z);
+  operand_any_float("edge_score_loss_live", "pos_weight", pos_weight, z);
+  TORCH_CHECK(y.dim() == 1 && y.size(0) == edge_index.size(1), "pangnn::edge_score_loss_live: y must be [E]");
+  TORCH_CHECK(live.is_cuda() && live.device() == z.device() && live.scalar_type() == at::kLong && live.numel() >= 1 &&
+                  live.is_contiguous(),
+              "pangnn::edge_score_loss_live: live must be a contiguous int64 tensor on ", z.device());
+  auto [logits, norms, loss, g_logits] = score_forward("edge_score_loss_live", z, edge_index, mode, y, pos_weight, 1, live);
   return {loss, logits, g_logits, norms};
 }
 
@@ -1353,6 +1377,39 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> edge_score_loss_autog
   return {o[0], o[1], o[2], o[3]};
 }
 
+// the padded batch's form: the same stored dL/dlogit (0 on the padding), the same node pass
+class EdgeScoreLossLiveFunction : public torch::autograd::Function<EdgeScoreLossLiveFunction> {
+ public:
+  static variable_list forward(AutogradContext* ctx, const at::Tensor& z, const at::Tensor& edge_index, int64_t mode,
+                               const at::Tensor& y, const OptT& pos_weight, const at::Tensor& live) {
+    at::AutoDispatchBelowADInplaceOrView below;
+    static auto op = typed_op<std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor>(
+        const at::Tensor&, const at::Tensor&, int64_t, const at::Tensor&, const OptT&, const at::Tensor&)>(
+        "pangnn::edge_score_loss_live");
+    auto [loss, logits, g_logits, norms] = op.call(z, edge_index, mode, y, pos_weight, live);
+    ctx->save_for_backward({z, edge_index, logits, g_logits, norms});
+    ctx->saved_data["mode"] = mode;
+    ctx->mark_non_differentiable({logits, g_logits, norms});
+    return {loss, logits, g_logits, norms};
+  }
+  static variable_list backward(AutogradContext* ctx, variable_list grads) {
+    variable_list out(6);
+    if (!grads[0].defined()) return out;
+    const auto s = ctx->get_saved_variables();
+    static auto op = typed_op<EdgeScoreBwd>("pangnn::edge_score_backward");
+    out[0] = op.call(s[3], s[0], s[1], s[2], s[4], OptT(grads[0]), ctx->saved_data["mode"].toInt());
+    return out;
+  }
+};
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> edge_score_loss_live_autograd(const at::Tensor& z,
+                                                                                         const at::Tensor& edge_index,
+                                                                                         int64_t mode, const at::Tensor& y,
+                                                                                         const OptT& pos_weight,
+                                                                                         const at::Tensor& live) {
+  auto o = EdgeScoreLossLiveFunction::apply(z, edge_index, mode, y, pos_weight, live);
+  return {o[0], o[1], o[2], o[3]};
+}
+
 class EdgeConvFunction : public torch::autograd::Function<EdgeConvFunction> {
  public:
   static variable_list forward(AutogradContext* ctx, const at::Tensor& u, const at::Tensor& v, const at::Tensor& w2,
@@ -1424,6 +1481,9 @@ TORCH_LIBRARY_FRAGMENT(pangnn, m) {
   m.def("edge_conv_backward(Tensor g, Tensor arg, Tensor u, Tensor v, Tensor w2, Tensor edge_index) -> (Tensor, Tensor, Tensor, Tensor)");
   m.def("edge_score_loss(Tensor z, Tensor edge_index, int mode, Tensor y, Tensor? pos_weight, int denom) -> "
         "(Tensor, Tensor, Tensor, Tensor)");
+  // ... of a padded fixed-shape batch: live[0] (device int64) real edges, the mean is over them
+  m.def("edge_score_loss_live(Tensor z, Tensor edge_index, int mode, Tensor y, Tensor? pos_weight, Tensor live) -> "
+        "(Tensor, Tensor, Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(pangnn, CompositeExplicitAutograd, m) {
@@ -1453,6 +1513,7 @@ TORCH_LIBRARY_IMPL(pangnn, CUDA, m) {
   m.impl("edge_score", &edge_score);
   m.impl("edge_score_backward", &edge_score_backward);
   m.impl("edge_score_loss", &edge_score_loss);
+  m.impl("edge_score_loss_live", &edge_score_loss_live);
   m.impl("edge_conv", &edge_conv);
   m.impl("edge_conv_backward", &edge_conv_backward);
 }
@@ -1467,5 +1528,6 @@ TORCH_LIBRARY_IMPL(pangnn, Autograd, m) {
   m.impl("decoder_mlp", &decoder_mlp_autograd);
   m.impl("edge_score", &edge_score_autograd);
   m.impl("edge_score_loss", &edge_score_loss_autograd);
+  m.impl("edge_score_loss_live", &edge_score_loss_live_autograd);
   m.impl("edge_conv", &edge_conv_autograd);
 }

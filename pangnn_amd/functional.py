@@ -795,9 +795,13 @@ def _decoder_f32(p, q, st: EdgeStructure, ex, cv, w2, b2, w3, b3, y=None, pw=Non
     DECODER_PRECISION 0 (pangnn_decoder_mlp_*, which take `precision`) and the widths of DECODER_ND_WIDTHS in either mode
     (pangnn_decoder_nd_*).  One launch of *_loss_f32 (y given: logits, loss and every gradient) or *_bwd_f32 (the given
     dL/dlogits), which writes dL/dh1 [E, D] and, for a source-sorted list, per-run partial rows; then dL/dP by source and
-    dL/dQ by target, into `out_p` / `out_q` when given (e.g. the column windows of one [N, 2D] gradient)."""
-    if live is not None:
-        raise ValueError("live= (a padded fixed-shape batch) needs node_dim 64 in the default precision mode")
+    dL/dQ by target, into `out_p` / `out_q` when given (e.g. the column windows of one [N, 2D] gradient).
+    `live` (device int64[1], with `y`): a padded fixed-shape batch as in _decoder_train16 — *_loss_live_f32 reads the number of
+    real edges, writes zero dL/dh1 rows and zero run parts for the padding and divides by that number (`denom` is ignored), so
+    the sums behind it need no change."""
+    if live is not None and y is None:
+        raise ValueError("live= (a padded fixed-shape batch) needs the fused loss (y=); the given-gradient backward has no "
+                         "such form")
     dev = p.device
     e, d = st.num_edges, p.shape[1]
     nd = d in DECODER_ND_WIDTHS
@@ -815,10 +819,10 @@ def _decoder_f32(p, q, st: EdgeStructure, ex, cv, w2, b2, w3, b3, y=None, pw=Non
     head = _decoder_head(p, q, st, ex, cv, w2, b2, w3, b3)
     tail = (_lib.ptr(g_h1), g_w2.data_ptr(), g_b2.data_ptr(), g_w3.data_ptr(), g_b3.data_ptr(), _lib.ptr(g_cv),
             _lib.ptr(parts), None if plan is None else plan.part_off.data_ptr()) + (() if nd else (DECODER_PRECISION,)) + \
-           (ws.data_ptr(), ws_bytes)
+           (() if live is None else (live.data_ptr(),)) + (ws.data_ptr(), ws_bytes)
     if fused:
-        _launch(dev, name + "loss_f32", *head, _lib.ptr(y), _lib.ptr(pw), int(denom), _lib.ptr(logits), loss.data_ptr(),
-                *tail, tag="dec.bwd")
+        _launch(dev, name + ("loss_f32" if live is None else "loss_live_f32"), *head, _lib.ptr(y), _lib.ptr(pw), int(denom),
+                _lib.ptr(logits), loss.data_ptr(), *tail, tag="dec.bwd")
     else:
         _launch(dev, name + "bwd_f32", *head, _lib.ptr(g_logits), *tail, tag="dec.bwd")
     gp = gq = None
@@ -967,8 +971,8 @@ class _DecoderLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, p, q, st: EdgeStructure, extra, cvec, w2, b2, w3, b3, y, pos_weight, denom, pq_joint, live=None):
         _lib.require_device(p, q, extra, cvec, w2, b2, w3, b3, y, pos_weight)
-        if live is not None and (DECODER_PRECISION != 1 or live.dtype != torch.int64 or not live.is_cuda):
-            raise ValueError("live= (a padded fixed-shape batch) needs the default decoder mode and a device int64 tensor")
+        if live is not None and (live.dtype != torch.int64 or not live.is_cuda or not live.is_contiguous()):
+            raise ValueError("live= (a padded fixed-shape batch) needs a contiguous device int64 tensor")
         p, q, ex, cv, w2, b2, w3, b3, y, pw = _decoder_operands(p, None if pq_joint else q, extra, cvec, w2, b2, w3, b3,
                                                                 y, pos_weight)
         loss, logits, gp, gq, g_cv, g_w2, g_b2, g_w3, g_b3 = _decoder_grads(
@@ -1089,11 +1093,17 @@ def edge_score(z, st: EdgeStructure, mode: str):
     return _torch_ops().edge_score(z, st, m)             # the only route: pangnn::edge_score (csrc/graph_ops.cpp)
 
 
-def edge_score_loss(z, st: EdgeStructure, mode: str, y, pos_weight=None, denom=None):
-    """(loss, detached logits) = (BCEWithLogitsLoss(pos_weight)(decoder(z), y) averaged over `denom` edges, logits)"""
+def edge_score_loss(z, st: EdgeStructure, mode: str, y, pos_weight=None, denom=None, live=None):
+    """(loss, detached logits) = (BCEWithLogitsLoss(pos_weight)(decoder(z), y) averaged over `denom` edges, logits).
+    `live` (device int64[1]): a padded fixed-shape batch whose first live[0] edges are real (train.ReplayedFreshStep): the loss
+    is their mean (`denom` is ignored), the padding's dL/dlogit is 0 and its nodes get zero gradient rows"""
     m = SCORE_MODES[mode]
     _whole_graph("edge_score_loss", st)
-    _lib.require_device(z, y, pos_weight)
+    _lib.require_device(z, y, pos_weight, live)
+    if live is not None:
+        if live.dtype != torch.int64 or not live.is_contiguous():
+            raise ValueError("live= (a padded fixed-shape batch) needs a contiguous device int64 tensor")
+        return _torch_ops().edge_score_loss_live(z, st, m, y, pos_weight, live)    # the only route: pangnn::edge_score_loss_live
     denom = st.num_edges if denom is None else denom
     return _torch_ops().edge_score_loss(z, st, m, y, pos_weight, denom)  # the only route: pangnn::edge_score_loss
 

@@ -288,23 +288,28 @@ class AlternateGCN(nn.Module):
         through the handle `forward` returns in training mode (deferred.DeferredLogits)."""
         from .train import criterion
         ops, z = self._fused_decoder_operands(graph)
-        padded = getattr(graph, "live_edges", None) is not None
-        if ops is not None and not (padded and self.mlp[2].in_features != 64):
+        # a padded fixed-shape batch (SubGraphDataset.padded_buffers) carries the number of its real edges on the device; every
+        # fused loss kernel reads it there (decoder16.hip's S / T pair, decoder.hip's one-pass backward, edge_score.hip)
+        live = getattr(graph, "live_edges", None)
+        if ops is not None:
             pq, st, extra, cvec, layer = ops
             if layer is not None:
                 return PF.decoder_loss_z(*layer, st, extra, cvec, self.mlp[2].weight, self.mlp[2].bias,
                                          self.mlp[4].weight.view(-1), self.mlp[4].bias, labels, pos_weight, labels.shape[0])
-            # a padded fixed-shape batch (SubGraphDataset.padded_buffers) carries the number of its real edges on the device
             return PF.decoder_loss_pq(pq, st, extra, cvec, self.mlp[2].weight, self.mlp[2].bias,
                                       self.mlp[4].weight.view(-1), self.mlp[4].bias, labels, pos_weight,
-                                      labels.shape[0], live=getattr(graph, "live_edges", None))
-        if getattr(graph, "live_edges", None) is not None:
-            raise NotImplementedError("a padded fixed-shape batch needs the fused training decoder (mlp decoder, node_dim 64)")
+                                      labels.shape[0], live=live)
         mode = self._score_mode()
         if mode is not None and self._scores_fused(z):
             # cosine / dot: logits, loss and dL/dlogit in one edge pass, dL/dz in one node pass (csrc/edge_score.hip)
             st = structure_of(graph.edge_index, z.shape[0], holder=graph, name="sim")
-            return PF.edge_score_loss(z, st, mode, labels, pos_weight, labels.shape[0])
+            return PF.edge_score_loss(z, st, mode, labels, pos_weight, labels.shape[0], live=live)
+        if live is not None:
+            # what is left takes the literal per-edge route, whose kernels and criterion count the padding as edges
+            raise NotImplementedError(
+                "a padded fixed-shape batch needs a fused training decoder (fused_decoder=True): the mlp decoder at node_dim "
+                "32, 64 or 128, or cosine / dot at a width of 16, 32, 64, 128 or 256 — and, with skip_connections, edge "
+                "weights that need no gradient")
         out = self._decode(z, graph)
         return criterion(out, labels, pos_weight), out.detach()
 

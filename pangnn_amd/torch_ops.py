@@ -11,10 +11,10 @@ registers, on the same ops,
     stored (half the bytes) with fp32 weights / accumulation / result; float16 rows are promoted to fp32 (the kernels
     have no fp16 row format); everything else runs in fp32.
 The per-step operators of the train step that read a graph (gcn_propagate, embed_conv_in[_linear], embed_propagate,
-decoder_loss, decoder_loss_z, decoder_mlp, edge_score, edge_score_loss, edge_conv and their backward ops) are C++ too since round 5 (csrc/graph_ops.cpp: schema, HIP implementation,
+decoder_loss, decoder_loss_z, decoder_mlp, edge_score, edge_score_loss, edge_score_loss_live, edge_conv and their backward ops) are C++ too since round 5 (csrc/graph_ops.cpp: schema, HIP implementation,
 autograd formula, and the structure registry they look a graph up in by the identity of its `edge_index` tensor); the second
 half of this module holds their fake kernels, the registry's build-on-miss hook and the wrappers `functional` calls with this
-package's structure objects.  edge_score, edge_score_loss and edge_conv have no other route, like linear and bce_with_logits;
+package's structure objects.  edge_score, edge_score_loss (and its padded-batch form edge_score_loss_live) and edge_conv have no other route, like linear and bce_with_logits;
 for propagate, the first-layer ops and the MLP decoder, which keep a ctypes autograd.Function twin (same kernels, same
 results), `functional.USE_DISPATCHER_OPS` chooses: PANGNN_DISPATCHER_OPS=auto: the ops only when a tracer / dispatch mode
 observes the calls, =0: never.
@@ -263,6 +263,13 @@ def _(z, edge_index, mode, y, pos_weight, denom):
     return f(), f(e), f(e), f(z.shape[0] if mode == 1 else 0, 2)
 
 
+@torch.library.register_fake("pangnn::edge_score_loss_live")
+def _(z, edge_index, mode, y, pos_weight, live):
+    f = lambda *s: z.new_empty(s, dtype=torch.float32)           # noqa: E731
+    e = edge_index.shape[1]
+    return f(), f(e), f(e), f(z.shape[0] if mode == 1 else 0, 2)
+
+
 @torch.library.register_fake("pangnn::edge_conv")
 def _(u, v, w2, b2, edge_index):
     return u.new_empty(u.shape, dtype=torch.float32), u.new_empty(u.shape, dtype=torch.int32)
@@ -332,6 +339,12 @@ def edge_score(z, st, mode):
 def edge_score_loss(z, st, mode, y, pos_weight, denom):
     _ready(st, _G.NEED_BY_DST | _G.NEED_BY_SRC)
     out = ops.edge_score_loss(z, st._key_tensor, int(mode), y, pos_weight, int(denom))
+    return out[0], out[1]
+
+
+def edge_score_loss_live(z, st, mode, y, pos_weight, live):
+    _ready(st, _G.NEED_BY_DST | _G.NEED_BY_SRC)
+    out = ops.edge_score_loss_live(z, st._key_tensor, int(mode), y, pos_weight, live)
     return out[0], out[1]
 
 

@@ -210,6 +210,12 @@ class ReplayedFreshStep(_PaddedReplay):
     point of the bit-equality test).  Results equal the unpadded fresh step (`train_step` on `ds.batch(...)`) up to fp32
     re-association: padded rows are zero rows of every sum, but the per-workgroup partial sums of the node-level kernels are
     grouped by the padded row count.
+    Served: every decoder whose fused loss kernel reads the real-edge count on the device — the mlp decoder at node_dim 64
+    (decoder16.hip's S / T pair; csrc/decoder.hip's one-pass backward under PANGNN_DECODER_PRECISION=0) and at node_dim 32 /
+    128 (csrc/decoder.hip), with or without `skip_connections`, and `cosine` / `dot` at a width of 16, 32, 64, 128 or 256
+    (csrc/edge_score.hip).  Refused (NotImplementedError from `loss_and_logits`): a non-fused route (`fused_decoder=False` /
+    "pair_add", any other width), differentiable edge weights with `skip_connections`; `--union_edge_weights` is not served
+    either (the padded buffers carry no union list).
     `stats`: a `metrics.EpochStats` (typically `capacity=0`) that the captured step ends with — the running training loss and
     the training confusion matrix of pangnn.py:218-222 with no host work per step; None: nothing changes."""
 
