@@ -142,6 +142,39 @@ int pangnn_collate_subgraphs_padded(const int64_t* edge_index, int64_t ld_e, con
                                     float* out_edge_attr, float* out_y, int64_t* out_ptr, int64_t* out_batch,
                                     float* out_x, int64_t* out_live, const pangnn_batch_orders* orders,
                                     pangnn_stream_t stream);
+/* The same two collations in the --union_edge_weights layout (dataset.py:373-381): instead of a neighbour list of its own
+ * the batch carries out_union_index[2][U] = [the batch's similarity edges | the batch's neighbour edges] and
+ * out_edge_attr[U] = [similarity weights | ones], so out_edge_attr[0 .. E) stays aligned with out_edge_index.  Everything
+ * else (out_edge_index, out_y, out_ptr, out_batch, out_x, out_live) is what the default-layout call writes.
+ * pangnn_collate_subgraphs_union: U = num_edges + num_nb; edge_attr is the data set's flat weight array.
+ * pangnn_collate_subgraphs_padded_union: U = max_edges + max_nb, union list = [real similarity edges | real neighbour edges
+ * | padding of the same kind as above, spread over the padded nodes by U - real edges], weights = [real | ones]: the
+ * first max_edges weights are the default layout's.  `orders` (nullable): both CSR orders of the similarity list with
+ * their plans, as above, and both CSR orders of the union list (rowptr / other / perm / keys; the part_* fields are ignored:
+ * only the decoder needs plans and it runs on the similarity list).  `rank` of a union order has ld_e + ld_b entries: for
+ * flat similarity edge t entry t, for flat neighbour edge t entry ld_e + t — the edge's position in the stable by-key
+ * order of ITS sub-graph's [similarity | neighbour] list.  Limits of `orders`: pangnn_collate_union_orders_supported
+ * (max_edges within pangnn_structure_small_supported, max_edges + max_nb <= 32768: the walk reads keys from global
+ * memory, so the one-workgroup sort's 16384 edges do not bound the union list). */
+int pangnn_collate_subgraphs_union(const int64_t* edge_index, int64_t ld_e, int64_t e0, int64_t num_edges,
+                                   const int64_t* nb_index, int64_t ld_b, int64_t b0, int64_t num_nb,
+                                   const float* edge_attr, const int64_t* node_off, int32_t num_graphs, int64_t n0,
+                                   int64_t num_nodes, int64_t* out_edge_index, int64_t* out_union_index,
+                                   float* out_edge_attr, int64_t* out_ptr, int64_t* out_batch, float* out_x,
+                                   pangnn_stream_t stream);
+typedef struct pangnn_union_batch_orders {
+  int32_t chunk_edges;
+  pangnn_batch_order sim_dst, sim_src, union_dst, union_src;
+} pangnn_union_batch_orders;
+int pangnn_collate_union_orders_supported(int64_t max_edges, int64_t max_nb, int64_t max_nodes);
+int pangnn_collate_subgraphs_padded_union(const int64_t* edge_index, int64_t ld_e, const int64_t* nb_index, int64_t ld_b,
+                                          const float* edge_attr, const float* y, const int64_t* node_off,
+                                          const int64_t* edge_off, const int64_t* nb_off, int64_t num_graphs_total,
+                                          const int64_t* graph_ids, int32_t max_graphs, int64_t max_edges, int64_t max_nb,
+                                          int64_t max_nodes, int64_t* out_edge_index, int64_t* out_union_index,
+                                          float* out_edge_attr, float* out_y, int64_t* out_ptr, int64_t* out_batch,
+                                          float* out_x, int64_t* out_live, const pangnn_union_batch_orders* orders,
+                                          pangnn_stream_t stream);
 /* dst[0 .. n) (device) = host_values[0 .. n), n <= 64, carried in the kernel arguments of one tiny launch: ordered with the
  * stream like any kernel and safe to call again before it ran (no pinned staging buffer to overwrite) — how the host hands
  * the next batch's sub-graph ids to a captured graph. */

@@ -30,6 +30,12 @@ SIGNATURES = {
     "pangnn_set_i64": (C.c_int, [_p, _p, _i32, _p]),
     "pangnn_collate_subgraphs": (C.c_int, [_p, _i64, _i64, _i64, _p, _i64, _i64, _i64, _p, _i32, _i64, _i64,
                                            _p, _p, _p, _p, _p, _p]),
+    # the --union_edge_weights layout of the two collations: (+ edge_attr in, the union list and its weights out)
+    "pangnn_collate_subgraphs_union": (C.c_int, [_p, _i64, _i64, _i64, _p, _i64, _i64, _i64, _p, _p, _i32, _i64, _i64,
+                                                 _p, _p, _p, _p, _p, _p, _p]),
+    "pangnn_collate_union_orders_supported": (C.c_int, [_i64, _i64, _i64]),
+    "pangnn_collate_subgraphs_padded_union": (C.c_int, [_p, _i64, _p, _i64, _p, _p, _p, _p, _p, _i64, _p, _i32, _i64, _i64,
+                                                        _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "pangnn_embed_linear_supported": (C.c_int, [_i32, _i32]),
     "pangnn_embed_linear_fwd": (C.c_int, [_p, _p, _i64, _p, _p, _p, _p, _i32, _i32, _p, _p, _i32, _p, _i64, _p]),
     "pangnn_embed_linear_bwd_workspace_bytes": (_sz, [_i32, _i32]),

@@ -323,6 +323,26 @@ extern "C" int pangnn_structure_small(const int64_t* edge_index, int64_t ld, int
 // ==============================================================================================================
 namespace pangnn {
 
+// graph pointer entry / node k of the batch (k counts the g + 1 pointer entries, then the n nodes)
+__device__ __forceinline__ void collate_ptr_or_node(int64_t k, const int64_t* __restrict__ node_off, int g, int64_t n0,
+                                                    int64_t* __restrict__ ptr, int64_t* __restrict__ batch,
+                                                    float* __restrict__ x) {
+  if (k <= g) {
+    ptr[k] = node_off[k] - n0;
+    return;
+  }
+  k -= g + 1;
+  // graph of node k: number of graph ends <= k  (torch.searchsorted(ptr[1:], k, right=True))
+  int lo = 0, hi = g;
+  const int64_t key = k + n0;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (node_off[mid + 1] <= key) lo = mid + 1; else hi = mid;
+  }
+  batch[k] = lo;
+  x[k] = 1.0f;
+}
+
 __global__ __launch_bounds__(kBlock) void collate_kernel(const int64_t* __restrict__ ei, int64_t ld_e, int64_t e0, int64_t e,
                                                          const int64_t* __restrict__ nb, int64_t ld_b, int64_t b0, int64_t b,
                                                          const int64_t* __restrict__ node_off, int g, int64_t n0, int64_t n,
@@ -344,20 +364,36 @@ __global__ __launch_bounds__(kBlock) void collate_kernel(const int64_t* __restri
       continue;
     }
     k -= 2 * b;
-    if (k <= g) {
-      ptr[k] = node_off[k] - n0;
+    collate_ptr_or_node(k, node_off, g, n0, ptr, batch, x);
+  }
+}
+
+// the same batch in the --union_edge_weights layout (dataset.py:373-381): out_un[2][e + b] = [similarity | neighbour]
+// edges, out_w[e + b] = [their weights | ones]; no neighbour list of its own
+__global__ __launch_bounds__(kBlock) void collate_union_kernel(
+    const int64_t* __restrict__ ei, int64_t ld_e, int64_t e0, int64_t e, const int64_t* __restrict__ nb, int64_t ld_b,
+    int64_t b0, int64_t b, const float* __restrict__ w, const int64_t* __restrict__ node_off, int g, int64_t n0, int64_t n,
+    int64_t* __restrict__ out_ei, int64_t* __restrict__ out_un, float* __restrict__ out_w, int64_t* __restrict__ ptr,
+    int64_t* __restrict__ batch, float* __restrict__ x) {
+  const int64_t u = e + b;
+  const int64_t total = 2 * e + 2 * u + (g + 1) + n;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < total; i += (int64_t)gridDim.x * kBlock) {
+    int64_t k = i;
+    if (k < 2 * e) {
+      const int64_t row = k >= e, col = k - row * e;
+      out_ei[k] = ei[row * ld_e + e0 + col] - n0;
       continue;
     }
-    k -= g + 1;
-    // graph of node k: number of graph ends <= k  (torch.searchsorted(ptr[1:], k, right=True))
-    int lo = 0, hi = g;
-    const int64_t key = k + n0;
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      if (node_off[mid + 1] <= key) lo = mid + 1; else hi = mid;
+    k -= 2 * e;
+    if (k < 2 * u) {
+      const int64_t row = k >= u, col = k - row * u;
+      const bool sim = col < e;
+      out_un[k] = (sim ? ei[row * ld_e + e0 + col] : nb[row * ld_b + b0 + (col - e)]) - n0;
+      if (row == 0) out_w[col] = sim ? w[e0 + col] : 1.0f;
+      continue;
     }
-    batch[k] = lo;
-    x[k] = 1.0f;
+    k -= 2 * u;
+    collate_ptr_or_node(k, node_off, g, n0, ptr, batch, x);
   }
 }
 
@@ -382,6 +418,27 @@ extern "C" int pangnn_collate_subgraphs(const int64_t* edge_index, int64_t ld_e,
   return 0;
 }
 
+extern "C" int pangnn_collate_subgraphs_union(const int64_t* edge_index, int64_t ld_e, int64_t e0, int64_t num_edges,
+                                              const int64_t* nb_index, int64_t ld_b, int64_t b0, int64_t num_nb,
+                                              const float* edge_attr, const int64_t* node_off, int32_t num_graphs, int64_t n0,
+                                              int64_t num_nodes, int64_t* out_edge_index, int64_t* out_union_index,
+                                              float* out_edge_attr, int64_t* out_ptr, int64_t* out_batch, float* out_x,
+                                              pangnn_stream_t stream) {
+  PG_CHECK_ARG(num_edges >= 0 && num_nb >= 0 && num_nodes >= 0 && num_graphs >= 0 && e0 >= 0 && b0 >= 0 &&
+                   ld_e >= e0 + num_edges && ld_b >= b0 + num_nb,
+               PANGNN_E_BADARG, "pangnn_collate_subgraphs_union: bad range");
+  PG_CHECK_ARG(node_off && out_ptr && (num_edges == 0 || (edge_index && edge_attr && out_edge_index)) &&
+                   (num_nb == 0 || nb_index) && (num_edges + num_nb == 0 || (out_union_index && out_edge_attr)) &&
+                   (num_nodes == 0 || (out_batch && out_x)),
+               PANGNN_E_BADARG, "pangnn_collate_subgraphs_union: null pointer");
+  const int64_t total = 4 * num_edges + 2 * num_nb + (num_graphs + 1) + num_nodes;
+  hipLaunchKernelGGL(collate_union_kernel, dim3(capped_grid(total, kBuildMaxBlocks)), dim3(kBlock), 0, (hipStream_t)stream,
+                     edge_index, ld_e, e0, num_edges, nb_index, ld_b, b0, num_nb, edge_attr, node_off, (int)num_graphs, n0,
+                     num_nodes, out_edge_index, out_union_index, out_edge_attr, out_ptr, out_batch, out_x);
+  PG_CHECK_LAUNCH("pangnn_collate_subgraphs_union");
+  return 0;
+}
+
 // ==============================================================================================================
 // Fixed-shape collation (round 4): the same disjoint union, of ANY list of sub-graphs (a shuffled DataLoader batch,
 // pangnn.py:152-153), written into buffers sized to the data set's maxima and padded with an inert tail, so that every
@@ -398,6 +455,13 @@ constexpr int kMaxPadGraphs = 256;
 struct BatchOrder { const int32_t* rank; int32_t* other; int32_t* perm; int32_t* keys; };
 struct BatchOrders { int enabled; BatchOrder sim_dst, sim_src, nb_dst, nb_src; };
 
+// kUnion: the --union_edge_weights layout (dataset.py:373-381) instead of a neighbour list of its own.  `out_nb` then is the
+// union list [2][max_u], max_u = max_e + max_b: [real similarity edges | real neighbour edges | padding of the same kind],
+// `out_w` has max_u entries [real weights | ones] (neighbour and padded edges both weigh 1, so its first max_e entries are
+// the default layout's), and ord.nb_dst / ord.nb_src describe the two orders of the union list: their `rank` covers
+// [flat similarity edges (ld_e) | flat neighbour edges] and counts inside the sub-graph's union, whose first sorted
+// position in the batch is ce[j] + cb[j].  Everything else is written exactly as without the flag.
+template <bool kUnion>
 __global__ __launch_bounds__(kBlock) void collate_padded_kernel(
     const int64_t* __restrict__ ei, int64_t ld_e, const int64_t* __restrict__ nb, int64_t ld_b,
     const float* __restrict__ w, const float* __restrict__ y, const int64_t* __restrict__ node_off,
@@ -458,11 +522,38 @@ __global__ __launch_bounds__(kBlock) void collate_padded_kernel(
   // once); the batch's order is the sub-graphs' orders one after the other (sub-graph j's node ids all precede those of
   // j + 1), i.e. sorted position = first edge of the sub-graph + rank.  The padding is already in order behind them.
   // Emits perm / other / keys of each order; rowptr and the run-sum plans follow from the sorted keys (order_walk_kernel).
+  [[maybe_unused]] const int64_t max_u = max_e + max_b, p_u = max_u - e_r - b_r;       // (the union list's, kUnion only)
   if (ord.enabled) {
-    const int64_t tot_o = max_e + max_b;
+    const int64_t tot_o = max_e + (kUnion ? max_u : max_b);
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < tot_o; i += (int64_t)gridDim.x * kBlock) {
       const bool sim = i < max_e;
       const int64_t col = sim ? i : i - max_e;
+      if constexpr (kUnion) {
+        if (!sim) {                  // column `col` of the union list: a similarity edge, a neighbour edge or padding
+          const BatchOrder od = ord.nb_dst, os = ord.nb_src;
+          if (col < e_r + b_r) {
+            const bool s = col < e_r;
+            const int64_t* c = s ? ce : cb;
+            const int64_t cc = s ? col : col - e_r;
+            const int j = slot(c, cc);
+            const int64_t id = gid[j];
+            const int64_t t = (s ? edge_off[id] : nb_off[id]) + (cc - c[j]);           // flat edge of its own list
+            const int64_t shift = cn[j] - node_off[id];
+            const int64_t* src_l = s ? ei : nb;
+            const int64_t ld = s ? ld_e : ld_b;
+            const int32_t sv = (int32_t)(src_l[t] + shift), dv = (int32_t)(src_l[ld + t] + shift);
+            const int64_t r = s ? t : ld_e + t, first = ce[j] + cb[j];
+            const int64_t pd = first + od.rank[r], ps = first + os.rank[r];
+            od.perm[pd] = (int32_t)col; od.other[pd] = sv; od.keys[pd] = dv;
+            os.perm[ps] = (int32_t)col; os.other[ps] = dv; os.keys[ps] = sv;
+          } else {
+            const int32_t v = (int32_t)(n_r + ((col - e_r - b_r) * n_padn) / (p_u > 0 ? p_u : 1));
+            od.perm[col] = (int32_t)col; od.other[col] = v; od.keys[col] = v;
+            os.perm[col] = (int32_t)col; os.other[col] = v; os.keys[col] = v;
+          }
+          continue;
+        }
+      }
       const int64_t real = sim ? e_r : b_r, p_l = sim ? p_e : p_b;
       const BatchOrder od = sim ? ord.sim_dst : ord.nb_dst, os = sim ? ord.sim_src : ord.nb_src;
       if (col < real) {
@@ -484,7 +575,7 @@ __global__ __launch_bounds__(kBlock) void collate_padded_kernel(
       }
     }
   }
-  const int64_t total = 2 * max_e + 2 * max_b + (max_g + 1) + max_n;
+  const int64_t total = 2 * max_e + 2 * (kUnion ? max_u : max_b) + (max_g + 1) + max_n;
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < total; i += (int64_t)gridDim.x * kBlock) {
     int64_t k = i;
     if (k < 2 * max_e) {
@@ -495,18 +586,38 @@ __global__ __launch_bounds__(kBlock) void collate_padded_kernel(
         const int64_t id = gid[j];
         v = ei[row * ld_e + edge_off[id] + (col - ce[j])] - node_off[id] + cn[j];
         if (row == 0) {
-          out_w[col] = w[edge_off[id] + (col - ce[j])];
+          if constexpr (!kUnion) out_w[col] = w[edge_off[id] + (col - ce[j])];     // (kUnion: with the union list below)
           out_y[col] = y[edge_off[id] + (col - ce[j])];
         }
       } else if (row == 0) {
-        out_w[col] = 1.0f;
+        if constexpr (!kUnion) out_w[col] = 1.0f;
         out_y[col] = 0.0f;
       }
       out_ei[k] = v;
       continue;
     }
     k -= 2 * max_e;
-    if (k < 2 * max_b) {
+    if constexpr (kUnion) {
+      if (k < 2 * max_u) {
+        const int64_t row = k >= max_u, col = k - row * max_u;
+        int64_t v = n_r + ((col - e_r - b_r) * n_padn) / (p_u > 0 ? p_u : 1);
+        float wv = 1.0f;
+        if (col < e_r) {
+          const int j = slot(ce, col);
+          const int64_t id = gid[j], t = edge_off[id] + (col - ce[j]);
+          v = ei[row * ld_e + t] - node_off[id] + cn[j];
+          if (row == 0) wv = w[t];
+        } else if (col < e_r + b_r) {
+          const int j = slot(cb, col - e_r);
+          const int64_t id = gid[j];
+          v = nb[row * ld_b + nb_off[id] + (col - e_r - cb[j])] - node_off[id] + cn[j];
+        }
+        out_nb[k] = v;
+        if (row == 0) out_w[col] = wv;
+        continue;
+      }
+      k -= 2 * max_u;
+    } else if (k < 2 * max_b) {
       const int64_t row = k >= max_b, col = k - row * max_b;
       int64_t v = n_r + ((col - b_r) * n_padn) / (p_b > 0 ? p_b : 1);
       if (col < b_r) {
@@ -517,7 +628,7 @@ __global__ __launch_bounds__(kBlock) void collate_padded_kernel(
       out_nb[k] = v;
       continue;
     }
-    k -= 2 * max_b;
+    if constexpr (!kUnion) k -= 2 * max_b;
     if (k <= max_g) {
       ptr[k] = k <= g ? cn[k] : n_r;
       continue;
@@ -604,6 +715,68 @@ __global__ void set_i64_kernel(int64_t* __restrict__ dst, I64x64 vals, int n) {
 
 }  // namespace pangnn
 
+extern "C" int pangnn_collate_union_orders_supported(int64_t max_edges, int64_t max_nb, int64_t max_nodes) {
+  return pangnn_structure_small_supported(max_edges, max_nodes) && max_nb >= 1 && max_edges + max_nb <= 2 * (int64_t)kSmallMaxEdges;
+}
+
+// both layouts of the padded collation: `second` = the neighbour list (its two orders in o[2], o[3]) or, kUnion, the union
+// list of max_edges + max_nb columns (its two orders there, no plans)
+template <bool kUnion>
+static int collate_padded_host(const char* who, const int64_t* edge_index, int64_t ld_e, const int64_t* nb_index, int64_t ld_b,
+                               const float* edge_attr, const float* y, const int64_t* node_off, const int64_t* edge_off,
+                               const int64_t* nb_off, int64_t num_graphs_total, const int64_t* graph_ids, int32_t max_graphs,
+                               int64_t max_edges, int64_t max_nb, int64_t max_nodes, int64_t* out_edge_index, int64_t* out_second,
+                               float* out_edge_attr, float* out_y, int64_t* out_ptr, int64_t* out_batch, float* out_x,
+                               int64_t* out_live, const pangnn_batch_order* const* o, int32_t chunk_edges,
+                               pangnn_stream_t stream) {
+  PG_CHECK_ARG(max_graphs >= 1 && max_graphs <= kMaxPadGraphs, PANGNN_E_BADARG, "%s: max_graphs must be in [1, %d]", who,
+               kMaxPadGraphs);
+  PG_CHECK_ARG(max_edges >= 1 && max_nb >= 1 && max_nodes >= 2 && num_graphs_total >= 0 && ld_e >= 0 && ld_b >= 0,
+               PANGNN_E_BADARG, "%s: bad size", who);
+  PG_CHECK_ARG(edge_index && nb_index && edge_attr && y && node_off && edge_off && nb_off && graph_ids && out_edge_index &&
+                   out_second && out_edge_attr && out_y && out_ptr && out_batch && out_x && out_live,
+               PANGNN_E_BADARG, "%s: null pointer", who);
+  const int64_t max_second = kUnion ? max_edges + max_nb : max_nb;
+  BatchOrders bo{};
+  if (o != nullptr) {
+    if (kUnion)
+      PG_CHECK_ARG(pangnn_collate_union_orders_supported(max_edges, max_nb, max_nodes), PANGNN_E_TOOLARGE,
+                   "%s: orders need max_edges <= %d, max_edges + max_nb <= %d and max_nodes <= %d", who, kSmallMaxEdges,
+                   2 * kSmallMaxEdges, kSmallMaxNodes);
+    else
+      PG_CHECK_ARG(pangnn_structure_small_supported(max_edges, max_nodes) && pangnn_structure_small_supported(max_nb, max_nodes),
+                   PANGNN_E_TOOLARGE, "%s: orders need max_edges, max_nb <= %d and max_nodes <= %d", who, kSmallMaxEdges,
+                   kSmallMaxNodes);
+    PG_CHECK_ARG(chunk_edges >= 32 && chunk_edges % 32 == 0, PANGNN_E_BADARG,
+                 "%s: orders->chunk_edges must be a positive multiple of 32", who);
+    BatchOrder* dst[4] = {&bo.sim_dst, &bo.sim_src, &bo.nb_dst, &bo.nb_src};
+    for (int k = 0; k < 4; ++k) {
+      PG_CHECK_ARG(o[k]->rank && o[k]->rowptr && o[k]->other && o[k]->perm && o[k]->keys, PANGNN_E_BADARG,
+                   "%s: orders: null pointer in order %d", who, k);
+      *dst[k] = BatchOrder{o[k]->rank, o[k]->other, o[k]->perm, o[k]->keys};
+    }
+    bo.enabled = 1;
+  }
+  const int64_t total = 2 * max_edges + 2 * max_second + (max_graphs + 1) + max_nodes;
+  hipLaunchKernelGGL(collate_padded_kernel<kUnion>, dim3(capped_grid(total, kBuildMaxBlocks)), dim3(kBlock), 0,
+                     (hipStream_t)stream, edge_index, ld_e, nb_index, ld_b, edge_attr, y, node_off, edge_off, nb_off, graph_ids,
+                     (int)max_graphs, num_graphs_total, max_edges, max_nb, max_nodes, out_edge_index, out_second,
+                     out_edge_attr, out_y, out_ptr, out_batch, out_x, out_live, bo);
+  PG_CHECK_LAUNCH(who);
+  if (o != nullptr) {
+    WalkOrders w{};
+    for (int k = 0; k < 4; ++k) {
+      const bool plan = !(kUnion && k >= 2);                       // the decoder runs on the similarity list only
+      w.o[k] = WalkOrder{o[k]->keys, (int)(k < 2 ? max_edges : max_second), (int)max_nodes, o[k]->rowptr,
+                         plan ? o[k]->part_off : nullptr, plan ? o[k]->part_rowptr : nullptr,
+                         plan ? o[k]->last_part : nullptr};
+    }
+    hipLaunchKernelGGL(order_walk_kernel, dim3(4), dim3(kSmallThreads), 0, (hipStream_t)stream, w, (int)chunk_edges);
+    PG_CHECK_LAUNCH(who);
+  }
+  return 0;
+}
+
 extern "C" int pangnn_collate_subgraphs_padded(const int64_t* edge_index, int64_t ld_e, const int64_t* nb_index,
                                                int64_t ld_b, const float* edge_attr, const float* y,
                                                const int64_t* node_off, const int64_t* edge_off, const int64_t* nb_off,
@@ -613,46 +786,29 @@ extern "C" int pangnn_collate_subgraphs_padded(const int64_t* edge_index, int64_
                                                float* out_y, int64_t* out_ptr, int64_t* out_batch, float* out_x,
                                                int64_t* out_live, const pangnn_batch_orders* orders,
                                                pangnn_stream_t stream) {
-  const char* who = "pangnn_collate_subgraphs_padded";
-  PG_CHECK_ARG(max_graphs >= 1 && max_graphs <= kMaxPadGraphs, PANGNN_E_BADARG, "%s: max_graphs must be in [1, %d]", who,
-               kMaxPadGraphs);
-  PG_CHECK_ARG(max_edges >= 1 && max_nb >= 1 && max_nodes >= 2 && num_graphs_total >= 0 && ld_e >= 0 && ld_b >= 0,
-               PANGNN_E_BADARG, "%s: bad size", who);
-  PG_CHECK_ARG(edge_index && nb_index && edge_attr && y && node_off && edge_off && nb_off && graph_ids && out_edge_index &&
-                   out_nb_index && out_edge_attr && out_y && out_ptr && out_batch && out_x && out_live,
-               PANGNN_E_BADARG, "%s: null pointer", who);
-  BatchOrders bo{};
-  if (orders != nullptr) {
-    PG_CHECK_ARG(pangnn_structure_small_supported(max_edges, max_nodes) && pangnn_structure_small_supported(max_nb, max_nodes),
-                 PANGNN_E_TOOLARGE, "%s: orders need max_edges, max_nb <= %d and max_nodes <= %d", who, kSmallMaxEdges,
-                 kSmallMaxNodes);
-    PG_CHECK_ARG(orders->chunk_edges >= 32 && orders->chunk_edges % 32 == 0, PANGNN_E_BADARG,
-                 "%s: orders->chunk_edges must be a positive multiple of 32", who);
-    const pangnn_batch_order* src[4] = {&orders->sim_dst, &orders->sim_src, &orders->nb_dst, &orders->nb_src};
-    BatchOrder* dst[4] = {&bo.sim_dst, &bo.sim_src, &bo.nb_dst, &bo.nb_src};
-    for (int k = 0; k < 4; ++k) {
-      PG_CHECK_ARG(src[k]->rank && src[k]->rowptr && src[k]->other && src[k]->perm && src[k]->keys, PANGNN_E_BADARG,
-                   "%s: orders: null pointer in order %d", who, k);
-      *dst[k] = BatchOrder{src[k]->rank, src[k]->other, src[k]->perm, src[k]->keys};
-    }
-    bo.enabled = 1;
-  }
-  const int64_t total = 2 * max_edges + 2 * max_nb + (max_graphs + 1) + max_nodes;
-  hipLaunchKernelGGL(collate_padded_kernel, dim3(capped_grid(total, kBuildMaxBlocks)), dim3(kBlock), 0,
-                     (hipStream_t)stream, edge_index, ld_e, nb_index, ld_b, edge_attr, y, node_off, edge_off, nb_off, graph_ids,
-                     (int)max_graphs, num_graphs_total, max_edges, max_nb, max_nodes, out_edge_index, out_nb_index,
-                     out_edge_attr, out_y, out_ptr, out_batch, out_x, out_live, bo);
-  PG_CHECK_LAUNCH(who);
-  if (orders != nullptr) {
-    WalkOrders w{};
-    const pangnn_batch_order* src[4] = {&orders->sim_dst, &orders->sim_src, &orders->nb_dst, &orders->nb_src};
-    for (int k = 0; k < 4; ++k)
-      w.o[k] = WalkOrder{src[k]->keys, (int)(k < 2 ? max_edges : max_nb), (int)max_nodes, src[k]->rowptr, src[k]->part_off,
-                         src[k]->part_rowptr, src[k]->last_part};
-    hipLaunchKernelGGL(order_walk_kernel, dim3(4), dim3(kSmallThreads), 0, (hipStream_t)stream, w, (int)orders->chunk_edges);
-    PG_CHECK_LAUNCH(who);
-  }
-  return 0;
+  const pangnn_batch_order* o[4] = {nullptr, nullptr, nullptr, nullptr};
+  if (orders != nullptr) { o[0] = &orders->sim_dst; o[1] = &orders->sim_src; o[2] = &orders->nb_dst; o[3] = &orders->nb_src; }
+  return collate_padded_host<false>("pangnn_collate_subgraphs_padded", edge_index, ld_e, nb_index, ld_b, edge_attr, y, node_off,
+                                    edge_off, nb_off, num_graphs_total, graph_ids, max_graphs, max_edges, max_nb, max_nodes,
+                                    out_edge_index, out_nb_index, out_edge_attr, out_y, out_ptr, out_batch, out_x, out_live,
+                                    orders != nullptr ? o : nullptr, orders != nullptr ? orders->chunk_edges : 0, stream);
+}
+
+extern "C" int pangnn_collate_subgraphs_padded_union(const int64_t* edge_index, int64_t ld_e, const int64_t* nb_index,
+                                                     int64_t ld_b, const float* edge_attr, const float* y,
+                                                     const int64_t* node_off, const int64_t* edge_off, const int64_t* nb_off,
+                                                     int64_t num_graphs_total, const int64_t* graph_ids, int32_t max_graphs,
+                                                     int64_t max_edges, int64_t max_nb, int64_t max_nodes,
+                                                     int64_t* out_edge_index, int64_t* out_union_index, float* out_edge_attr,
+                                                     float* out_y, int64_t* out_ptr, int64_t* out_batch, float* out_x,
+                                                     int64_t* out_live, const pangnn_union_batch_orders* orders,
+                                                     pangnn_stream_t stream) {
+  const pangnn_batch_order* o[4] = {nullptr, nullptr, nullptr, nullptr};
+  if (orders != nullptr) { o[0] = &orders->sim_dst; o[1] = &orders->sim_src; o[2] = &orders->union_dst; o[3] = &orders->union_src; }
+  return collate_padded_host<true>("pangnn_collate_subgraphs_padded_union", edge_index, ld_e, nb_index, ld_b, edge_attr, y,
+                                   node_off, edge_off, nb_off, num_graphs_total, graph_ids, max_graphs, max_edges, max_nb,
+                                   max_nodes, out_edge_index, out_union_index, out_edge_attr, out_y, out_ptr, out_batch, out_x,
+                                   out_live, orders != nullptr ? o : nullptr, orders != nullptr ? orders->chunk_edges : 0, stream);
 }
 
 extern "C" int pangnn_set_i64(int64_t* dst, const int64_t* host_values, int32_t n, pangnn_stream_t stream) {

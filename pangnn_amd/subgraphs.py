@@ -58,6 +58,12 @@ class BatchOrders(ctypes.Structure):
                 ("nb_src", BatchOrder)]
 
 
+# pangnn_union_batch_orders (pangnn_collate_subgraphs_padded_union): the union list's two orders in place of the neighbour list's
+class UnionBatchOrders(ctypes.Structure):
+    _fields_ = [("chunk_edges", ctypes.c_int32), ("sim_dst", BatchOrder), ("sim_src", BatchOrder), ("union_dst", BatchOrder),
+                ("union_src", BatchOrder)]
+
+
 def _unique_sorted(keys: torch.Tensor) -> torch.Tensor:
     return torch.unique(keys)          # sorted ascending, duplicates dropped
 
@@ -215,6 +221,26 @@ class SubGraphDataset:
     def __len__(self):
         return self.num_graphs
 
+    @staticmethod
+    def _default_layout(i, gr):
+        """sub-graph `i` of a list in the layout the flat data set stores.  A --union_edge_weights sub-graph (src/dataset.py:
+        287-302: `union_edge_index` = [neighbour | similarity] edges, `edge_attr` = [1 per neighbour edge | similarity
+        weights], no `neighbour_edge_index`) is split back into its two lists; anything else is returned as it is."""
+        if not hasattr(gr, "union_edge_index") or hasattr(gr, "neighbour_edge_index"):
+            return gr
+        un, ei, w = gr.union_edge_index, gr.edge_index, gr.edge_attr
+        if un.dim() != 2 or un.shape[0] != 2 or ei.dim() != 2 or ei.shape[0] != 2:
+            raise ValueError(f"sub-graph {i}: union_edge_index / edge_index must be [2, E]")
+        u, e = int(un.shape[1]), int(ei.shape[1])
+        if u < e or w.shape[0] != u:
+            raise ValueError(f"sub-graph {i}: a union sub-graph needs one weight per union edge and its similarity edges "
+                             f"inside the union ({u} union edges, {e} similarity edges, {w.shape[0]} weights)")
+        if not torch.equal(un[:, u - e:], ei):
+            raise ValueError(f"sub-graph {i}: the last {e} union edges are not edge_index")
+        if not bool((w[:u - e] == 1).all()):
+            raise ValueError(f"sub-graph {i}: the weights of the {u - e} neighbour edges in front are not all 1")
+        return SimpleNamespace(x=gr.x, edge_index=ei, neighbour_edge_index=un[:, :u - e], edge_attr=w[u - e:], y=gr.y)
+
     @classmethod
     def from_data_list(cls, graphs, device=None) -> "SubGraphDataset":
         """The flat data set of a LIST of per-group sub-graphs as the reference builds them (`UnionGraphDataset`'s
@@ -223,21 +249,20 @@ class SubGraphDataset:
         the reference's own sub-graphs train through `batch()`, `train.GraphedTrainStep` and `train.ReplayedFreshStep`
         (one captured HIP graph for every shuffled mini-batch) without going through this package's graph construction.
         Edge order inside a sub-graph is kept (PyG's `Batch.from_data_list` keeps it too: logits come back in that order);
-        one host -> device copy per tensor kind, once per data set."""
+        one host -> device copy per tensor kind, once per data set.
+        --union_edge_weights sub-graphs (`union_edge_index`, no `neighbour_edge_index`) are accepted too and stored in the
+        same default layout (`_default_layout`): union batches are derived at collation, `batch(..., union=True)`."""
         graphs = list(graphs)
         if not graphs:
             raise ValueError("from_data_list needs at least one sub-graph")
         if device is None:
             device = graphs[0].edge_index.device
+        graphs = [cls._default_layout(i, gr) for i, gr in enumerate(graphs)]
         for i, gr in enumerate(graphs):
             n = int(gr.x.shape[0])
             ei, nb = gr.edge_index, gr.neighbour_edge_index
             if ei.dim() != 2 or ei.shape[0] != 2 or nb.dim() != 2 or nb.shape[0] != 2:
                 raise ValueError(f"sub-graph {i}: edge_index / neighbour_edge_index must be [2, E]")
-            if hasattr(gr, "union_edge_index") and not hasattr(gr, "neighbour_edge_index"):
-                raise ValueError(f"sub-graph {i} is a --union_edge_weights sub-graph (src/dataset.py:286-299: union_edge_index, "
-                                 f"edge_attr = [1 per neighbour edge | similarity weights]); the flat data set holds the default "
-                                 f"layout (edge_index + neighbour_edge_index, one weight per similarity edge)")
             if gr.edge_attr.shape[0] != ei.shape[1] or gr.y.shape[0] != ei.shape[1]:
                 # (a longer edge_attr is the union layout, whose similarity weights are the LAST e entries: never slice it)
                 raise ValueError(f"sub-graph {i}: edge_attr has {gr.edge_attr.shape[0]} and y {gr.y.shape[0]} entries for "
@@ -274,7 +299,10 @@ class SubGraphDataset:
                 sorted_by_src=bool((src[1:] >= src[:-1]).all()) if src.numel() > 1 else True)
         return h
 
-    def batch(self, i0: int, i1: int):
+    def batch(self, i0: int, i1: int, union: bool = False):
+        """`union`: the --union_edge_weights layout (dataset.py:373-381) — `union_edge_index` = [the batch's similarity edges |
+        its neighbour edges], `edge_attr` = [similarity weights | ones] (so `edge_attr[:E]` are the weights of `edge_index`),
+        no `neighbour_edge_index`; `edge_index`, `y` and everything else as in the default layout."""
         i1 = min(i1, self.num_graphs)
         h = self._host()
         n0, n1 = h.node[i0], h.node[i1]
@@ -282,6 +310,8 @@ class SubGraphDataset:
         b0, b1 = h.nb[i0], h.nb[i1]
         dev = self.edge_index.device
         ptr = self.node_off[i0:i1 + 1] - n0
+        if union:
+            return self._union_batch(i0, i1, n0, n1, e0, e1, b0, b1, ptr)
         # what this producer knows about the batch (graph.EdgeStructure hints): ids are local and in range by
         # construction; a slice of a source-sorted flat list shifted by a constant is source-sorted
         hints = {"sim": {"valid_ids": True, "sorted_by_src": h.sorted_by_src}, "nb": {"valid_ids": True}}
@@ -312,6 +342,43 @@ class SubGraphDataset:
             ptr=ptr, num_graphs=i1 - i0,
             # graph id of every node: position of the node among the graphs' end offsets (no data-dependent output size)
             batch=torch.searchsorted(ptr[1:].contiguous(), torch.arange(n1 - n0, device=dev), right=True))
+
+    def _union_batch(self, i0, i1, n0, n1, e0, e1, b0, b1, ptr):
+        """`batch(i0, i1, union=True)`: one launch on a device-resident set (pangnn_collate_subgraphs_union), index ops on a
+        CPU-resident one"""
+        dev = self.edge_index.device
+        n, e, b, g = n1 - n0, e1 - e0, b1 - b0, i1 - i0
+        hints = {"sim": {"valid_ids": True, "sorted_by_src": self._host().sorted_by_src},
+                 "union": {"valid_ids": True, "band_width": 0}}
+        if dev.type == "cuda" and COLLATE_KERNEL:
+            lib = _lib.load()
+            buf = torch.empty(2 * e + 2 * (e + b) + (g + 1) + n, dtype=torch.int64, device=dev)
+            x = torch.empty(n, 1, dtype=torch.float32, device=dev)
+            w = torch.empty(e + b, dtype=torch.float32, device=dev)
+            ei, un = buf[:2 * e].view(2, e), buf[2 * e:4 * e + 2 * b].view(2, e + b)
+            ptr, bid = buf[4 * e + 2 * b:4 * e + 2 * b + g + 1], buf[4 * e + 2 * b + g + 1:]
+            src_ei, src_nb = self.edge_index, self.neighbour_edge_index
+            if not (src_ei.is_contiguous() and src_nb.is_contiguous() and self.node_off.is_contiguous()
+                    and self.edge_attr.is_contiguous()):
+                raise ValueError("SubGraphDataset tensors must be contiguous")
+            if self.edge_attr.dtype != torch.float32:
+                raise ValueError("edge_attr must be float32")
+            with _lib.device_guard(dev):
+                _lib.check(lib.pangnn_collate_subgraphs_union(
+                    src_ei.data_ptr(), src_ei.shape[1], e0, e, src_nb.data_ptr(), src_nb.shape[1], b0, b,
+                    self.edge_attr.data_ptr(), self.node_off.data_ptr() + 8 * i0, g, n0, n, _lib.ptr(ei), _lib.ptr(un),
+                    _lib.ptr(w), ptr.data_ptr(), _lib.ptr(bid), _lib.ptr(x), _lib.stream_ptr()),
+                    "pangnn_collate_subgraphs_union")
+            return SimpleNamespace(_pangnn_hints=hints, x=x, edge_index=ei, edge_attr=w, y=self.y[e0:e1],
+                                   union_edge_index=un, ptr=ptr, num_graphs=g, batch=bid)
+        ei = (self.edge_index[:, e0:e1] - n0).contiguous()
+        return SimpleNamespace(
+            _pangnn_hints=hints, x=torch.ones(n, 1, dtype=torch.float32, device=dev), edge_index=ei,
+            edge_attr=torch.cat([self.edge_attr[e0:e1], torch.ones(b, dtype=self.edge_attr.dtype, device=dev)]),
+            y=self.y[e0:e1].contiguous(),
+            union_edge_index=torch.cat([ei, self.neighbour_edge_index[:, b0:b1] - n0], dim=1),
+            ptr=ptr, num_graphs=g,
+            batch=torch.searchsorted(ptr[1:].contiguous(), torch.arange(n, device=dev), right=True))
 
     def graph(self, i: int):
         return self.batch(i, i + 1)
@@ -347,10 +414,12 @@ class SubGraphDataset:
         n, e, b = self._counts(ids)
         return len(ids) <= spec.graphs and n < spec.nodes and e <= spec.edges and b <= spec.nb_edges
 
-    def structure_index(self):
+    def structure_index(self, union: bool = False):
         """per flat edge of both lists: its position inside its own sub-graph in the by-target and in the by-source order
         (int32; stable — equal keys keep list order).  A property of the data set, computed once with two stable sorts per
-        list; with it a batch's CSR orders are written without any sort (pangnn_collate_subgraphs_padded, `orders`)."""
+        list; with it a batch's CSR orders are written without any sort (pangnn_collate_subgraphs_padded, `orders`).
+        `union`: also `union_dst` / `union_src` [E + B] — entry t for flat similarity edge t, entry E + t for flat neighbour
+        edge t: the edge's position in either order of its sub-graph's union list (pangnn_collate_subgraphs_padded_union)."""
         idx = self.__dict__.get("_structure_index")
         if idx is None:
             dev = self.edge_index.device
@@ -372,9 +441,25 @@ class SubGraphDataset:
             sd, ss = ranks(self.edge_index, self.edge_off)
             nd, ns = ranks(self.neighbour_edge_index, self.nb_off)
             idx = self._structure_index = SimpleNamespace(sim_dst=sd, sim_src=ss, nb_dst=nd, nb_src=ns)
+        if union and not hasattr(idx, "union_dst"):
+            # the same for the --union_edge_weights list of a sub-graph, [its similarity edges | its neighbour edges]: one
+            # stable sort per order over [flat similarity | flat neighbour] keyed by the node id — at equal keys similarity
+            # edges come first, each kind in list order: the tie order of a stable sort of a batch's union list
+            dev = self.edge_index.device
+            both = torch.cat([self.edge_index, self.neighbour_edge_index], dim=1)
+            cnt_e, cnt_b = self.edge_off[1:] - self.edge_off[:-1], self.nb_off[1:] - self.nb_off[:-1]
+            gids = torch.arange(self.num_graphs, device=dev)
+            gid = torch.cat([torch.repeat_interleave(gids, cnt_e), torch.repeat_interleave(gids, cnt_b)])
+            first = (self.edge_off[:-1] + self.nb_off[:-1])[gid]
+            pos = torch.arange(both.shape[1], device=dev)
+            for name, row in (("union_dst", 1), ("union_src", 0)):
+                order = torch.argsort(both[row], stable=True)
+                r = torch.empty_like(pos)
+                r[order] = pos
+                setattr(idx, name, (r - first).to(torch.int32).contiguous())
         return idx
 
-    def padded_buffers(self, spec, orders: bool = True):
+    def padded_buffers(self, spec, orders: bool = True, union: bool = False):
         """the fixed buffers of a padded batch + the device list of sub-graph ids it is collated from.  `orders`: also the
         buffers of both CSR orders (and the decoder's run-sum plans) of both edge lists, written by the collation itself —
         no per-batch sort (`structure_index`); False, or shapes beyond the small-structure limits: built per batch by
@@ -382,41 +467,54 @@ class SubGraphDataset:
         Layout facts a consumer of the PyG-like fields needs: `ptr` has spec.graphs + 1 entries (entries past the real graphs
         repeat the real node count); `batch` gives a PADDED node the id of a dedicated padding segment — the number of real
         graphs of the current batch, which for a full batch equals spec.graphs — so per-graph pooling over `batch` must be sized
-        `num_graphs` = spec.graphs + 1 (what this buffer reports), and its last used row is the padding's."""
+        `num_graphs` = spec.graphs + 1 (what this buffer reports), and its last used row is the padding's.
+        `union`: the --union_edge_weights layout — no `neighbour_edge_index` but `union_edge_index` [2, U], U = spec.edges +
+        spec.nb_edges: [real similarity edges | real neighbour edges | padding of the same kind], and `edge_attr` [U] = [real
+        weights | ones], whose first spec.edges entries are the default layout's.  Its orders are those of the similarity list
+        (with plans) and of the union list (none: the decoder runs on the similarity list); they are collation-written up to
+        U = 32768 (pangnn_collate_union_orders_supported)."""
         spec = PaddedSpec(*spec)
         g, n, e, b = spec
         dev = self.edge_index.device
-        ei, nb, ptr, bid, live, ids = carve(torch.int64, dev, [2 * e, 2 * b, g + 1, n, 8, g])
+        u = e + b if union else b                         # columns of the second list: the union list / the neighbour list
+        ei, nb, ptr, bid, live, ids = carve(torch.int64, dev, [2 * e, 2 * u, g + 1, n, 8, g])
         ids.fill_(-1)
         live.zero_()
-        w, y, x = carve(torch.float32, dev, [e, e, n])
+        w, y, x = carve(torch.float32, dev, [u if union else e, e, n])
         hints = {"sim": {"valid_ids": True, "sorted_by_src": self._host().sorted_by_src, "band_width": 0},
-                 "nb": {"valid_ids": True, "band_width": 0}}
+                 "union" if union else "nb": {"valid_ids": True, "band_width": 0}}
         buf = SimpleNamespace(_pangnn_hints=hints, x=x.view(n, 1), edge_index=ei.view(2, e), edge_attr=w, y=y,
-                              neighbour_edge_index=nb.view(2, b), ptr=ptr, batch=bid, live=live, live_edges=live[:1],
-                              graph_ids=ids, spec=spec, num_graphs=g + 1, orders=None)
+                              ptr=ptr, batch=bid, live=live, live_edges=live[:1],
+                              graph_ids=ids, spec=spec, num_graphs=g + 1, orders=None, union=bool(union))
+        setattr(buf, "union_edge_index" if union else "neighbour_edge_index", nb.view(2, u))
         lib = _lib.load()
-        if orders and dev.type == "cuda" and lib.pangnn_structure_small_supported(e, n) \
-                and lib.pangnn_structure_small_supported(b, n):
+        if not orders or dev.type != "cuda":
+            return buf
+        if union:
+            if lib.pangnn_collate_union_orders_supported(e, b, n):
+                buf.orders = self._order_buffers(n, e, b, dev, union=True)
+        elif lib.pangnn_structure_small_supported(e, n) and lib.pangnn_structure_small_supported(b, n):
             buf.orders = self._order_buffers(n, e, b, dev)
         return buf
 
-    def _order_buffers(self, n, e, b, dev):
-        """device tables of the four CSR orders of a padded batch + the ctypes descriptor the collation takes"""
+    def _order_buffers(self, n, e, b, dev, union: bool = False):
+        """device tables of the four CSR orders of a padded batch + the ctypes descriptor the collation takes (`union`: the
+        second list is the union list of e + b columns)"""
         ct = chunk_tiles_for(e)
         nc = n_chunks(e, ct)
-        rk = self.structure_index()
+        rk = self.structure_index(union=union)
+        second, b = ("union", e + b) if union else ("nb", b)
         # order after order: other, perm, keys (+ part_off: the similarity list's plans) | rowptr (+ part_rowptr); behind
         # them each plan's last_part, in a 16-byte slot of its own
         i32 = iter(carve(torch.int32, dev, [e, e, e, nc] * 2 + [b] * 6))
         i64 = iter(carve(torch.int64, dev, [n + 1] * 6 + [1, 1]))
         seg = {}
-        for name in ("sim_dst", "sim_src", "nb_dst", "nb_src"):
+        for name in ("sim_dst", "sim_src", second + "_dst", second + "_src"):
             t = seg[name] = {"other": next(i32), "perm": next(i32), "keys": next(i32), "rowptr": next(i64)}
             if name.startswith("sim"):
                 t["part_off"], t["part_rowptr"] = next(i32), next(i64)
         seg["sim_dst"]["last_part"], seg["sim_src"]["last_part"] = i64
-        desc = BatchOrders(chunk_edges=32 * ct)
+        desc = (UnionBatchOrders if union else BatchOrders)(chunk_edges=32 * ct)
         for name, t in seg.items():
             o = getattr(desc, name)
             o.rank = getattr(rk, name).data_ptr()
@@ -429,7 +527,8 @@ class SubGraphDataset:
         spec, ct = buf.spec, buf.orders.chunk_tiles
         n_bound = part_bound(spec.nodes, spec.edges, ct)
         out = {}
-        for name, ei in (("sim", buf.edge_index), ("nb", buf.neighbour_edge_index)):
+        second = ("union", buf.union_edge_index) if buf.union else ("nb", buf.neighbour_edge_index)
+        for name, ei in (("sim", buf.edge_index), second):
             td, ts = buf.orders.tables[name + "_dst"], buf.orders.tables[name + "_src"]
             plans = None if name != "sim" else {
                 (by, ct): RunPlan(n_bound, t["part_off"], t["part_rowptr"], t["keys"], ct, t["last_part"])
@@ -451,18 +550,21 @@ class SubGraphDataset:
             raise ValueError("SubGraphDataset tensors must be contiguous")
         if self.edge_attr.dtype != torch.float32 or self.y.dtype != torch.float32:
             raise ValueError("edge_attr / y must be float32")
+        # (a union batch: the same arguments, the union list where the neighbour list goes and edge_attr of its length)
+        union = getattr(buf, "union", False)
+        entry = "pangnn_collate_subgraphs_padded_union" if union else "pangnn_collate_subgraphs_padded"
+        second = buf.union_edge_index if union else buf.neighbour_edge_index
         with _lib.device_guard(src_ei.device):
-            _lib.check(lib.pangnn_collate_subgraphs_padded(
+            _lib.check(getattr(lib, entry)(
                 src_ei.data_ptr(), src_ei.shape[1], src_nb.data_ptr(), src_nb.shape[1], self.edge_attr.data_ptr(),
                 self.y.data_ptr(), self.node_off.data_ptr(), self.edge_off.data_ptr(), self.nb_off.data_ptr(),
                 self.num_graphs, buf.graph_ids.data_ptr(), g, e, b, n, buf.edge_index.data_ptr(),
-                buf.neighbour_edge_index.data_ptr(), buf.edge_attr.data_ptr(), buf.y.data_ptr(), buf.ptr.data_ptr(),
+                second.data_ptr(), buf.edge_attr.data_ptr(), buf.y.data_ptr(), buf.ptr.data_ptr(),
                 buf.batch.data_ptr(), buf.x.data_ptr(), buf.live.data_ptr(),
-                None if buf.orders is None else ctypes.byref(buf.orders.desc), _lib.stream_ptr()),
-                "pangnn_collate_subgraphs_padded")
+                None if buf.orders is None else ctypes.byref(buf.orders.desc), _lib.stream_ptr()), entry)
         # what is cached on the batch object belongs to the previous content of the buffers (same addresses): replace it
         # by the structures over the tables this collation wrote, or drop it (built on first use as for any batch)
-        for ei in (buf.edge_index, buf.neighbour_edge_index):        # only THIS batch's entries of the identity-keyed cache
+        for ei in (buf.edge_index, second):        # only THIS batch's entries of the identity-keyed cache
             forget(structure_key(ei, n), ei)
         if buf.orders is None:
             buf.__dict__.pop("_pangnn_structs", None)

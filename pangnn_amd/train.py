@@ -128,10 +128,13 @@ class _PaddedReplay:
     (everyday ones of `slack` x the mean batch, worst-case ones built on first use), the step `self._step(buf)` captured into
     one HIP graph per set of buffers, and the choice of the set a batch fits.  A subclass states `_step(buf)` (one padded
     step, no host read-back; returns a tuple of tensors) and `_kept()`: the tensors a step changes that building a slot must
-    leave as they were (the warm-up steps before capture run for real)."""
+    leave as they were (the warm-up steps before capture run for real).  It sets `self.model` before `_init_slots`: the model's
+    `union_edge_weights` flag selects the layout of the buffers (`SubGraphDataset.padded_buffers(union=)`)."""
 
     def _init_slots(self, ds, batch_size, graphs, capture, warmup, slack):
         self.ds, self.capture, self.warmup = ds, bool(capture), int(warmup)
+        # a --union_edge_weights model reads `union_edge_index` and its weights: the buffers are collated in that layout
+        self.union = bool(getattr(getattr(self.model, "flags", None), "union_edge_weights", False))
         self._first = list(range(min(batch_size, ds.num_graphs))) if graphs is None else [int(i) for i in list(graphs)[:batch_size]]
         worst = ds.padded_spec(batch_size, graphs)
         tight = worst if slack is None else ds.padded_spec(batch_size, graphs, slack)
@@ -153,7 +156,7 @@ class _PaddedReplay:
         if hit is not None:
             return hit
         ds = self.ds
-        buf = ds.padded_buffers(spec)
+        buf = ds.padded_buffers(spec, union=self.union)
         first = [i for i in self._first]
         while len(first) > 1 and not ds.fits(spec, first):
             first.pop()
@@ -214,8 +217,12 @@ class ReplayedFreshStep(_PaddedReplay):
     (decoder16.hip's S / T pair; csrc/decoder.hip's one-pass backward under PANGNN_DECODER_PRECISION=0) and at node_dim 32 /
     128 (csrc/decoder.hip), with or without `skip_connections`, and `cosine` / `dot` at a width of 16, 32, 64, 128 or 256
     (csrc/edge_score.hip).  Refused (NotImplementedError from `loss_and_logits`): a non-fused route (`fused_decoder=False` /
-    "pair_add", any other width), differentiable edge weights with `skip_connections`; `--union_edge_weights` is not served
-    either (the padded buffers carry no union list).
+    "pair_add", any other width), differentiable edge weights with `skip_connections`.
+    `--union_edge_weights` models are served with the same decoders: their buffers carry `union_edge_index` [2, spec.edges +
+    spec.nb_edges] and its weights [real | ones] in place of the neighbour list, both CSR orders of the union list written by
+    the same collation launch (`pangnn_collate_subgraphs_padded_union`); the decoder reads `edge_index`, `live_edges` and the
+    similarity list's plans exactly as for any other model, and `skip_connections` reads `edge_attr[:spec.edges]`, the
+    weights of `edge_index`.
     `stats`: a `metrics.EpochStats` (typically `capacity=0`) that the captured step ends with — the running training loss and
     the training confusion matrix of pangnn.py:218-222 with no host work per step; None: nothing changes."""
 
@@ -281,8 +288,8 @@ class ReplayedFreshEval(_PaddedReplay):
     `out` are plain logits of all max_edges entries; those of the padded tail are whatever the decoder computes for the inert
     self loops and are never read (`metrics.EpochStats` takes the number of real edges from device memory).  So every decoder
     and width `model(buf)` supports in eval mode is served — `mlp` at any node_dim, `cosine`, `dot`, with or without
-    `skip_connections` / `base_model` — wider than the training replay; `--union_edge_weights` is not (the padded buffers carry
-    no union list).  Per batch the host does one id write and one graph launch; loss, confusion counts and the scores the
+    `skip_connections` / `base_model` / `union_edge_weights` (buffers in the union layout, as for the training replay) — wider
+    than the training replay.  Per batch the host does one id write and one graph launch; loss, confusion counts and the scores the
     ranking metrics need accumulate in `self.stats`, read out once by `compute()`.
     `ranking`: keep scores and labels for ROC-AUC / PR-AUC; the capacity is the edge total of `graphs` (default: all), i.e. one
     pass over that validation set between two `reset()`s.  `capture=False` runs the very same padded step eagerly.
@@ -292,8 +299,6 @@ class ReplayedFreshEval(_PaddedReplay):
     def __init__(self, model, ds, pos_weight, batch_size: int = 32, graphs=None, capture: bool = True, warmup: int = 1,
                  slack: float = 1.4, threshold: float = 0.5, ranking: bool = True):
         from .metrics import EpochStats
-        if getattr(getattr(model, "flags", None), "union_edge_weights", False):
-            raise NotImplementedError("ReplayedFreshEval: a padded batch carries no union edge list (--union_edge_weights)")
         dev = ds.edge_index.device
         if pos_weight is not None:       # the device scalar the captured launch reads: made once, never inside the capture
             pos_weight = torch.as_tensor(pos_weight).detach().to(device=dev, dtype=torch.float32).reshape(-1)[:1]
