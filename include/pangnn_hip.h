@@ -1036,6 +1036,43 @@ int    pangnn_qscore_bwd(const int64_t* rowptr, const int32_t* item, const void*
                          int32_t g_dtype, const double* lse, int64_t num_segments, int64_t num_edges, const double* t,
                          double epsilon, void* gscore, double* gt, double* t_parts, pangnn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The induced similarity edges of per-group sub-graphs (csrc/induced_edges.hip; pangnn_amd/subgraphs.py, step 3 of
+ * build_subgraphs, whose index-op form _induced_edges_index_ops is the definition).  All tables are int64.
+ *   rowptr [num_nodes + 1], dst [num_edges]: the relation grouped by source, targets in [0, num_nodes);
+ *   row_node [num_rows]: the global node of every row, rows in (group, local id) order;
+ *   group_off [num_groups + 1]: group g owns rows [group_off[g], group_off[g + 1]) (group_off[0] = 0, non-decreasing,
+ *     group_off[num_groups] = num_rows; a group may be empty); the local id of row r of group g is r - group_off[g];
+ *   sorted_node / sorted_local [num_rows]: over the same ranges, each group's node ids ascending and their local ids.
+ * For every row r (group g, node v, local id l) and every position p in [rowptr[v], rowptr[v + 1]), ascending: if dst[p]
+ * is a node of group g with local id m, the triple (l, m, p) is emitted.  Output order: rows in row order, positions
+ * ascending inside a row — the inputs alone fix every output address (no atomics: two calls give the same bytes), and
+ * duplicate (src, dst) entries of the relation are each emitted.  Nothing proportional to the number of positions walked
+ * is stored.
+ *
+ * pangnn_induced_edges_count: row_off [num_rows + 1] = exclusive scan of the rows' hit counts, row_off[num_rows] = the
+ *   total (read it back to size the outputs).  One memset, one launch and one rocPRIM scan on `stream`.
+ * pangnn_induced_edges_fill: the same walk on the same inputs; out_src / out_dst / out_pos [total] = l / m / p of every hit,
+ *   written at row_off[r] + its rank inside the row (a triple that would land at or past `total` is not written).
+ *   total == 0 launches nothing.
+ * Both only enqueue; neither allocates.  `scratch`: pangnn_induced_edges_scratch_bytes(num_rows) bytes, 16-byte aligned (0
+ * from the query: num_rows out of range, or failure — it asks rocPRIM for the scan's temporary size, which needs a device);
+ * NULL or smaller: PANGNN_E_WORKSPACE.  Negative sizes, rows without groups or nodes, a NULL table with num_rows > 0 (dst:
+ * and num_edges > 0), a NULL output with total > 0: PANGNN_E_BADARG.  num_nodes >= 2^31 (node ids are held as 32-bit words on
+ * chip), num_rows or num_groups >= 2^40: PANGNN_E_TOOLARGE; positions and output addresses are 64-bit, num_edges is not
+ * bounded.  A group of any size and a row of any length are handled (a group's ids are staged on chip up to 6144 of them,
+ * searched in place beyond).
+ * ---------------------------------------------------------------------------------------- */
+int64_t pangnn_induced_edges_scratch_bytes(int64_t num_rows);
+int    pangnn_induced_edges_count(const int64_t* rowptr, const int64_t* dst, int64_t num_nodes, int64_t num_edges,
+                                  const int64_t* row_node, int64_t num_rows, const int64_t* group_off, int64_t num_groups,
+                                  const int64_t* sorted_node, const int64_t* sorted_local, int64_t* row_off, void* scratch,
+                                  int64_t scratch_bytes, pangnn_stream_t stream);
+int    pangnn_induced_edges_fill(const int64_t* rowptr, const int64_t* dst, int64_t num_nodes, int64_t num_edges,
+                                 const int64_t* row_node, int64_t num_rows, const int64_t* group_off, int64_t num_groups,
+                                 const int64_t* sorted_node, const int64_t* sorted_local, const int64_t* row_off,
+                                 int64_t total, int64_t* out_src, int64_t* out_dst, int64_t* out_pos, pangnn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -209,6 +209,12 @@ SIGNATURES = {
     "pangnn_qscore_fwd": (C.c_int, [_p, _p, _p, _i32, _i64, _i64, _p, C.c_double, C.c_double, _p, _i32, _p, _p]),
     # (rowptr, item, score, score_dtype, g, g_dtype, lse, num_segments, num_edges, t, epsilon, gscore, gt, t_parts, stream)
     "pangnn_qscore_bwd": (C.c_int, [_p, _p, _p, _i32, _p, _i32, _p, _i64, _i64, _p, C.c_double, _p, _p, _p, _p]),
+    # induced similarity edges of per-group sub-graphs (csrc/induced_edges.hip): (rowptr, dst, num_nodes, num_edges, row_node,
+    # num_rows, group_off, num_groups, sorted_node, sorted_local, ...) + (row_off, scratch, bytes, stream) /
+    # (row_off, total, out_src, out_dst, out_pos, stream)
+    "pangnn_induced_edges_scratch_bytes": (_i64, [_i64]),
+    "pangnn_induced_edges_count": (C.c_int, [_p, _p, _i64, _i64, _p, _i64, _p, _i64, _p, _p, _p, _p, _i64, _p]),
+    "pangnn_induced_edges_fill": (C.c_int, [_p, _p, _i64, _i64, _p, _i64, _p, _i64, _p, _p, _p, _i64, _p, _p, _p, _p]),
 }
 
 ABI_VERSION = 3          # PANGNN_ABI_VERSION of include/pangnn_hip.h this binding was written against

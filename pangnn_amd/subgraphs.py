@@ -21,6 +21,10 @@ the extra neighbour nodes by ascending position.  Parity with the reference-buil
 checked on GLOBAL ids: same node set, same similarity edge set with the same weights and labels, same
 neighbour edge set (tests/test_construct.py).
 
+Step 3 on a GPU-resident relation is a count / scan / fill pass of HIP that walks the out-edges in place
+(csrc/induced_edges.hip; `induced_edges`), and `groups_per_pass` runs the whole program a slice of the group ids at a
+time, so that no temporary grows with all groups at once; either way the data set is the same bit for bit.
+
 The result is one flat "dataset" whose index tensors already carry dataset-wide node numbering, so a
 mini-batch of consecutive sub-graphs (PyG `Batch.from_data_list`, pangnn.py:152-153) is a pair of
 slices and one subtraction — no per-step collation on the host.
@@ -28,6 +32,7 @@ slices and one subtraction — no per-step collation on the host.
 from __future__ import annotations
 
 import ctypes
+import os
 from types import SimpleNamespace
 from typing import NamedTuple, Optional
 
@@ -86,27 +91,90 @@ def _expand_by_src(rowptr: torch.Tensor, dst_sorted: torch.Tensor, gid: torch.Te
     return gid[rep], dst_sorted[epos], epos, rep
 
 
-def build_subgraphs(num_nodes: int, src, dst, weight, group_id: torch.Tensor, group_member: torch.Tensor,
-                    neighbours: int = 1, labels_group_of: Optional[torch.Tensor] = None, pair_src=None,
-                    pair_dst=None, require_edges_ge_members: bool = False):
-    """(src, dst, weight): normalised similarity relation (self hits already removed).
-    (group_id, group_member): the ortholog groups as parallel arrays (group ids 0..G-1, gene node ids).
-    Labels as in construct.whole_graph: `labels_group_of[node]` or explicit (pair_src, pair_dst)."""
-    dev = src.device
-    n = int(num_nodes)
+def _lookup(lk_sorted: torch.Tensor, lk_local: torch.Tensor, n: int, g: torch.Tensor, v: torch.Tensor):
+    """(found, local id) of node v in group g, from the ascending (group * n + node) keys of every group's nodes"""
+    q = g * n + v
+    if lk_sorted.numel() == 0:
+        return torch.zeros_like(q, dtype=torch.bool), torch.zeros_like(q)
+    pos = torch.searchsorted(lk_sorted, q).clamp_(max=lk_sorted.numel() - 1)
+    return lk_sorted[pos] == q, lk_local[pos]
+
+
+# step 3 of build_subgraphs on a GPU-resident relation is a count / scan / fill pass of HIP (pangnn_induced_edges_count /
+# _fill: nothing of the size of the expanded out-edges is stored); False, or PANGNN_INDUCED_KERNEL=0 in the environment: the
+# index ops a CPU-resident relation always takes (_induced_edges_index_ops, what tests/test_induced_edges.py compares the
+# kernel with)
+INDUCED_KERNEL = os.environ.get("PANGNN_INDUCED_KERNEL", "1") != "0"
+
+
+def _induced_edges_index_ops(n: int, rowptr: torch.Tensor, dst: torch.Tensor, t):
+    """The definition of step 3: every out-edge of every (group, node) row of the tables `t` (_pass_tables) whose target is a
+    node of the same group -> (group, edge position, source local id, target local id), rows in row order, positions
+    ascending inside a row.  Expands ALL out-edges of all rows (four int64 columns, a search result and masks) before it
+    drops those that leave the group."""
+    eg, et, epos, rep = _expand_by_src(rowptr, dst, t.all_g, t.all_n)
+    inside, t_local = _lookup(t.lk_sorted, t.lk_local, n, eg, et)
+    return eg[inside], epos[inside], t.local[rep][inside], t_local[inside]
+
+
+def _induced_edges_kernel(n: int, rowptr: torch.Tensor, dst: torch.Tensor, t):
+    """the same four columns from pangnn_induced_edges_count / _fill (csrc/induced_edges.hip): temporaries of a few words per
+    ROW, one host read-back (the total, which sizes the outputs)"""
+    dev = dst.device
+    rows, groups, e = int(t.all_n.numel()), int(t.node_off_g.numel()) - 1, int(dst.numel())
+    if rows == 0:
+        return tuple(torch.empty(0, dtype=torch.int64, device=dev) for _ in range(4))
+    lib = _lib.load()
+    # each group's node ids in ascending order: lk_sorted is ordered by (group, node) and all_g by group, with the same counts
+    sorted_node = t.lk_sorted - t.all_g * n
+    tables = (rowptr, dst, t.all_n, t.node_off_g, sorted_node, t.lk_local)
+    if any(x.dtype != torch.int64 or not x.is_contiguous() or x.device != dev for x in tables):
+        raise ValueError("the induced-edge pass takes contiguous int64 tables on the relation's device")
+    with _lib.device_guard(dev):
+        need = lib.pangnn_induced_edges_scratch_bytes(rows)
+        if need <= 0:
+            raise _lib.PangnnHipError("pangnn_induced_edges_scratch_bytes failed")
+        row_off = torch.empty(rows + 1, dtype=torch.int64, device=dev)
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+        head = (rowptr.data_ptr(), dst.data_ptr() if e else None, n, e, t.all_n.data_ptr(), rows, t.node_off_g.data_ptr(),
+                groups, sorted_node.data_ptr(), t.lk_local.data_ptr())
+        _lib.check(lib.pangnn_induced_edges_count(*head, row_off.data_ptr(), scratch.data_ptr(), need, _lib.stream_ptr()),
+                   "pangnn_induced_edges_count")
+        total = int(row_off[-1])
+        del scratch
+        out = torch.empty(3, total, dtype=torch.int64, device=dev)
+        _lib.check(lib.pangnn_induced_edges_fill(*head, row_off.data_ptr(), total, _lib.ptr(out[0]) if total else None,
+                                                 _lib.ptr(out[1]) if total else None, _lib.ptr(out[2]) if total else None,
+                                                 _lib.stream_ptr()), "pangnn_induced_edges_fill")
+    per_group = row_off[t.node_off_g[1:]] - row_off[t.node_off_g[:-1]]
+    eg = torch.repeat_interleave(torch.arange(groups, device=dev), per_group, output_size=total)
+    return eg, out[2], out[0], out[1]
+
+
+def induced_edges(n: int, rowptr: torch.Tensor, dst: torch.Tensor, t):
+    """step 3 of build_subgraphs over the node tables `t` of a pass: (group, edge position, source local id, target local id)
+    of every similarity edge with both endpoints inside a sub-graph"""
+    if dst.is_cuda and INDUCED_KERNEL:
+        return _induced_edges_kernel(n, rowptr, dst, t)
+    return _induced_edges_index_ops(n, rowptr, dst, t)
+
+
+def _canonical_relation(n: int, src, dst, weight):
+    """the relation without self hits and out-of-range ids, in (src, dst) order, and its by-source row pointer"""
     ok = (src != dst) & (src >= 0) & (dst >= 0) & (src < n) & (dst < n)
     src, dst, weight = src[ok], dst[ok], weight[ok]
     order = torch.argsort(src * n + dst, stable=True)                 # canonical (src, dst) order
     src, dst, weight = src[order], dst[order], weight[order]
-    rowptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    rowptr = torch.zeros(n + 1, dtype=torch.int64, device=src.device)
     rowptr[1:] = torch.cumsum(torch.bincount(src, minlength=n), 0)
-    has_rows = (rowptr[1:] - rowptr[:-1]) > 0
+    return src, dst, weight, rowptr
 
-    ngroups = int(group_id.max().item()) + 1 if group_id.numel() else 0
-    gsize = torch.bincount(group_id, minlength=ngroups)
-    keep_m = gsize[group_id] > 1                                       # dataset.py:230
-    gid, mem = group_id[keep_m], group_member[keep_m]
 
+def _pass_tables(n: int, rowptr: torch.Tensor, dst: torch.Tensor, gid: torch.Tensor, mem: torch.Tensor, ngroups: int,
+                 neighbours: int):
+    """steps 1 and 2 for the groups 0..ngroups-1 given by their (gid, mem) member rows: every sub-graph's node list in
+    (group, local id) order, the (group, node) -> local id lookup table, and the positional neighbour pairs"""
+    dev = dst.device
     # 1. BFS (get_connected_nodes): keys = gid * n + node
     core = _unique_sorted(gid * n + mem)
     frontier = core
@@ -146,31 +214,31 @@ def build_subgraphs(num_nodes: int, src, dst, weight, group_id: torch.Tensor, gr
     lk = all_g * n + all_n
     lo = torch.argsort(lk)
     lk_sorted, lk_local = lk[lo], local[lo]
+    return SimpleNamespace(all_g=all_g, all_n=all_n, local=local, node_off_g=node_off_g, nodes_per_group=nodes_per_group,
+                           lk_sorted=lk_sorted, lk_local=lk_local, nb_g=nb_g, nb_a=nb_a, nb_b=nb_b)
 
-    def lookup(g, v):
-        q = g * n + v
-        if lk_sorted.numel() == 0:
-            return torch.zeros_like(q, dtype=torch.bool), torch.zeros_like(q)
-        pos = torch.searchsorted(lk_sorted, q).clamp_(max=lk_sorted.numel() - 1)
-        return lk_sorted[pos] == q, lk_local[pos]
+
+def _build_pass(n: int, rel, gid: torch.Tensor, mem: torch.Tensor, gsize: torch.Tensor, neighbours: int, label_of,
+                require_edges_ge_members: bool):
+    """steps 1 to 4 for the groups 0..G-1 of one pass (G = gsize.numel(); `rel`: _canonical_relation): groups do not interact,
+    so a pass is the whole program on a slice of the group ids.  Returns the kept groups (`kept`, pass-local ids) renumbered
+    0..k-1 in the `*_g` columns, with LOCAL node ids in the edge columns."""
+    src, dst, weight, rowptr = rel
+    dev = dst.device
+    ngroups = int(gsize.numel())
+    t = _pass_tables(n, rowptr, dst, gid, mem, ngroups, neighbours)
+    all_g, all_n, nodes_per_group = t.all_g, t.all_n, t.nodes_per_group
 
     # 3. similarity edges with both endpoints inside the sub-graph (build_edge_index on the sub dict)
-    eg, et, epos, rep = _expand_by_src(rowptr, dst, all_g, all_n)
-    inside, t_local = lookup(eg, et)
-    eg, epos, s_local, t_local = eg[inside], epos[inside], local[rep][inside], t_local[inside]
+    eg, epos, s_local, t_local = induced_edges(n, rowptr, dst, t)
     e_w = weight[epos].to(torch.float32)
-    s_glob, t_glob = src[epos], dst[epos]
-    if labels_group_of is not None:
-        a, b = labels_group_of[s_glob], labels_group_of[t_glob]
-        y = ((a == b) & (a >= 0)).to(torch.float32)
-    else:
-        k = torch.cat([pair_src * n + pair_dst, pair_dst * n + pair_src]).unique()
-        y = _isin_sorted(k, s_glob * n + t_glob).to(torch.float32)
+    y = label_of(src[epos], dst[epos])
     edges_per_group = torch.bincount(eg, minlength=ngroups)
 
     # neighbour edges (core v, v +- k), both directions, de-duplicated
-    _, a_local = lookup(nb_g, nb_a)
-    _, b_local = lookup(nb_g, nb_b)
+    nb_g = t.nb_g
+    _, a_local = _lookup(t.lk_sorted, t.lk_local, n, nb_g, t.nb_a)
+    _, b_local = _lookup(t.lk_sorted, t.lk_local, n, nb_g, t.nb_b)
     big = int(nodes_per_group.max().item()) + 1 if ngroups else 1
     und = _unique_sorted(torch.cat([(nb_g * big + a_local) * big + b_local, (nb_g * big + b_local) * big + a_local]))
     ng = torch.div(und, big * big, rounding_mode="floor")
@@ -179,20 +247,76 @@ def build_subgraphs(num_nodes: int, src, dst, weight, group_id: torch.Tensor, gr
     nb_per_group = torch.bincount(ng, minlength=ngroups)
 
     # 4. drop groups (dataset.py:230,235,248,252)
-    sim_rows = torch.zeros(ngroups, dtype=torch.int64, device=dev).index_add_(0, all_g, has_rows[all_n].long())
+    has_rows = (rowptr[all_n + 1] - rowptr[all_n]) > 0
+    sim_rows = torch.zeros(ngroups, dtype=torch.int64, device=dev).index_add_(0, all_g, has_rows.long())
     keep_g = (gsize > 1) & (nodes_per_group > 0) & (sim_rows > 0)
     if require_edges_ge_members:
         keep_g &= edges_per_group >= gsize
     new_gid = torch.cumsum(keep_g.long(), 0) - 1
-    n_sub = int(keep_g.sum())
 
     def compact(g, *cols):
         m = keep_g[g]
         return (new_gid[g[m]],) + tuple(c[m] for c in cols)
 
-    all_g2, all_n2, local2 = compact(all_g, all_n, local)
+    all_g2, all_n2 = compact(all_g, all_n)
     eg2, s2, t2, w2, y2 = compact(eg, s_local, t_local, e_w, y)
     ng2, na2, nb2 = compact(ng, na, nbb)
+    return SimpleNamespace(kept=torch.nonzero(keep_g).view(-1), node_g=all_g2, node_global=all_n2, edge_g=eg2, s=s2, t=t2,
+                           w=w2, y=y2, nb_g=ng2, nb_a=na2, nb_b=nb2)
+
+
+def build_subgraphs(num_nodes: int, src, dst, weight, group_id: torch.Tensor, group_member: torch.Tensor,
+                    neighbours: int = 1, labels_group_of: Optional[torch.Tensor] = None, pair_src=None,
+                    pair_dst=None, require_edges_ge_members: bool = False, groups_per_pass: Optional[int] = None):
+    """(src, dst, weight): normalised similarity relation (self hits already removed).
+    (group_id, group_member): the ortholog groups as parallel arrays (group ids 0..G-1, gene node ids).
+    Labels as in construct.whole_graph: `labels_group_of[node]` or explicit (pair_src, pair_dst).
+    `groups_per_pass`: None builds every group at once; an integer k builds k consecutive group ids at a time and joins the
+    passes — the same data set bit for bit (groups do not interact), with the per-group temporaries (BFS expansion, node and
+    neighbour tables, lookup keys) bounded by what k groups need instead of what all of them need."""
+    dev = src.device
+    n = int(num_nodes)
+    if groups_per_pass is not None and int(groups_per_pass) < 1:
+        raise ValueError(f"groups_per_pass must be a positive number of groups or None, not {groups_per_pass!r}")
+    rel = _canonical_relation(n, src, dst, weight)
+
+    ngroups = int(group_id.max().item()) + 1 if group_id.numel() else 0
+    gsize = torch.bincount(group_id, minlength=ngroups)
+    keep_m = gsize[group_id] > 1                                       # dataset.py:230
+    gid, mem = group_id[keep_m], group_member[keep_m]
+
+    if labels_group_of is not None:
+        def label_of(s_glob, t_glob):
+            a, b = labels_group_of[s_glob], labels_group_of[t_glob]
+            return ((a == b) & (a >= 0)).to(torch.float32)
+    else:
+        pair_keys = torch.cat([pair_src * n + pair_dst, pair_dst * n + pair_src]).unique()
+
+        def label_of(s_glob, t_glob):
+            return _isin_sorted(pair_keys, s_glob * n + t_glob).to(torch.float32)
+
+    if groups_per_pass is None or ngroups == 0:
+        parts = [_build_pass(n, rel, gid, mem, gsize, int(neighbours), label_of, require_edges_ge_members)]
+    else:
+        parts, k, n_kept = [], int(groups_per_pass), 0
+        for g0 in range(0, ngroups, k):
+            g1 = min(g0 + k, ngroups)
+            m = (gid >= g0) & (gid < g1)
+            p = _build_pass(n, rel, gid[m] - g0, mem[m], gsize[g0:g1], int(neighbours), label_of, require_edges_ge_members)
+            # join: group ids back to the caller's, sub-graph numbers running on across the passes
+            p.kept, p.node_g, p.edge_g, p.nb_g = p.kept + g0, p.node_g + n_kept, p.edge_g + n_kept, p.nb_g + n_kept
+            n_kept += int(p.kept.numel())
+            parts.append(p)
+
+    def joined(name):
+        return getattr(parts[0], name) if len(parts) == 1 else torch.cat([getattr(p, name) for p in parts])
+
+    kept = joined("kept")
+    n_sub = int(kept.numel())
+    all_g2, all_n2 = joined("node_g"), joined("node_global")
+    eg2, s2, t2, w2, y2 = (joined(c) for c in ("edge_g", "s", "t", "w", "y"))
+    ng2, na2, nb2 = joined("nb_g"), joined("nb_a"), joined("nb_b")
+    del parts
     node_off = torch.zeros(n_sub + 1, dtype=torch.int64, device=dev)
     node_off[1:] = torch.cumsum(torch.bincount(all_g2, minlength=n_sub), 0)
     edge_off = torch.zeros(n_sub + 1, dtype=torch.int64, device=dev)
@@ -204,7 +328,7 @@ def build_subgraphs(num_nodes: int, src, dst, weight, group_id: torch.Tensor, gr
         num_graphs=n_sub, node_off=node_off, edge_off=edge_off, nb_off=nb_off, node_global=all_n2,
         edge_index=torch.stack([s2 + node_off[eg2], t2 + node_off[eg2]]), edge_attr=w2, y=y2,
         neighbour_edge_index=torch.stack([na2 + node_off[ng2], nb2 + node_off[ng2]]),
-        group_of_graph=torch.nonzero(keep_g).view(-1))
+        group_of_graph=kept)
 
 
 # batches of a GPU-resident data set are collated by one HIP launch (pangnn_collate_subgraphs); False: the index ops
